@@ -12,8 +12,12 @@ Tiers
   e2e:   embed -> 50-step DDIM sampling (CFG) -> 50-step DDIM inversion -> extract with the SD2.1-shaped UNet
          (synthetic weights).  Roofline: MFMA.   
 
-Prints ONE JSON line on rank 0.  The CPU baseline leg (rank 0, N == 1 only) times the oracle's reference-shaped scalar
-port on a bounded sample; it is a reported baseline, never the thing measured.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps of the headline tier (e2e, or the tier
+--tier names) and prints the line; --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy.
+--full adds everything else, as a default run measured it before: the codec tier riding along with e2e (`tiers`), the
+board's clock / power during the timed region, the instrumented step behind the roofline objects, and the CPU baseline
+leg (rank 0, N == 1 only), which times the oracle's reference-shaped scalar port on a bounded sample; it is a reported
+baseline, never the thing measured.
 """
 import argparse
 import json
@@ -62,6 +66,11 @@ def parse():
     ap.add_argument("--preflight", action="store_true", help="every rank: device check, RCCL init, one broadcast + all_gather_into_tensor + all_reduce under a hard "
                                                              "time limit (GSW_PREFLIGHT_TIMEOUT_S, default 120); rank 0 prints ONE JSON line; a failing stage is named and exits 3")
     ap.add_argument("--launcher-selftest", action="store_true", help="only rendezvous, all-gather the ranks and print them (GSW_BENCH_BACKEND=gloo on a CPU host)")
+    ap.add_argument("--full", action="store_true", help="also the codec tier next to e2e, board clock / power, the roofline objects (one instrumented step after the "
+                                                        "timed region) and the CPU baseline; a plain run measures the headline tier only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline tier computed in its last timed step as DIR/<name>.npy (float32 / float64, <= 64 MB in all: a fixed, seeded "
+                         "sample of images when the whole batch is larger)")
     a = ap.parse_args()
     if a.steps is None:
         a.steps = 50 if a.tier == "codec" else 2
@@ -163,6 +172,27 @@ def cpu_baseline(n_images: int, message_length: int, all_cores: bool = True, win
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(dirname: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: `arrays` (name -> host array of the last timed step, images along axis 0) as dirname/<name>.npy, float64 kept, anything else as
+    float32.  Over `limit` bytes in all, every array keeps the same fraction of its images, chosen by a fixed seed (the same indices for arrays of
+    the same batch), so two builds dump the same sample."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    frac = min(1.0, (limit - 4096 * len(arrays)) / total) if total else 1.0
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        if frac < 1.0 and v.ndim > 0 and v.shape[0] > 1:
+            k = max(1, int(v.shape[0] * frac))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], k, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} to {dirname}" + (f" (a seeded {frac:.3g} of the images of each)" if frac < 1.0 else ""),
+          file=sys.stderr)
+
+
 def self_launch(args) -> int:
     """`python bench.py --gpus N` from a bare shell (no torch.distributed.run around it): start N rank processes -- one per GPU, RCCL over
     127.0.0.1 -- poll them, stop the siblings as soon as one fails, and return the worst exit code.  The parent never touches HIP (it does
@@ -213,8 +243,9 @@ def ranks_seen(world, local_rank):
     return [int(v) for v in out.tolist()]
 
 
-def run_codec(args, rank, world, local_rank, steps, warmup, cpu_codec=None):
-    """Codec tier: returns the result dict on rank 0 (None elsewhere)."""
+def run_codec(args, rank, world, local_rank, steps, warmup, cpu_codec=None, outputs=None):
+    """Codec tier: returns the result dict on rank 0 (None elsewhere); `outputs` (a dict), when given, receives the host copies of what the last timed
+    step computed."""
     import torch
     import torch.distributed as dist
     import gswm_amd
@@ -286,6 +317,8 @@ def run_codec(args, rank, world, local_rank, steps, warmup, cpu_codec=None):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if outputs is not None:
+        outputs.update(embedded_latents=z32.cpu(), bits=bits.cpu(), flags=flags.cpu())
 
     # correctness gate (outside the timed region): lossless => every bit of every image
     want = torch.frombuffer(bytearray(k), dtype=torch.uint8).to(dev)
@@ -348,7 +381,7 @@ def run_codec(args, rank, world, local_rank, steps, warmup, cpu_codec=None):
                          "kernels": {"gsw_embed_kernel": {"bytes": bytes_embed, "avg_us": t_embed * 1e6, "GBps": bytes_embed / t_embed / 1e9},
                                      "gsw_extract_wave_kernel": {"bytes": bytes_extract, "avg_us": t_extract * 1e6, "GBps": bytes_extract / t_extract / 1e9}}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_codec if cpu_codec is not None else cpu_baseline(args.cpu_images, M, all_cores=False)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
         else:
@@ -374,7 +407,7 @@ def main():
         from gswm_amd import dist as gdist
         sys.exit(gdist.preflight_main(os.environ.get("GSW_BENCH_BACKEND", "nccl"), float(os.environ.get("GSW_PREFLIGHT_TIMEOUT_S", "120"))))
     cpu_codec = None
-    if args.gpus == 1 and not args.no_cpu_baseline and not args.launcher_selftest and args.tier in ("both", "codec"):
+    if args.full and args.gpus == 1 and not args.no_cpu_baseline and not args.launcher_selftest and args.tier in ("both", "codec"):
         cpu_codec = cpu_baseline(args.cpu_images, args.message_length)        # before any HIP call: the all-cores leg starts worker processes
     rank, world, local_rank = init_dist(args)
     import torch.distributed as dist
@@ -386,13 +419,16 @@ def main():
             dist.destroy_process_group()
         return
     codec_res = e2e_res = None
-    if args.tier in ("both", "codec"):
+    outputs = {} if args.dump_outputs else None            # the headline tier's last timed step, host copies
+    if args.tier == "codec" or (args.tier == "both" and args.full):
         k = args.steps if args.tier == "codec" else args.codec_steps
         w = args.warmup if args.tier == "codec" else 5
-        codec_res = run_codec(args, rank, world, local_rank, k, w, cpu_codec)
+        codec_res = run_codec(args, rank, world, local_rank, k, w, cpu_codec, outputs if args.tier == "codec" else None)
     if args.tier in ("both", "e2e"):
         from bench_e2e import run_e2e
-        e2e_res = run_e2e(args, rank, world, local_rank)
+        e2e_res = run_e2e(args, rank, world, local_rank, outputs)
+    if rank == 0 and outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
     if rank == 0:
         if args.tier == "codec":
             out = codec_res

@@ -111,7 +111,9 @@ def _bucket_scalars(fam, dt_instr):
     return out
 
 
-def run_e2e(args, rank, world, local_rank):
+def run_e2e(args, rank, world, local_rank, outputs=None):
+    """e2e tier: returns the result dict on rank 0 (None elsewhere); `outputs` (a dict), when given, receives the host copies of what the last timed step
+    computed.  The board sampler, the instrumented step behind the roofline objects and the CPU baseline run with --full only."""
     import torch
     import torch.distributed as dist
     import gswm_amd
@@ -133,11 +135,12 @@ def run_e2e(args, rank, world, local_rank):
     if os.environ.get("GSW_CHANNELS_LAST", "0") == "1":   # NCHW measured faster here (377 vs 343 TFLOP/s at B=64)
         model = model.to(memory_format=torch.channels_last)
     h, w = args.height // 8, args.width // 8
-    flops_row = U.count_flops_per_image(model, h, w)
+    full = args.full
+    flops_row = U.count_flops_per_image(model, h, w) if full else 0
     from gswm_amd.graph import graphed
     eps = graphed(model, clone_output=False)                                    # forwards of <= 32 rows replay a captured HIP graph (GSW_GRAPH=never: eager A/B)
     tm = TimedModel(eps, flops_row)
-    tm.prefix_flops_per_row = float(U.count_cfg_shared_prefix_flops(model, h, w)) if U.CFG_SHARED_PREFIX else 0.0
+    tm.prefix_flops_per_row = float(U.count_cfg_shared_prefix_flops(model, h, w)) if U.CFG_SHARED_PREFIX and full else 0.0
     g = torch.Generator(device="cpu").manual_seed(1)
     ctx_uncond = (torch.randn(1, 77, ctx_dim, generator=g) * 1.0).to(dev, dtype)        # stands for CLIP("")
     ctx_text = (torch.randn(B, 77, ctx_dim, generator=g) * 1.0).to(dev, dtype)          # stands for CLIP(prompt)
@@ -174,17 +177,16 @@ def run_e2e(args, rank, world, local_rank):
             z_T = pipe.embed(B, seed=params["seed"], image_index0=idx0)
             x0 = pipe.generate(z_T, ctx_text, 7.5)
             with torch.no_grad():
-                for chunk in x0.split(args.vae_chunk):
-                    imaging.tensor_to_image(V.latents_to_img(chunk, vae))
-            return z_T, x0, None, None
+                images = [imaging.tensor_to_image(V.latents_to_img(chunk, vae)) for chunk in x0.split(args.vae_chunk)]
+            return z_T, x0, None, None, {"images_u8": images}
         if vae is None:
-            return pipe.roundtrip(B, ctx_text, seed=params["seed"], image_index0=idx0, guidance_scale=7.5)
+            return (*pipe.roundtrip(B, ctx_text, seed=params["seed"], image_index0=idx0, guidance_scale=7.5), {})
         z_T = pipe.embed(B, seed=params["seed"], image_index0=idx0)
         x0 = pipe.generate(z_T, ctx_text, 7.5)
         with torch.no_grad():
-            image_stages(x0)
+            x0_image = image_stages(x0)
         bits, flags = pipe.invert_and_extract(x0)
-        return z_T, x0, bits, flags
+        return z_T, x0, bits, flags, {"latents_through_image_stages": x0_image}
 
     for i in range(args.warmup):
         step(i)
@@ -198,13 +200,15 @@ def run_e2e(args, rank, world, local_rank):
     matched = torch.zeros((), dtype=torch.int64, device=dev)
     flagged = torch.zeros((), dtype=torch.int64, device=dev)
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]      # step boundaries (recorded, never waited on inside the region)
-    from bench_board import BoardSampler
-    board = BoardSampler(local_rank)               # shader clock + board power of this rank's device while the region runs (a 20 Hz sysfs reader thread)
-    board.__enter__()
+    board = None
+    if full:
+        from bench_board import BoardSampler
+        board = BoardSampler(local_rank)           # shader clock + board power of this rank's device while the region runs (a 20 Hz sysfs reader thread)
+        board.__enter__()
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        z_T, x0, bits, flags = step(args.warmup + i)
+        z_T, x0, bits, flags, extra = step(args.warmup + i)
         if bits is not None:
             matched += codec.bit_matches(bits, M, params["message"]).sum()
             flagged += (flags != 0).sum()
@@ -214,7 +218,13 @@ def run_e2e(args, rank, world, local_rank):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    board.__exit__()
+    if board is not None:
+        board.__exit__()
+    if outputs is not None:
+        outputs.update(embedded_latents=z_T.cpu(), sampled_latents=x0.cpu())
+        if bits is not None:
+            outputs.update(bits=bits.cpu(), flags=flags.cpu())
+        outputs.update({k: (torch.cat(v) if isinstance(v, list) else v).cpu() for k, v in extra.items()})
     if txt2img:
         # nothing was extracted inside the region: the lossless gate of this workload is the embedded Z_s_T of the last step read back by the extract kernel
         bits, flags = codec.extract_batch(z_T, params["key"], params["nonce"], M)
@@ -224,30 +234,31 @@ def run_e2e(args, rank, world, local_rank):
     if vae is not None:
         fallbacks.update({"vae: " + k: v for k, v in V.FALLBACKS.items()})
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    # ONE more step, instrumented (HIP events around every UNet forward and every convolution / matmul launch, on the stream they are
-    # launched on): it feeds the roofline objects and stays OUT of the timed region above -- the events cost launch slots
-    from gswm_amd import pf as _pf
-    # A graph replay executes no Python, so the per-launch events would only see the VAE: whenever the timed region replayed graphs the instrumented
-    # step runs the forwards EAGERLY (same kernels, same arguments -- tests/test_gpu_graph.py -- but with the host launch path in between) and the
-    # line says so; fallbacks baked into a captured graph are reported from the capture (graph.GraphedEpsModel.capture_fallbacks).
-    conv_timer = _pf.ConvTimer()
-    tm.enabled = True
-    _pf.CONV_TIMER = conv_timer
-    replayed = eps.stats["replays"] > 0
-    mode_before, eps.mode = eps.mode, ("never" if replayed else eps.mode)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    step(args.warmup + args.steps)
-    e1.record()
-    torch.cuda.synchronize()
-    eps.mode = mode_before
-    _pf.CONV_TIMER = None
-    tm.enabled = False
-    measured_in = ("one instrumented EAGER step after the timed region (the timed region replays HIP graphs of the same launches; event times here include the "
-                   "host launch gaps, so per-launch rates are lower bounds)" if replayed else "one instrumented step after the timed region")
+    if full:
+        # ONE more step, instrumented (HIP events around every UNet forward and every convolution / matmul launch, on the stream they are
+        # launched on): it feeds the roofline objects and stays OUT of the timed region above -- the events cost launch slots
+        from gswm_amd import pf as _pf
+        # A graph replay executes no Python, so the per-launch events would only see the VAE: whenever the timed region replayed graphs the instrumented
+        # step runs the forwards EAGERLY (same kernels, same arguments -- tests/test_gpu_graph.py -- but with the host launch path in between) and the
+        # line says so; fallbacks baked into a captured graph are reported from the capture (graph.GraphedEpsModel.capture_fallbacks).
+        conv_timer = _pf.ConvTimer()
+        tm.enabled = True
+        _pf.CONV_TIMER = conv_timer
+        replayed = eps.stats["replays"] > 0
+        mode_before, eps.mode = eps.mode, ("never" if replayed else eps.mode)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        step(args.warmup + args.steps)
+        e1.record()
+        torch.cuda.synchronize()
+        eps.mode = mode_before
+        _pf.CONV_TIMER = None
+        tm.enabled = False
+        measured_in = ("one instrumented EAGER step after the timed region (the timed region replays HIP graphs of the same launches; event times here include the "
+                       "host launch gaps, so per-launch rates are lower bounds)" if replayed else "one instrumented step after the timed region")
+        dt_instr = e0.elapsed_time(e1) * 1e-3
     for k_, v_ in getattr(eps, "capture_fallbacks", {}).items():
         fallbacks["captured graph: " + k_] = fallbacks.get("captured graph: " + k_, 0) + v_
-    dt_instr = e0.elapsed_time(e1) * 1e-3
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -276,8 +287,10 @@ def run_e2e(args, rank, world, local_rank):
                         "steps": len(step_ms), "p50_per_image_s": step_ms[len(step_ms) // 2] * 1e-3 / B},
             "eps_model_launch_path": {"mode": eps.mode, "graph_max_rows": eps.max_rows, **eps.stats},
         }
-        cs = conv_timer.summary()
         out["fallbacks_off_the_hand_written_path"] = fallbacks
+        if not full:
+            return out
+        cs = conv_timer.summary()
         # what the board did during the timed region: under the 1400 W limit the MFMA-heavy kernels of this path run at 1.7-2.0 GHz on random operands
         # (profiles/r04h_power_cap_probe.txt), so the fractions below -- against the 2.4 GHz peak -- come with the clock they were measured at
         out["board"] = board.summary()

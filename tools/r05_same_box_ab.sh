@@ -18,7 +18,7 @@ GSWM_LIB=$OLD timeout 300 python3 tools/unet_forward_bench.py 64 > $O/unet_forwa
 timeout 300 python3 tools/unet_forward_bench.py 64 > $O/unet_forward_b64_new.txt 2>&1; tail -1 $O/unet_forward_b64_new.txt
 for v in old new old new; do
   if [ $v = old ]; then export GSWM_LIB=$OLD; else unset GSWM_LIB; fi
-  timeout 900 python3 bench.py --tier e2e --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_e2e_b64_$v.json 2> $O/bench_e2e_b64_$v.err; echo "b64 $v rc=$?"
+  timeout 900 python3 bench.py --full --tier e2e --steps 1 --warmup 1 --no-cpu-baseline > $O/bench_e2e_b64_$v.json 2> $O/bench_e2e_b64_$v.err; echo "b64 $v rc=$?"
   python3 -c "
 import json
 d=json.load(open('$O/bench_e2e_b64_$v.json')); r=d['roofline']; print('$v', d['value'], r['achieved'], r['conv3x3_tflops'], r['dense_tflops'], d['board']['sclk_mhz_mean'], d['board']['power_w_mean'])"
