@@ -5,11 +5,11 @@ with G = W+3 zero guard rows at both ends of the allocation.  A 3x3 tap is then 
 single GEMM whose operand loader needs no boundary logic (see the kernel header)."""
 from __future__ import annotations
 
+import ctypes as _C
+import os
 from typing import Optional
 
 import torch
-
-import ctypes as _C
 
 from . import _native as N
 from .codec import _dt, _stream_ptr
@@ -361,8 +361,8 @@ def _gn_workspace(device, B, groups, C=0):
 
 # One-launch GroupNorm for small batches (gsw_groupnorm_pf_fused: a workgroup per (image, group) keeps the group in registers): used while the grid stays
 # a few hundred workgroups -- beyond that the two coalesced passes (or the producer's column records) win
-GN_FUSED_MAX_WGS = int(__import__("os").environ.get("GSW_GN_FUSED_MAX_WGS", "512"))
-GN_FUSED_MAX_PIXELS = int(__import__("os").environ.get("GSW_GN_FUSED_MAX_PIXELS", "1024"))      # measured on one image: 32 x 32 and below 5.5-10 us against ~13.5 for the
+GN_FUSED_MAX_WGS = int(os.environ.get("GSW_GN_FUSED_MAX_WGS", "512"))
+GN_FUSED_MAX_PIXELS = int(os.environ.get("GSW_GN_FUSED_MAX_PIXELS", "1024"))      # measured on one image: 32 x 32 and below 5.5-10 us against ~13.5 for the
                                                                                                  # two launches; 64 x 64 22 us (4-byte accesses 640 bytes apart)
 
 
@@ -431,6 +431,11 @@ def groupnorm_pf(x: PF, gamma: torch.Tensor, beta: torch.Tensor, groups: int, ep
     return res
 
 
+def gn_pf(x: PF, norm, act: bool = True, tokens: bool = False):
+    """groupnorm_pf with the parameters of an nn.GroupNorm"""
+    return groupnorm_pf(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act=act, tokens=tokens)
+
+
 def pack_geglu_weight(w: torch.Tensor, b: Optional[torch.Tensor]):
     """GEGLU projection [2I, K] (rows: I value then I gate) -> rows interleaved per 16-row block as [8 value | 8 gate] of the same 8
     outputs: in the MFMA accumulator layout value and gate of one output then sit 32 lanes apart in the same register (the engine's
@@ -451,7 +456,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], *, re
 
 
 GEMM_MODES = {"plain": 0, "geglu": 1, "trans": 2, "tok2pf": 3}
-SMALL_GEMM_MAX_ROWS = int(__import__("os").environ.get("GSW_SMALL_GEMM_MAX_ROWS", "128"))      # dense linears of at most that many rows run on gsw_gemm_small (0: never)
+SMALL_GEMM_MAX_ROWS = int(os.environ.get("GSW_SMALL_GEMM_MAX_ROWS", "128"))      # dense linears of at most that many rows run on gsw_gemm_small (0: never)
 SMALL_GEMM_MAX_K = 2560
 
 
@@ -551,7 +556,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
 
 # ---- LayerNorm folded into the consuming GEMM (gsw_gemm_ln): LN(x) W^T + b = rstd (x W'^T) + nrm u + v, W' = W diag(gamma), u = W' 1, v = W beta + b
 FOLD_LN = True
-FOLD_LN_MIN_ROWS = int(__import__("os").environ.get("GSW_FOLD_LN_MIN_ROWS", "1024"))       # below that the consumers would rather take the split-K form, which the folded epilogue does not have
+FOLD_LN_MIN_ROWS = int(os.environ.get("GSW_FOLD_LN_MIN_ROWS", "1024"))       # below that the consumers would rather take the split-K form, which the folded epilogue does not have
 
 
 def ln_stat(x: torch.Tensor, eps: float) -> Optional[torch.Tensor]:
@@ -714,11 +719,13 @@ def conv3x3_res_pf(x: PF, w_cat: torch.Tensor, bias: Optional[torch.Tensor], *, 
 ATTN_HEAD_DIMS = (40, 64, 80, 160)
 
 
+def half_gpu(x: torch.Tensor) -> bool:
+    """a device tensor of fp16 / bf16: what the hand-written kernels take"""
+    return x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)
+
+
 def attention_ok(x: torch.Tensor, heads: int, head_dim: int, n_q: int, n_k: int) -> bool:
-    return x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and head_dim in ATTN_HEAD_DIMS and n_q >= 1 and n_k % 8 == 0
-
-
-attention_hd64_ok = attention_ok
+    return half_gpu(x) and head_dim in ATTN_HEAD_DIMS and n_q >= 1 and n_k % 8 == 0
 
 
 def dup_pf(x: "PF") -> "PF":

@@ -16,11 +16,16 @@ CPU baseline) and are counted in `FALLBACKS` when a GPU call has to use them.
 from __future__ import annotations
 
 import math
+import os
+import warnings
 from typing import Optional, Sequence
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _native as N
+from . import checkpoint, codec, graph, pf, xattn
 
 
 # Fused HIP elementwise kernels (libgswm: gsw_groupnorm_silu, gsw_geglu) replace torch's GroupNorm -> SiLU (-> broadcast add)
@@ -36,7 +41,6 @@ def _fusable(x: torch.Tensor) -> bool:
 def gn_act(x: torch.Tensor, norm: nn.GroupNorm, act: bool = True, pre_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """act(GroupNorm(x + pre_bias[:, :, None, None]))"""
     if _fusable(x):
-        from . import codec
         return codec.groupnorm_silu(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act=act, pre_bias=pre_bias)
     if pre_bias is not None:
         x = x + pre_bias[:, :, None, None]
@@ -52,8 +56,7 @@ USE_PF = True
 
 
 def _pw(conv: nn.Conv2d) -> torch.Tensor:
-    from .pf import cached, pack_conv_weight
-    return cached(conv, "_gsw_packed", (conv.weight,), lambda: pack_conv_weight(conv.weight.detach()))
+    return pf.cached(conv, "_gsw_packed", (conv.weight,), lambda: pf.pack_conv_weight(conv.weight.detach()))
 
 
 UPSAMPLE_SUBPIXEL = True   # Upsample2D = four 2x2 convolutions of the low-resolution tensor (gsw_conv_up2x_pf) instead of upsample + 3x3
@@ -76,7 +79,7 @@ FALLBACKS = {}        # (reason -> count) of GPU half-precision calls that left 
 # Leaving the hand-written path (a shape off the engine's K % 64 / N % 8 grid, attention keys % 8, a lattice the padded-flat layout does not take) RAISES by default: a
 # 200 x 136 image must not silently run a different backend (hipBLASLt / MIOpen / aotriton).  GSW_STRICT_KERNELS=0, `--strict_kernels 0` of the harness or
 # `unet.STRICT = vae.STRICT = False` opt into the library kernels; every such call is then counted in FALLBACKS and warned about once per reason.
-STRICT = __import__("os").environ.get("GSW_STRICT_KERNELS", "1") != "0"
+STRICT = os.environ.get("GSW_STRICT_KERNELS", "1") != "0"
 
 
 def _note_fallback(why: str):
@@ -84,14 +87,13 @@ def _note_fallback(why: str):
         raise RuntimeError("gswm unet (strict kernels): " + why + " -- this call would run a library kernel (hipBLASLt / MIOpen / SDPA); "
                            "pass --strict_kernels 0 to allow it")
     if why not in FALLBACKS:       # loud, once per reason: a GPU run that leaves the hand-written kernels should never be silent
-        import warnings
         warnings.warn("gswm unet: " + why, RuntimeWarning, stacklevel=3)
     FALLBACKS[why] = FALLBACKS.get(why, 0) + 1
 
 
 def _own_gemm_ok(x: torch.Tensor, K: int, N: int) -> bool:
     """The matmul engine takes fp16 / bf16 device tensors with K % 64 == 0 and N % 8 == 0 (every SD 1.x / 2.x linear)."""
-    if not (OWN_GEMM and USE_PF and FUSED_KERNELS and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)):
+    if not (OWN_GEMM and USE_PF and FUSED_KERNELS and pf.half_gpu(x)):
         return False
     if K % 64 or N % 8:
         _note_fallback(f"linear K={K} N={N}: library GEMM")
@@ -111,9 +113,8 @@ def _lin(x: torch.Tensor, lin: nn.Linear, resid: Optional[torch.Tensor] = None, 
     """Linear (+ residual in the epilogue) on the matmul engine, else torch.  out: written in place (same shape, contiguous).
     rowstats: the launch also leaves the row records a following LayerNorm can be folded from (pf.ln_stat) on the result."""
     if _own_gemm_ok(x, lin.in_features, lin.out_features):
-        from .pf import gemm
         w, b = _wb(lin, x)
-        return gemm(x.contiguous(), w, b, resid=None if resid is None else resid.contiguous(), out=out, rowstats=rowstats)
+        return pf.gemm(x.contiguous(), w, b, resid=None if resid is None else resid.contiguous(), out=out, rowstats=rowstats)
     y = lin(x)
     y = y if resid is None else y + resid
     return y if out is None else out.copy_(y)
@@ -123,17 +124,11 @@ def _lin_t(x: torch.Tensor, lin: nn.Linear, out: Optional[torch.Tensor] = None) 
     """[B, S, K] -> (lin(x))^T = [B, N, S]: the value projection in the layout the attention kernel consumes."""
     b, n, _ = x.shape
     if _own_gemm_ok(x, lin.in_features, lin.out_features) and n % 8 == 0:
-        from .pf import gemm
         w, bias = _wb(lin, x)
-        return gemm(x.contiguous(), w, bias, mode="trans", tokens=n, out=out)
+        return pf.gemm(x.contiguous(), w, bias, mode="trans", tokens=n, out=out)
     vt = torch.bmm(lin.weight.unsqueeze(0).expand(b, -1, -1), x.transpose(1, 2))
     vt = vt if lin.bias is None else vt + lin.bias[None, :, None]
     return vt if out is None else out.copy_(vt)
-
-
-def _gn_pf(x, norm: nn.GroupNorm, act=True, tokens=False):
-    from .pf import groupnorm_pf
-    return groupnorm_pf(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act=act, tokens=tokens)
 
 
 def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0) -> torch.Tensor:
@@ -157,10 +152,18 @@ class TimestepEmbedding(nn.Module):
 class TembRows:
     """silu(time embedding) [B, temb] and, per resnet, its time_emb_proj output as a column slice [B, cout] of ONE GEMM over the concatenated
     projection weights (22 resnets -> one launch instead of 22; the convolution epilogue reads the slice through its row stride)."""
-    __slots__ = ("act", "rows", "table")
+    __slots__ = ("act", "rows", "table", "widths")
 
-    def __init__(self, act, rows, table=None):
-        self.act, self.rows, self.table = act, rows, table      # table: the [B, sum of channels] matrix the row slices view
+    def __init__(self, act, table, widths):
+        """table: the [B, sum of channels] matrix; widths: (key, channels) per resnet in column order (key: id(resnet)) -> rows[key] = its column slice"""
+        self.act, self.table, self.widths, self.rows, off = act, table, widths, {}, 0
+        for key, n in widths:
+            self.rows[key] = table[:, off:off + n]
+            off += n
+
+    def doubled(self) -> "TembRows":
+        """the rows of B images -> of the 2B images of the doubled batch"""
+        return TembRows(None if self.act is None else torch.cat([self.act, self.act], dim=0), torch.cat([self.table, self.table], dim=0), self.widths)
 
 
 class ResnetBlock2D(nn.Module):
@@ -181,25 +184,23 @@ class ResnetBlock2D(nn.Module):
     def forward_pf(self, x, temb_act, x2=None):
         """x2: optional second PF tensor -- the block's input is the channel concatenation [x | x2] (a skip connection), which is
         never materialised: GroupNorm and the shortcut read both tensors in place."""
-        from .pf import PF, conv_pf, conv3x3_res_pf, conv3x3_res_fusable, groupnorm_pf2
         cout = self.conv2.out_channels
-        fuse = self.conv_shortcut is not None and conv3x3_res_fusable(x, cout) and (x2 is None or x2.C % 64 == 0)
+        fuse = self.conv_shortcut is not None and pf.conv3x3_res_fusable(x, cout) and (x2 is None or x2.C % 64 == 0)
         if x2 is not None and not fuse:
-            x, x2 = PF(torch.cat([x.buf, x2.buf], dim=1), x.B, x.H, x.W, x.C + x2.C), None
-        n1 = groupnorm_pf2(x, x2, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, act=True)
+            x, x2 = pf.PF(torch.cat([x.buf, x2.buf], dim=1), x.B, x.H, x.W, x.C + x2.C), None
+        n1 = pf.groupnorm_pf2(x, x2, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, act=True)
         rowbias = temb_act.rows[id(self)] if isinstance(temb_act, TembRows) else _lin(temb_act, self.time_emb_proj).contiguous()
-        h = conv_pf(n1, _pw(self.conv1), self.conv1.bias, rowbias=rowbias, gn_only=True)       # read by norm2 and nothing else: no border zeroing when it wrote records
-        h = _gn_pf(h, self.norm2)
+        h = pf.conv_pf(n1, _pw(self.conv1), self.conv1.bias, rowbias=rowbias, gn_only=True)       # read by norm2 and nothing else: no border zeroing when it wrote records
+        h = pf.gn_pf(h, self.norm2)
         if self.conv_shortcut is None:
-            return conv_pf(h, _pw(self.conv2), self.conv2.bias, resid=x)                 # residual add in the GEMM epilogue
+            return pf.conv_pf(h, _pw(self.conv2), self.conv2.bias, resid=x)                 # residual add in the GEMM epilogue
         if not fuse:
-            sc = conv_pf(x, _pw(self.conv_shortcut), self.conv_shortcut.bias, ksize=1)
-            return conv_pf(h, _pw(self.conv2), self.conv2.bias, resid=sc)
-        from .pf import cached
-        c = cached(self, "_gsw_res", (self.conv2.weight, self.conv2.bias, self.conv_shortcut.weight, self.conv_shortcut.bias),
+            sc = pf.conv_pf(x, _pw(self.conv_shortcut), self.conv_shortcut.bias, ksize=1)
+            return pf.conv_pf(h, _pw(self.conv2), self.conv2.bias, resid=sc)
+        c = pf.cached(self, "_gsw_res", (self.conv2.weight, self.conv2.bias, self.conv_shortcut.weight, self.conv_shortcut.bias),
                    lambda: (torch.cat([_pw(self.conv2), self.conv_shortcut.weight.detach()[:, :, 0, 0]], dim=1).contiguous(),      # [N, 9*C | C_shortcut]
                             (self.conv2.bias.detach() + self.conv_shortcut.bias.detach()).contiguous()))                           # summed biases
-        return conv3x3_res_pf(h, c[0], c[1], x1=x, x2=x2)                                # conv2 + conv_shortcut in one GEMM
+        return pf.conv3x3_res_pf(h, c[0], c[1], x1=x, x2=x2)                                # conv2 + conv_shortcut in one GEMM
 
 
 def _padded_ctx(ctx: torch.Tensor):
@@ -222,6 +223,11 @@ def _padded_ctx(ctx: torch.Tensor):
     return pad, n
 
 
+def _padded_keys(ctx: torch.Tensor) -> int:
+    """key count of _padded_ctx(ctx)"""
+    return (ctx.shape[1] + 63) // 64 * 64
+
+
 class Attention(nn.Module):
     def __init__(self, dim, ctx_dim, heads, head_dim):
         super().__init__()
@@ -233,6 +239,24 @@ class Attention(nn.Module):
         self.to_k = nn.Linear(ctx_dim, inner, bias=False)
         self.to_v = nn.Linear(ctx_dim, inner, bias=False)
         self.to_out = nn.ModuleList([nn.Linear(inner, dim)])
+
+    @property
+    def head_dim(self) -> int:
+        return self.to_q.out_features // self.heads
+
+    def _no_qkv_bias(self) -> bool:
+        return self.to_q.bias is None and self.to_k.bias is None and self.to_v.bias is None
+
+    def _wcat(self, which: str) -> torch.Tensor:
+        """The projection weights named by the letters of `which` ("qk" | "qkv") stacked row-wise, cached on the module (pf.cached, keyed by those weights)."""
+        ws = tuple(getattr(self, "to_" + c).weight for c in which)
+        return pf.cached(self, "_gsw_w" + which, ws, lambda: torch.cat([w.detach() for w in ws], dim=0).contiguous())
+
+    def _folded(self, which: str, norm: nn.LayerNorm):
+        """pf.fold_ln_weights of the projection(s) "q" | "qk" | "v" behind LayerNorm `norm`, cached on the module (keyed by the weights and the norm's parameters)."""
+        ws = tuple(getattr(self, "to_" + c).weight for c in which)
+        return pf.cached(self, "_gsw_ln_" + which, ws + (norm.weight, norm.bias),
+                         lambda: pf.fold_ln_weights(ws[0].detach() if len(ws) == 1 else torch.cat([w.detach() for w in ws], dim=0), None, norm.weight, norm.bias))
 
     def context_kv(self, src: torch.Tensor):
         """Cross-attention keys / values^T of a (padded) context tensor: they depend on the context only, so they are computed once per
@@ -254,21 +278,17 @@ class Attention(nn.Module):
         """attn(LayerNorm(x)) + resid with the LayerNorm folded into the projections that consume it (pf.gemm_ln): x is the RAW residual stream,
         stat its per-row (rstd, -rstd mean).  Self-attention: q | k and V^T; cross-attention: q (keys / values come from the context).
         project=False: the attention output BEFORE to_out (the caller hands it, to_out and the residual to the launch that consumes them: fused_sublayer)."""
-        from .pf import attention, cached, fold_ln_weights, gemm_ln
-        b, n, _ = x.shape
+        n = x.shape[1]
         inner = self.to_q.out_features
         if ctx is None:
-            fq = cached(self, "_gsw_ln_qk", (self.to_q.weight, self.to_k.weight, norm.weight, norm.bias),
-                        lambda: fold_ln_weights(torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach()], dim=0), None, norm.weight, norm.bias))
-            fv = cached(self, "_gsw_ln_v", (self.to_v.weight, norm.weight, norm.bias), lambda: fold_ln_weights(self.to_v.weight.detach(), None, norm.weight, norm.bias))
-            qk = gemm_ln(x, stat, *fq)
-            vt = gemm_ln(x, stat, *fv, mode="trans", tokens=n)
-            o = attention(qk[..., :inner], qk[..., inner:], vt, self.heads)
+            qk = pf.gemm_ln(x, stat, *self._folded("qk", norm))
+            vt = pf.gemm_ln(x, stat, *self._folded("v", norm), mode="trans", tokens=n)
+            o = pf.attention(qk[..., :inner], qk[..., inner:], vt, self.heads)
         else:
             src, valid = _padded_ctx(ctx)
-            fq = cached(self, "_gsw_ln_q", (self.to_q.weight, norm.weight, norm.bias), lambda: fold_ln_weights(self.to_q.weight.detach(), None, norm.weight, norm.bias))
+            fq = self._folded("q", norm)
             k_ctx, vt_ctx = self.context_kv(src)
-            o = attention(gemm_ln(x, stat, *fq), k_ctx, vt_ctx, self.heads, valid_keys=valid)
+            o = pf.attention(pf.gemm_ln(x, stat, *fq), k_ctx, vt_ctx, self.heads, valid_keys=valid)
         if not project:
             return o
         return _lin(o, self.to_out[0], resid, rowstats=True)
@@ -278,7 +298,6 @@ class Attention(nn.Module):
         [B or 2B, 77, D] (2B: classifier-free guidance on shared latents -> [2B, S, 320]).  eps_next: leave the statistics of the new rows for the next LayerNorm.
         pre = (o, to_out): the same launch also runs the output projection of the self-attention in front -- x is then that projection's RESIDUAL, o the
         attention output, and the stream x + to_out(o) the sublayer works on exists in registers only (stat is not needed)."""
-        from . import xattn
         blob, v, idx = xattn.context_operands(self, norm, ctx, x.dtype)
         if pre is not None:
             return xattn.fused(x, None, blob, v, idx, ctx.shape[0], self.heads, eps_out=eps_next, pre_o=pre[0], pre_w=xattn.out_projection_operand(pre[1], x.dtype),
@@ -289,69 +308,53 @@ class Attention(nn.Module):
         """Classifier-free guidance with shared latents: x [B, S, C] holds the queries' input ONCE, ctx [2B, 77, D] = (uncond | text) contexts.  The
         query projection runs on B rows; the 77-key attention once per context half, both writing one [2B, S, C] tensor; -> attention output (before
         the output projection).  stat / norm: LayerNorm folded into the projection (x is the raw residual stream), else x is already normalised."""
-        from .pf import attention, cached, fold_ln_weights, gemm_ln
         B = x.shape[0]
         src, valid = _padded_ctx(ctx)
         k_ctx, vt_ctx = self.context_kv(src)
-        if stat is not None:
-            fq = cached(self, "_gsw_ln_q", (self.to_q.weight, norm.weight, norm.bias), lambda: fold_ln_weights(self.to_q.weight.detach(), None, norm.weight, norm.bias))
-            q = gemm_ln(x, stat, *fq)
-        else:
-            q = _lin(x, self.to_q)
+        q = pf.gemm_ln(x, stat, *self._folded("q", norm)) if stat is not None else _lin(x, self.to_q)
         o = torch.empty((2 * B, x.shape[1], self.to_q.out_features), dtype=x.dtype, device=x.device)
-        attention(q, k_ctx[:B], vt_ctx[:B], self.heads, valid_keys=valid, out=o[:B])
-        attention(q, k_ctx[B:], vt_ctx[B:], self.heads, valid_keys=valid, out=o[B:])
+        pf.attention(q, k_ctx[:B], vt_ctx[:B], self.heads, valid_keys=valid, out=o[:B])
+        pf.attention(q, k_ctx[B:], vt_ctx[B:], self.heads, valid_keys=valid, out=o[B:])
         return o
 
     def ln_foldable(self, x, ctx=None) -> bool:
-        from .pf import attention_ok
         n = x.shape[1]
-        sk = n if ctx is None else (ctx.shape[1] + 63) // 64 * 64
-        return (OWN_ATTENTION and FUSED_KERNELS and n % 8 == 0 and self.to_q.bias is None and self.to_k.bias is None and self.to_v.bias is None
-                and attention_ok(x, self.heads, self.to_q.out_features // self.heads, n, sk) and (ctx is None or CACHE_CONTEXT_KV)
+        return (OWN_ATTENTION and FUSED_KERNELS and n % 8 == 0 and self._no_qkv_bias()
+                and pf.attention_ok(x, self.heads, self.head_dim, n, n if ctx is None else _padded_keys(ctx)) and (ctx is None or CACHE_CONTEXT_KV)
                 and _own_gemm_ok(x, self.to_q.in_features, self.to_q.out_features))
+
+    def _qkv(self, x, src, cross: bool):
+        """(q, k, V^T) as the attention kernel reads them, keys / values projected from `src` (the padded context, or x itself).  The value projection is
+        computed transposed (V^T = W_v src^T, one GEMM either way) because the kernel consumes V^T tiles.  Tried in this order: cached context K / V^T
+        (CACHE_CONTEXT_KV); q | k | V^T from one launch (FUSED_QKV); q | k from one GEMM + V^T (FUSED_QK); three projections."""
+        n, inner = x.shape[1], self.to_q.out_features
+        if cross and CACHE_CONTEXT_KV:
+            k_ctx, vt_ctx = self.context_kv(src)
+            return _lin(x, self.to_q), k_ctx, vt_ctx
+        if (not cross and FUSED_QK and FUSED_QKV and self._no_qkv_bias() and (2 * inner) % 160 == 0 and n % 8 == 0
+                and _own_gemm_ok(x, self.to_q.in_features, 3 * inner)):
+            wqkv = self._wcat("qkv")
+            if wqkv.dtype == x.dtype:
+                qk, vt = pf.gemm_qkv(x.contiguous(), wqkv, 2 * inner)
+                return qk[..., :inner], qk[..., inner:], vt
+        vt = _lin_t(src, self.to_v)
+        if not cross and FUSED_QK:
+            wqk = self._wcat("qk")            # x is read once; the kernel takes q and k as column slices
+            qk = pf.gemm(x.contiguous(), wqk, None) if _own_gemm_ok(x, wqk.shape[1], wqk.shape[0]) else F.linear(x, wqk)
+            return qk[..., :inner], qk[..., inner:], vt
+        return _lin(x, self.to_q), _lin(src, self.to_k), vt
 
     def forward(self, x, ctx=None, resid=None):
         """resid: added to the output projection (in its GEMM epilogue on the own path): `x + attn(norm(x))` of the transformer block"""
         b, n, _ = x.shape
         if OWN_ATTENTION and FUSED_KERNELS:
-            from .pf import attention, attention_ok
             src, valid = (x, n) if ctx is None else _padded_ctx(ctx)
-            if attention_ok(x, self.heads, self.to_q.out_features // self.heads, n, src.shape[1]):
-                # hand-written flash-attention kernel (self- and cross-attention); the value projection is computed transposed
-                # (V^T = W_v src^T, one GEMM either way) because the kernel consumes V^T tiles.  Padded context rows are zero and
-                # masked by `valid`.
-                if ctx is not None and CACHE_CONTEXT_KV:
-                    k_ctx, vt_ctx = self.context_kv(src)
-                    o = attention(_lin(x, self.to_q), k_ctx, vt_ctx, self.heads, valid_keys=valid)
-                    return _lin(o, self.to_out[0], resid)
-                inner = self.to_q.out_features
-                if (ctx is None and FUSED_QK and FUSED_QKV and self.to_q.bias is None and self.to_k.bias is None and self.to_v.bias is None
-                        and (2 * inner) % 160 == 0 and n % 8 == 0 and _own_gemm_ok(x, self.to_q.in_features, 3 * inner)):
-                    from .pf import cached, gemm_qkv
-                    wqkv = cached(self, "_gsw_wqkv", (self.to_q.weight, self.to_k.weight, self.to_v.weight),
-                                  lambda: torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach(), self.to_v.weight.detach()], dim=0).contiguous())
-                    if wqkv.dtype == x.dtype:
-                        qk, vt = gemm_qkv(x.contiguous(), wqkv, 2 * inner)
-                        o = attention(qk[..., :inner], qk[..., inner:], vt, self.heads, valid_keys=valid)
-                        return _lin(o, self.to_out[0], resid)
-                vt = _lin_t(src, self.to_v)
-                if ctx is None and FUSED_QK:
-                    # self-attention: q and k from ONE GEMM over x (x is read once); the kernel takes them as column slices
-                    from .pf import cached
-                    wqk = cached(self, "_gsw_wqk", (self.to_q.weight, self.to_k.weight), lambda: torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach()], dim=0).contiguous())
-                    if _own_gemm_ok(x, wqk.shape[1], wqk.shape[0]):
-                        from .pf import gemm
-                        qk = gemm(x.contiguous(), wqk, None)
-                    else:
-                        qk = F.linear(x, wqk)
-                    inner = self.to_q.out_features
-                    o = attention(qk[..., :inner], qk[..., inner:], vt, self.heads, valid_keys=valid)
-                else:
-                    o = attention(_lin(x, self.to_q), _lin(src, self.to_k), vt, self.heads, valid_keys=valid)
-                return _lin(o, self.to_out[0], resid)
-            if x.is_cuda and x.dtype in (torch.float16, torch.bfloat16):
-                _note_fallback(f"attention head_dim={self.to_q.out_features // self.heads} Sq={n} Sk={src.shape[1]}: torch SDPA")
+            if pf.attention_ok(x, self.heads, self.head_dim, n, src.shape[1]):
+                # hand-written flash-attention kernel (self- and cross-attention).  Padded context rows are zero and masked by `valid`.
+                q, k, vt = self._qkv(x, src, ctx is not None)
+                return _lin(pf.attention(q, k, vt, self.heads, valid_keys=valid), self.to_out[0], resid)
+            if pf.half_gpu(x):
+                _note_fallback(f"attention head_dim={self.head_dim} Sq={n} Sk={src.shape[1]}: torch SDPA")
         ctx = x if ctx is None else ctx
         q = _lin(x, self.to_q).view(b, n, self.heads, -1).transpose(1, 2)
         k = _lin(ctx, self.to_k).view(b, ctx.shape[1], self.heads, -1).transpose(1, 2)
@@ -368,13 +371,11 @@ class GEGLU(nn.Module):
     def forward(self, x):
         inner = self.proj.out_features // 2
         if _own_gemm_ok(x, self.proj.in_features, self.proj.out_features) and inner % 80 == 0:
-            from .pf import gemm, pack_geglu_weight, cached     # value * gelu(gate) in the GEMM epilogue: no [M, 2I] intermediate
-            _wb(self.proj, x)
-            c = cached(self, "_gsw_geglu", (self.proj.weight, self.proj.bias), lambda: pack_geglu_weight(self.proj.weight.detach(), self.proj.bias.detach()))
-            return gemm(x.contiguous(), c[0], c[1], mode="geglu")
+            _wb(self.proj, x)                 # value * gelu(gate) in the GEMM epilogue: no [M, 2I] intermediate
+            c = pf.cached(self, "_gsw_geglu", (self.proj.weight, self.proj.bias), lambda: pf.pack_geglu_weight(self.proj.weight.detach(), self.proj.bias.detach()))
+            return pf.gemm(x.contiguous(), c[0], c[1], mode="geglu")
         y = self.proj(x)
         if FUSED_KERNELS and y.is_cuda and y.is_contiguous() and (y.shape[-1] // 2) % 8 == 0:
-            from . import codec
             return codec.geglu(y)
         h, gate = y.chunk(2, dim=-1)
         return h * F.gelu(gate)
@@ -388,12 +389,26 @@ class FeedForward(nn.Module):
     def forward(self, x, resid=None, rowstats: bool = False):
         return _lin(self.net[0](x), self.net[2], resid, rowstats=rowstats)
 
+    def _folded(self, norm: nn.LayerNorm):
+        """pf.fold_ln_weights of the GEGLU projection behind LayerNorm `norm`, cached on the module (keyed by the projection's and the norm's parameters)."""
+        proj = self.net[0].proj
+        return pf.cached(self, "_gsw_ln_ff1", (proj.weight, proj.bias, norm.weight, norm.bias),
+                         lambda: pf.fold_ln_weights(proj.weight.detach(), proj.bias, norm.weight, norm.bias, geglu=True))
+
     def forward_ln(self, x, stat, norm: nn.LayerNorm, resid=None):
         """ff(LayerNorm(x)) + resid with the LayerNorm folded into the GEGLU projection (pf.gemm_ln)"""
-        from .pf import cached, fold_ln_weights, gemm_ln
-        proj = self.net[0].proj
-        f = cached(self, "_gsw_ln_ff1", (proj.weight, proj.bias, norm.weight, norm.bias), lambda: fold_ln_weights(proj.weight.detach(), proj.bias, norm.weight, norm.bias, geglu=True))
-        return _lin(gemm_ln(x, stat, *f, mode="geglu"), self.net[2], resid, rowstats=True)
+        return _lin(pf.gemm_ln(x, stat, *self._folded(norm), mode="geglu"), self.net[2], resid, rowstats=True)
+
+
+def _fused_block_ok(like: torch.Tensor, channels: int) -> bool:
+    """Tokens [B, S, channels] with the dtype and device of `like` (the tokens themselves, or the latent they will be made from) run the fused transformer
+    block of BasicTransformerBlock.forward; the token tensor must be contiguous as well (BasicTransformerBlock.fused_ok)."""
+    return FUSED_KERNELS and pf.half_gpu(like) and channels % 8 == 0 and channels <= 1536
+
+
+def _cached_kv_on() -> bool:
+    """the switches behind cross-attention on the own kernel with per-context cached K / V^T"""
+    return OWN_ATTENTION and FUSED_KERNELS and CACHE_CONTEXT_KV
 
 
 class BasicTransformerBlock(nn.Module):
@@ -406,31 +421,32 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ff = FeedForward(dim)
 
+    @staticmethod
+    def fused_ok(x) -> bool:
+        """this token tensor runs the fused block (else the plain torch modules)"""
+        return _fused_block_ok(x, x.shape[-1]) and x.is_contiguous()
+
     def dup_ok(self, x, ctx) -> bool:
-        """forward(x, ctx, dup=True) is available: the fused path with the own attention kernel and cached context K / V"""
-        from .pf import attention_ok
+        """forward(x, ctx, dup=True) is available: the fused path with the own attention kernel and cached context K / V, ctx holding two contexts per row of x"""
         a = self.attn2
-        return (FUSED_KERNELS and OWN_ATTENTION and CACHE_CONTEXT_KV and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and x.is_contiguous()
-                and x.shape[-1] % 8 == 0 and x.shape[-1] <= 1536 and ctx.shape[0] == 2 * x.shape[0]
-                and attention_ok(x, a.heads, a.to_q.out_features // a.heads, x.shape[1], (ctx.shape[1] + 63) // 64 * 64))
+        return (self.fused_ok(x) and _cached_kv_on() and ctx.shape[0] == 2 * x.shape[0]
+                and pf.attention_ok(x, a.heads, a.head_dim, x.shape[1], _padded_keys(ctx)))
 
     def _cross_sublayer(self, x, ctx, dup: bool, one_launch: bool):
         """x + attn2(norm2(x), ctx) on the hand-written path; dup: x holds B rows, ctx 2B -> 2B rows"""
-        from .codec import add_layernorm
-        from .pf import ln_stat
-        st = ln_stat(x, self.norm2.eps) if (one_launch or self.attn2.ln_foldable(x, ctx[: x.shape[0]] if dup else ctx)) else None
+        st = pf.ln_stat(x, self.norm2.eps) if (one_launch or self.attn2.ln_foldable(x, ctx[: x.shape[0]] if dup else ctx)) else None
         if st is not None and one_launch:
             return self.attn2.fused_sublayer(x, st, self.norm2, ctx, eps_next=self.norm3.eps)
         if dup:
             if st is not None:
                 o = self.attn2.cross_dup(x, ctx, stat=st, norm=self.norm2)
             else:
-                _, n = add_layernorm(x, None, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+                _, n = codec.add_layernorm(x, None, self.norm2.weight, self.norm2.bias, self.norm2.eps)
                 o = self.attn2.cross_dup(n, ctx)
             return _lin(o, self.attn2.to_out[0], torch.cat([x, x], dim=0), rowstats=True)
         if st is not None:
             return self.attn2.forward_ln(x, st, self.norm2, ctx, resid=x)
-        _, n = add_layernorm(x, None, self.norm2.weight, self.norm2.bias, self.norm2.eps)
+        _, n = codec.add_layernorm(x, None, self.norm2.weight, self.norm2.bias, self.norm2.eps)
         return self.attn2(n, ctx, resid=x)
 
     def forward(self, x, ctx, dup: bool = False):
@@ -438,37 +454,33 @@ class BasicTransformerBlock(nn.Module):
         queries are computed once on the B rows the two halves share."""
         if dup and not self.dup_ok(x, ctx):
             x, dup = torch.cat([x, x], dim=0), False
-        if FUSED_KERNELS and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and x.is_contiguous() and x.shape[-1] % 8 == 0 \
-                and x.shape[-1] <= 1536:
-            from .codec import add_layernorm
-            from .pf import ln_stat
-            # the residual adds ride in the output projections' GEMM epilogues.  Each LayerNorm is FOLDED into the projections that consume it when the
-            # launch that produced x left row records on it (large batches: pf.ln_stat) -- the normalised tensor is then never written; otherwise it is
-            # one read + one write (gsw_add_layernorm)
-            from . import xattn
-            one_launch = xattn.usable(x, self.attn2, ctx)      # the 320-channel level: norm2 + query projection + 77-key attention + output projection + residual in one kernel
-            st = ln_stat(x, self.norm1.eps) if self.attn1.ln_foldable(x) else None
-            if st is not None and one_launch and xattn.PRE_ENABLED and tuple(self.attn1.to_out[0].weight.shape) == (xattn.CHANNELS, xattn.CHANNELS):
-                # ... and the self-attention's output projection + bias + residual + norm2's statistics as that kernel's prologue: the stream between the two
-                # attention sublayers is never stored (dup: the launch writes 2B rows from B)
-                o1 = self.attn1.forward_ln(x, st, self.norm1, project=False)
-                x = self.attn2.fused_sublayer(x, None, self.norm2, ctx, eps_next=self.norm3.eps, pre=(o1, self.attn1.to_out[0]))
-            else:
-                if st is not None:
-                    x = self.attn1.forward_ln(x, st, self.norm1, resid=x)
-                else:
-                    _, n = add_layernorm(x, None, self.norm1.weight, self.norm1.bias, self.norm1.eps)
-                    x = self.attn1(n, resid=x)
-                x = self._cross_sublayer(x, ctx, dup, one_launch)
-            inner4 = self.ff.net[2].in_features
-            st = ln_stat(x, self.norm3.eps) if (inner4 % 80 == 0 and _own_gemm_ok(x, x.shape[-1], 2 * inner4)) else None
+        if not self.fused_ok(x):
+            x = x + self.attn1(self.norm1(x))
+            x = x + self.attn2(self.norm2(x), ctx)
+            return x + self.ff(self.norm3(x))
+        # the residual adds ride in the output projections' GEMM epilogues.  Each LayerNorm is FOLDED into the projections that consume it when the
+        # launch that produced x left row records on it (large batches: pf.ln_stat) -- the normalised tensor is then never written; otherwise it is
+        # one read + one write (gsw_add_layernorm)
+        one_launch = xattn.usable(x, self.attn2, ctx)      # the 320-channel level: norm2 + query projection + 77-key attention + output projection + residual in one kernel
+        st = pf.ln_stat(x, self.norm1.eps) if self.attn1.ln_foldable(x) else None
+        if st is not None and one_launch and xattn.pre_usable(self.attn1.to_out[0]):
+            # ... and the self-attention's output projection + bias + residual + norm2's statistics as that kernel's prologue: the stream between the two
+            # attention sublayers is never stored (dup: the launch writes 2B rows from B)
+            o1 = self.attn1.forward_ln(x, st, self.norm1, project=False)
+            x = self.attn2.fused_sublayer(x, None, self.norm2, ctx, eps_next=self.norm3.eps, pre=(o1, self.attn1.to_out[0]))
+        else:
             if st is not None:
-                return self.ff.forward_ln(x, st, self.norm3, resid=x)
-            _, n = add_layernorm(x, None, self.norm3.weight, self.norm3.bias, self.norm3.eps)
-            return self.ff(n, resid=x)
-        x = x + self.attn1(self.norm1(x))
-        x = x + self.attn2(self.norm2(x), ctx)
-        return x + self.ff(self.norm3(x))
+                x = self.attn1.forward_ln(x, st, self.norm1, resid=x)
+            else:
+                _, n = codec.add_layernorm(x, None, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+                x = self.attn1(n, resid=x)
+            x = self._cross_sublayer(x, ctx, dup, one_launch)
+        inner4 = self.ff.net[2].in_features
+        st = pf.ln_stat(x, self.norm3.eps) if (inner4 % 80 == 0 and _own_gemm_ok(x, x.shape[-1], 2 * inner4)) else None
+        if st is not None:
+            return self.ff.forward_ln(x, st, self.norm3, resid=x)
+        _, n = codec.add_layernorm(x, None, self.norm3.weight, self.norm3.bias, self.norm3.eps)
+        return self.ff(n, resid=x)
 
 
 class Transformer2DModel(nn.Module):
@@ -490,21 +502,18 @@ class Transformer2DModel(nn.Module):
 
     def forward_pf(self, x, ctx, dup: bool = False):
         """dup: x holds B images, ctx 2B contexts -> a PF tensor of 2B images (see UNet2DCondition.forward)"""
-        from . import xattn
         if xattn.gn_proj_usable(x, self.norm, self.proj_in):
             # the 320-channel level at large batch: GroupNorm + proj_in in one launch, the rows normalised on their way into the matrix pipe (never stored)
             y = xattn.gn_proj(x, self.norm, self.proj_in, eps_next=self.transformer_blocks[0].norm1.eps)
         else:
-            y = _lin(_gn_pf(x, self.norm, act=False, tokens=True), self.proj_in, rowstats=True)      # GroupNorm writes dense tokens directly
+            y = _lin(pf.gn_pf(x, self.norm, act=False, tokens=True), self.proj_in, rowstats=True)      # GroupNorm writes dense tokens directly
         for i, blk in enumerate(self.transformer_blocks):
             y = blk(y, ctx, dup=dup and i == 0)
         if dup:
-            from .pf import dup_pf
-            x = dup_pf(x)
+            x = pf.dup_pf(x)
         if _own_gemm_ok(y, self.proj_out.in_features, self.proj_out.out_features):
-            from .pf import gemm        # proj_out + residual written straight into the PF tensor's interior rows (x has no other reader)
-            w, b = _wb(self.proj_out, y)
-            gemm(y.contiguous(), w, b, resid=x.rows, mode="tok2pf", tokens=x.H * x.W, width=x.W, out=x.rows, stats_for=x)
+            w, b = _wb(self.proj_out, y)        # proj_out + residual written straight into the PF tensor's interior rows (x has no other reader)
+            pf.gemm(y.contiguous(), w, b, resid=x.rows, mode="tok2pf", tokens=x.H * x.W, width=x.W, out=x.rows, stats_for=x)
         else:
             x.interior.add_(_lin(y, self.proj_out).view(x.B, x.H, x.W, x.C))
             x.stats = None
@@ -520,8 +529,7 @@ class Downsample2D(nn.Module):
         return self.conv(x)
 
     def forward_pf(self, x):
-        from .pf import conv_pf
-        return conv_pf(x, _pw(self.conv), self.conv.bias, stride=2)
+        return pf.conv_pf(x, _pw(self.conv), self.conv.bias, stride=2)
 
 
 class Upsample2D(nn.Module):
@@ -533,17 +541,15 @@ class Upsample2D(nn.Module):
         return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
 
     def forward_pf(self, x):
-        from .pf import PF, conv_pf, conv_up2x_pf, conv_up2x_fusable, pack_upsample_weight
-        if UPSAMPLE_SUBPIXEL and conv_up2x_fusable(x, self.conv.out_channels):
-            from .pf import cached
-            w4 = cached(self, "_gsw_up4", (self.conv.weight,), lambda: pack_upsample_weight(self.conv.weight))
-            return conv_up2x_pf(x, w4, self.conv.bias)            # 2.25x fewer FLOPs, no upsampled intermediate
-        up = PF.zeros(x.B, 2 * x.H, 2 * x.W, x.C, x.buf.dtype, x.buf.device)
+        if UPSAMPLE_SUBPIXEL and pf.conv_up2x_fusable(x, self.conv.out_channels):
+            w4 = pf.cached(self, "_gsw_up4", (self.conv.weight,), lambda: pf.pack_upsample_weight(self.conv.weight))
+            return pf.conv_up2x_pf(x, w4, self.conv.bias)            # 2.25x fewer FLOPs, no upsampled intermediate
+        up = pf.PF.zeros(x.B, 2 * x.H, 2 * x.W, x.C, x.buf.dtype, x.buf.device)
         xi, g = x.interior, up.grid
         for dy in (0, 1):
             for dx in (0, 1):
                 g[:, 1 + dy:1 + dy + 2 * x.H:2, 1 + dx:1 + dx + 2 * x.W:2, :].copy_(xi)
-        return conv_pf(up, _pw(self.conv), self.conv.bias)
+        return pf.conv_pf(up, _pw(self.conv), self.conv.bias)
 
 
 class DownBlock(nn.Module):
@@ -567,7 +573,6 @@ class DownBlock(nn.Module):
     def forward_pf(self, x, temb, ctx, skips, dup_temb=None):
         """dup_temb (first down block under classifier-free guidance with shared latents): x holds B images, ctx 2B contexts; the first resnet and the
         first transformer up to its cross-attention run on B images, everything after on 2B with the doubled time-embedding rows `dup_temb`"""
-        from .pf import PF
         for i, r in enumerate(self.resnets):
             x = r.forward_pf(x, temb)
             if self.attentions is not None:
@@ -603,7 +608,6 @@ class UpBlock(nn.Module):
         return x
 
     def forward_pf(self, x, temb, ctx, skips):
-        from .pf import PF
         for i, r in enumerate(self.resnets):
             x = r.forward_pf(x, temb, x2=skips.pop())
             if self.attentions is not None:
@@ -624,6 +628,99 @@ class MidBlock(nn.Module):
 
     def forward_pf(self, x, temb, ctx):
         return self.resnets[1].forward_pf(self.attentions[0].forward_pf(self.resnets[0].forward_pf(x, temb), ctx), temb)
+
+
+TEMB_TABLE = True     # integer timesteps: the whole time-embedding chain (sinusoid -> linear -> SiLU -> linear -> SiLU -> every resnet's time_emb_proj) is a
+                      # function of t alone -- tabulated once over the training timesteps, a forward gathers its rows (one launch instead of ~20, and the
+                      # 50 MB of projection weights are not streamed per forward)
+NUM_TRAIN_TIMESTEPS = 1000   # default length of the table; a model built from a checkpoint carries its scheduler's value as `model.num_train_timesteps`
+                             # (extract.Models sets it from scheduler/scheduler_config.json), and ddim.DDIMSchedule refuses timesteps outside the range on the host
+
+CONV_OUT_DIRECT_MAX_PIXELS = 65536      # conv_out (320 -> 4) as the one-wave-per-16-pixels kernel writing NCHW directly (gsw_conv3x3_pf_nchw); above that the
+                                        # LDS-tiled 64-column kernel moves fewer bytes through L2
+
+CFG_SHARED_PREFIX = os.environ.get("GSW_CFG_SHARED_PREFIX", "1") != "0"      # classifier-free guidance: the part of a forward that does not see the context runs once for both halves of the batch
+
+
+def _edge_conv_weights(self):
+    """conv_in (4 -> 320) and conv_out (320 -> 4) for the PF GEMM: the 4-channel side is zero-padded to one 64-wide tile."""
+    w_in, w_out = self.conv_in.weight, self.conv_out.weight
+
+    def build():
+        wi = torch.zeros((w_in.shape[0], 64, 3, 3), dtype=w_in.dtype, device=w_in.device)
+        wi[:, : w_in.shape[1]] = w_in.detach()
+        wo = torch.zeros((64, w_out.shape[1], 3, 3), dtype=w_out.dtype, device=w_out.device)
+        wo[: w_out.shape[0]] = w_out.detach()
+        bo = torch.zeros(64, dtype=w_out.dtype, device=w_out.device)
+        bo[: w_out.shape[0]] = self.conv_out.bias.detach()
+        return pf.pack_conv_weight(wi), pf.pack_conv_weight(wo), bo
+
+    return pf.cached(self, "_gsw_edge", (w_in, w_out, self.conv_out.bias), build)
+
+
+def _resnets(self):
+    """every ResnetBlock2D of the model, in module order (= the column order of the time-embedding rows)"""
+    resnets = getattr(self, "_gsw_resnets", None)
+    if resnets is None:
+        resnets = self._gsw_resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D)]
+    return resnets
+
+
+def _temb_widths(resnets):
+    return [(id(r), r.time_emb_proj.out_features) for r in resnets]
+
+
+def _temb_rows(self, temb: torch.Tensor):
+    """Every resnet's time_emb_proj(temb) from one GEMM over the row-concatenated weights -> TembRows (or temb itself off the engine)."""
+    resnets = _resnets(self)
+    widths = _temb_widths(resnets)
+    if not resnets or not _own_gemm_ok(temb, temb.shape[-1], sum(n for _, n in widths)) or any(n % 8 for _, n in widths):
+        return temb
+    params = tuple(p for r in resnets for p in (r.time_emb_proj.weight, r.time_emb_proj.bias))
+    wcat, bcat = pf.cached(self, "_gsw_temb_cat", params, lambda: (torch.cat([r.time_emb_proj.weight.detach() for r in resnets], dim=0).contiguous(),
+                                                                     torch.cat([r.time_emb_proj.bias.detach() for r in resnets], dim=0).contiguous()))
+    if wcat.dtype != temb.dtype:
+        return temb
+    return TembRows(temb, pf.gemm(temb.contiguous(), wcat, bcat), widths)
+
+
+def _temb_rows_from_table(self, t: torch.Tensor, x: torch.Tensor):
+    """TembRows gathered from the per-model table [num_train_timesteps, sum of the resnets' channels], or None when t is not an integer tensor / the
+    projections do not run on the engine.  The table is as long as the model's `num_train_timesteps` (the scheduler config's; 1000 by default).  The
+    schedules of ddim.py validate their timesteps against that range on the host; a device tensor outside it would be clamped by gsw_gather_rows."""
+    if t.dtype not in (torch.int64, torch.int32) or not t.is_cuda or t.numel() not in (1, x.shape[0]):
+        return None
+    resnets = _resnets(self)
+    if not resnets or any(r.time_emb_proj.out_features % 8 for r in resnets):
+        return None
+    te = self.time_embedding
+    if te.linear_1.weight.dtype != x.dtype or te.linear_1.weight.device != x.device:
+        return None
+    params = (te.linear_1.weight, te.linear_1.bias, te.linear_2.weight, te.linear_2.bias) + tuple(p for r in resnets for p in (r.time_emb_proj.weight, r.time_emb_proj.bias))
+
+    def build():
+        with torch.no_grad():
+            tt = torch.arange(int(getattr(self, "num_train_timesteps", NUM_TRAIN_TIMESTEPS)), device=x.device)
+            temb = F.silu(te(timestep_embedding(tt, self.c0).to(x.dtype)))
+            rows = _temb_rows(self, temb)
+            if not isinstance(rows, TembRows):
+                return None
+            return rows.table.contiguous()
+
+    table = pf.cached(self, "_gsw_temb_table", params, build)
+    if table is not None and table.shape[0] != int(getattr(self, "num_train_timesteps", NUM_TRAIN_TIMESTEPS)):      # the scheduler length changed after the table was built
+        self._gsw_temb_table = None
+        table = pf.cached(self, "_gsw_temb_table", params, build)
+        graph.weights_changed()      # a captured forward gathers from the OLD table's address: every graph entry must re-capture
+    if table is None:
+        return None
+    B, n_tot = x.shape[0], table.shape[1]
+    idx = t if t.dtype == torch.int64 else t.to(torch.int64)
+    out = torch.empty((B, n_tot), dtype=table.dtype, device=table.device)
+    with torch.cuda.device(x.device):
+        N.check(N.lib().gsw_gather_rows(table.data_ptr(), n_tot * table.element_size(), table.shape[0], idx.data_ptr(), 0 if idx.numel() == 1 else 1,
+                                        out.data_ptr(), n_tot * table.element_size(), B, n_tot * table.element_size(), codec._stream_ptr()))
+    return TembRows(None, out, _temb_widths(resnets))
 
 
 class UNet2DCondition(nn.Module):
@@ -688,7 +785,7 @@ class UNet2DCondition(nn.Module):
         temb = F.silu(temb)                      # every resnet applies SiLU to the same embedding: do it once
         if self._pf_ok(x):
             return self._forward_pf(x, _temb_rows(self, temb), ctx, cfg_dup)
-        if USE_PF and FUSED_KERNELS and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16):
+        if USE_PF and FUSED_KERNELS and pf.half_gpu(x):
             _note_fallback(f"UNet forward on {tuple(x.shape)} {x.dtype}: off the padded-flat path (fp16 / bf16, conv channels % 64, lattice % {1 << (len(self.down_blocks) - 1)}): plain torch modules")
         h = self.conv_in(x)
         skips = [h]
@@ -701,209 +798,76 @@ class UNet2DCondition(nn.Module):
         # run channels-last
         return self.conv_out(gn_act(h, self.conv_norm_out)).contiguous(memory_format=torch.contiguous_format)
 
+    def _pf_ok(self, x: torch.Tensor) -> bool:
+        if not (USE_PF and FUSED_KERNELS and pf.half_gpu(x)):
+            return False
+        ok = getattr(self, "_pf_shapes_ok", None)
+        if ok is None:
+            ok = all(m.in_channels % 64 == 0 and m.out_channels % 64 == 0 for n, m in self.named_modules()
+                     if isinstance(m, nn.Conv2d) and n not in ("conv_in", "conv_out"))
+            self._pf_shapes_ok = ok
+        n_down = len(self.down_blocks) - 1
+        return ok and x.shape[-1] % (1 << n_down) == 0 and x.shape[-2] % (1 << n_down) == 0
 
-def _unet_pf_ok(self, x: torch.Tensor) -> bool:
-    if not (USE_PF and FUSED_KERNELS and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16)):
-        return False
-    ok = getattr(self, "_pf_shapes_ok", None)
-    if ok is None:
-        ok = all(m.in_channels % 64 == 0 and m.out_channels % 64 == 0 for n, m in self.named_modules()
-                 if isinstance(m, nn.Conv2d) and n not in ("conv_in", "conv_out"))
-        self._pf_shapes_ok = ok
-    n_down = len(self.down_blocks) - 1
-    return ok and x.shape[-1] % (1 << n_down) == 0 and x.shape[-2] % (1 << n_down) == 0
+    def _cfg_dup_ok(self, x: torch.Tensor, ctx: torch.Tensor) -> bool:
+        """forward(cfg_dup=True) may share the prefix.  Asked from the latent, before any token tensor exists: the shape / dtype / device terms and switches of
+        BasicTransformerBlock.dup_ok for the first transformer block (not its contiguity or row-count terms), plus OWN_GEMM and the query projection on the engine."""
+        b0 = self.down_blocks[0]
+        if b0.attentions is None or not isinstance(b0.attentions[0].transformer_blocks[0], BasicTransformerBlock):
+            return False
+        a = b0.attentions[0].transformer_blocks[0].attn2
+        return (_fused_block_ok(x, b0.attentions[0].proj_in.out_features) and _cached_kv_on() and OWN_GEMM and a.head_dim in pf.ATTN_HEAD_DIMS
+                and _own_gemm_ok(x, a.to_q.in_features, a.to_q.out_features))
 
-
-def _edge_conv_weights(self):
-    """conv_in (4 -> 320) and conv_out (320 -> 4) for the PF GEMM: the 4-channel side is zero-padded to one 64-wide tile."""
-    from .pf import cached, pack_conv_weight
-    w_in, w_out = self.conv_in.weight, self.conv_out.weight
-
-    def build():
-        wi = torch.zeros((w_in.shape[0], 64, 3, 3), dtype=w_in.dtype, device=w_in.device)
-        wi[:, : w_in.shape[1]] = w_in.detach()
-        wo = torch.zeros((64, w_out.shape[1], 3, 3), dtype=w_out.dtype, device=w_out.device)
-        wo[: w_out.shape[0]] = w_out.detach()
-        bo = torch.zeros(64, dtype=w_out.dtype, device=w_out.device)
-        bo[: w_out.shape[0]] = self.conv_out.bias.detach()
-        return pack_conv_weight(wi), pack_conv_weight(wo), bo
-
-    return cached(self, "_gsw_edge", (w_in, w_out, self.conv_out.bias), build)
-
-
-def _temb_rows(self, temb: torch.Tensor):
-    """Every resnet's time_emb_proj(temb) from one GEMM over the row-concatenated weights -> TembRows (or temb itself off the engine)."""
-    resnets = getattr(self, "_gsw_resnets", None)
-    if resnets is None:
-        resnets = self._gsw_resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D)]
-    n_tot = sum(r.time_emb_proj.out_features for r in resnets)
-    if not resnets or not _own_gemm_ok(temb, temb.shape[-1], n_tot) or any(r.time_emb_proj.out_features % 8 for r in resnets):
-        return temb
-    from .pf import cached, gemm
-    params = tuple(p for r in resnets for p in (r.time_emb_proj.weight, r.time_emb_proj.bias))
-    wcat, bcat = cached(self, "_gsw_temb_cat", params, lambda: (torch.cat([r.time_emb_proj.weight.detach() for r in resnets], dim=0).contiguous(),
-                                                                  torch.cat([r.time_emb_proj.bias.detach() for r in resnets], dim=0).contiguous()))
-    if wcat.dtype != temb.dtype:
-        return temb
-    rb = gemm(temb.contiguous(), wcat, bcat)
-    rows, off = {}, 0
-    for r in resnets:
-        n = r.time_emb_proj.out_features
-        rows[id(r)] = rb[:, off:off + n]
-        off += n
-    return TembRows(temb, rows, rb)
-
-
-TEMB_TABLE = True     # integer timesteps: the whole time-embedding chain (sinusoid -> linear -> SiLU -> linear -> SiLU -> every resnet's time_emb_proj) is a
-                      # function of t alone -- tabulated once over the training timesteps, a forward gathers its rows (one launch instead of ~20, and the
-                      # 50 MB of projection weights are not streamed per forward)
-NUM_TRAIN_TIMESTEPS = 1000   # default length of the table; a model built from a checkpoint carries its scheduler's value as `model.num_train_timesteps`
-                             # (extract.Models sets it from scheduler/scheduler_config.json), and ddim.DDIMSchedule refuses timesteps outside the range on the host
-
-
-def _temb_rows_from_table(self, t: torch.Tensor, x: torch.Tensor):
-    """TembRows gathered from the per-model table [num_train_timesteps, sum of the resnets' channels], or None when t is not an integer tensor / the
-    projections do not run on the engine.  The table is as long as the model's `num_train_timesteps` (the scheduler config's; 1000 by default).  The
-    schedules of ddim.py validate their timesteps against that range on the host; a device tensor outside it would be clamped by gsw_gather_rows."""
-    if t.dtype not in (torch.int64, torch.int32) or not t.is_cuda or t.numel() not in (1, x.shape[0]):
-        return None
-    resnets = getattr(self, "_gsw_resnets", None)
-    if resnets is None:
-        resnets = self._gsw_resnets = [m for m in self.modules() if isinstance(m, ResnetBlock2D)]
-    if not resnets or any(r.time_emb_proj.out_features % 8 for r in resnets):
-        return None
-    te = self.time_embedding
-    if te.linear_1.weight.dtype != x.dtype or te.linear_1.weight.device != x.device:
-        return None
-    from .pf import cached
-    from . import _native as N
-    from .codec import _stream_ptr
-    params = (te.linear_1.weight, te.linear_1.bias, te.linear_2.weight, te.linear_2.bias) + tuple(p for r in resnets for p in (r.time_emb_proj.weight, r.time_emb_proj.bias))
-
-    def build():
-        with torch.no_grad():
-            tt = torch.arange(int(getattr(self, "num_train_timesteps", NUM_TRAIN_TIMESTEPS)), device=x.device)
-            temb = F.silu(te(timestep_embedding(tt, self.c0).to(x.dtype)))
-            rows = _temb_rows(self, temb)
-            if not isinstance(rows, TembRows):
-                return None
-            return rows.table.contiguous()
-
-    table = cached(self, "_gsw_temb_table", params, build)
-    if table is not None and table.shape[0] != int(getattr(self, "num_train_timesteps", NUM_TRAIN_TIMESTEPS)):      # the scheduler length changed after the table was built
-        self._gsw_temb_table = None
-        table = cached(self, "_gsw_temb_table", params, build)
-        from . import graph
-        graph.weights_changed()      # a captured forward gathers from the OLD table's address: every graph entry must re-capture
-    if table is None:
-        return None
-    B, n_tot = x.shape[0], table.shape[1]
-    idx = t if t.dtype == torch.int64 else t.to(torch.int64)
-    out = torch.empty((B, n_tot), dtype=table.dtype, device=table.device)
-    with torch.cuda.device(x.device):
-        N.check(N.lib().gsw_gather_rows(table.data_ptr(), n_tot * table.element_size(), table.shape[0], idx.data_ptr(), 0 if idx.numel() == 1 else 1,
-                                        out.data_ptr(), n_tot * table.element_size(), B, n_tot * table.element_size(), _stream_ptr()))
-    rows, off = {}, 0
-    for r in resnets:
-        n = r.time_emb_proj.out_features
-        rows[id(r)] = out[:, off:off + n]
-        off += n
-    return TembRows(None, rows, out)
-
-
-CONV_OUT_DIRECT_MAX_PIXELS = 65536      # conv_out (320 -> 4) as the one-wave-per-16-pixels kernel writing NCHW directly (gsw_conv3x3_pf_nchw); above that the
-                                        # LDS-tiled 64-column kernel moves fewer bytes through L2
-
-
-CFG_SHARED_PREFIX = __import__("os").environ.get("GSW_CFG_SHARED_PREFIX", "1") != "0"      # classifier-free guidance: the part of a forward that does not see the context runs once for both halves of the batch
-
-
-def _unet_cfg_dup_ok(self, x: torch.Tensor, ctx: torch.Tensor) -> bool:
-    b0 = self.down_blocks[0]
-    if b0.attentions is None or not isinstance(b0.attentions[0].transformer_blocks[0], BasicTransformerBlock):
-        return False
-    tokens = torch.empty((x.shape[0], x.shape[2] * x.shape[3], b0.attentions[0].proj_in.out_features), dtype=x.dtype, device="meta")
-    blk = b0.attentions[0].transformer_blocks[0]
-    a = blk.attn2
-    from .pf import ATTN_HEAD_DIMS
-    return (FUSED_KERNELS and OWN_ATTENTION and CACHE_CONTEXT_KV and OWN_GEMM and tokens.shape[-1] % 8 == 0 and tokens.shape[-1] <= 1536
-            and (a.to_q.out_features // a.heads) in ATTN_HEAD_DIMS and _own_gemm_ok(x, a.to_q.in_features, a.to_q.out_features))
-
-
-def _dup_temb(temb):
-    """time-embedding rows of B images -> of the 2B images of the doubled batch"""
-    if isinstance(temb, TembRows):
-        tab = torch.cat([temb.table, temb.table], dim=0)
-        rows, off = {}, 0
-        for k, v in temb.rows.items():           # (insertion order = column order)
-            n = v.shape[1]
-            rows[k] = tab[:, off:off + n]
-            off += n
-        return TembRows(None if temb.act is None else torch.cat([temb.act, temb.act], dim=0), rows, tab)
-    return torch.cat([temb, temb], dim=0)
-
-
-def _unet_forward_pf(self, x: torch.Tensor, temb, ctx: torch.Tensor, cfg_dup: bool = False) -> torch.Tensor:
-    from .pf import PF, conv_pf, cached, pack_conv_weight, dup_pf
-    from . import _native as N
-    from .codec import _dt, _stream_ptr
-    w_in, w_out, b_out = _edge_conv_weights(self)
-    B, cin, H, W = x.shape
-    xin = PF.empty(B, H, W, 64, x.dtype, x.device)
-    xc = x.contiguous()
-    with torch.cuda.device(x.device):
-        N.check(N.lib().gsw_nchw_to_pf(xc.data_ptr(), xin.rows.data_ptr(), B, cin, H, W, 64, _dt(x.dtype), _stream_ptr()))
-    h = conv_pf(xin, w_in, self.conv_in.bias)
-    skips = [h]
-    if cfg_dup:
-        temb2 = _dup_temb(temb)
-        h = self.down_blocks[0].forward_pf(h, temb, ctx, skips, dup_temb=temb2)
-        skips[0] = dup_pf(skips[0])              # the conv_in skip is consumed by the last up-block resnet, on 2B images
-        temb, B = temb2, 2 * B
-        rest = self.down_blocks[1:]
-    else:
-        rest = self.down_blocks
-    for blk in rest:
-        h = blk.forward_pf(h, temb, ctx, skips)
-    h = self.mid_block.forward_pf(h, temb, ctx)
-    for blk in self.up_blocks:
-        h = blk.forward_pf(h, temb, ctx, skips)
-    hn = _gn_pf(h, self.conv_norm_out, act=True)
-    nout = self.conv_out.out_channels
-    if B * H * W <= CONV_OUT_DIRECT_MAX_PIXELS and nout <= 16 and hn.C % 32 == 0 and self.conv_out.bias is not None:
-        wo = cached(self.conv_out, "_gsw_packed_direct", (self.conv_out.weight,), lambda: pack_conv_weight(self.conv_out.weight.detach()))
-        y = torch.empty((B, nout, H, W), dtype=x.dtype, device=x.device)
+    def _forward_pf(self, x: torch.Tensor, temb, ctx: torch.Tensor, cfg_dup: bool = False) -> torch.Tensor:
+        w_in, w_out, b_out = _edge_conv_weights(self)
+        B, cin, H, W = x.shape
+        xin = pf.PF.empty(B, H, W, 64, x.dtype, x.device)
+        xc = x.contiguous()
         with torch.cuda.device(x.device):
-            N.check(N.lib().gsw_conv3x3_pf_nchw(hn.rows.data_ptr(), wo.data_ptr(), self.conv_out.bias.data_ptr(), y.data_ptr(), B, H, W, hn.C, nout,
-                                                _dt(x.dtype), _stream_ptr()))
-        return y
-    y = conv_pf(hn, w_out, b_out)
-    return y.interior[..., :nout].permute(0, 3, 1, 2).contiguous()
+            N.check(N.lib().gsw_nchw_to_pf(xc.data_ptr(), xin.rows.data_ptr(), B, cin, H, W, 64, codec._dt(x.dtype), codec._stream_ptr()))
+        h = pf.conv_pf(xin, w_in, self.conv_in.bias)
+        skips = [h]
+        if cfg_dup:
+            temb2 = temb.doubled() if isinstance(temb, TembRows) else torch.cat([temb, temb], dim=0)      # the time-embedding rows of the doubled batch
+            h = self.down_blocks[0].forward_pf(h, temb, ctx, skips, dup_temb=temb2)
+            skips[0] = pf.dup_pf(skips[0])              # the conv_in skip is consumed by the last up-block resnet, on 2B images
+            temb, B = temb2, 2 * B
+            rest = self.down_blocks[1:]
+        else:
+            rest = self.down_blocks
+        for blk in rest:
+            h = blk.forward_pf(h, temb, ctx, skips)
+        h = self.mid_block.forward_pf(h, temb, ctx)
+        for blk in self.up_blocks:
+            h = blk.forward_pf(h, temb, ctx, skips)
+        hn = pf.gn_pf(h, self.conv_norm_out, act=True)
+        nout = self.conv_out.out_channels
+        if B * H * W <= CONV_OUT_DIRECT_MAX_PIXELS and nout <= 16 and hn.C % 32 == 0 and self.conv_out.bias is not None:
+            wo = pf.cached(self.conv_out, "_gsw_packed_direct", (self.conv_out.weight,), lambda: pf.pack_conv_weight(self.conv_out.weight.detach()))
+            y = torch.empty((B, nout, H, W), dtype=x.dtype, device=x.device)
+            with torch.cuda.device(x.device):
+                N.check(N.lib().gsw_conv3x3_pf_nchw(hn.rows.data_ptr(), wo.data_ptr(), self.conv_out.bias.data_ptr(), y.data_ptr(), B, H, W, hn.C, nout,
+                                                    codec._dt(x.dtype), codec._stream_ptr()))
+            return y
+        y = pf.conv_pf(hn, w_out, b_out)
+        return y.interior[..., :nout].permute(0, 3, 1, 2).contiguous()
 
-
-def _unet_prepare_context(self, ctx: torch.Tensor) -> None:
-    """Bring the per-context caches (padded copy, every cross-attention layer's K / V^T) up to date for `ctx` without running a forward --
-    in place when they exist (graph.py calls this after overwriting a captured graph's static context buffer)."""
-    if not (OWN_ATTENTION and FUSED_KERNELS and CACHE_CONTEXT_KV and ctx.is_cuda):
-        return
-    from .pf import attention_ok
-    src, _ = _padded_ctx(ctx)
-    for blk in self.modules():
-        if isinstance(blk, BasicTransformerBlock):
-            a = blk.attn2
-            if attention_ok(ctx, a.heads, a.to_q.out_features // a.heads, 1, src.shape[1]):
-                a.context_kv(src)
-            from . import xattn
-            if xattn.ENABLED and a.to_q.in_features == xattn.CHANNELS and ctx.shape[1] <= xattn.MAX_KEYS and ctx.dtype in (torch.float16, torch.bfloat16):
-                xattn.context_operands(a, blk.norm2, ctx, ctx.dtype)      # the one-launch cross-attention's per-context fragment streams
-                if xattn.PRE_ENABLED and tuple(blk.attn1.to_out[0].weight.shape) == (xattn.CHANNELS, xattn.CHANNELS):
-                    xattn.out_projection_operand(blk.attn1.to_out[0], ctx.dtype)      # ... and the prologue's (the self-attention's output projection; per layer, not per context)
-
-
-UNet2DCondition._cfg_dup_ok = _unet_cfg_dup_ok
-UNet2DCondition.prepare_context = _unet_prepare_context
-UNet2DCondition._pf_ok = _unet_pf_ok
-UNet2DCondition._forward_pf = _unet_forward_pf
+    def prepare_context(self, ctx: torch.Tensor) -> None:
+        """Bring the per-context caches (padded copy, every cross-attention layer's K / V^T) up to date for `ctx` without running a forward --
+        in place when they exist (graph.py calls this after overwriting a captured graph's static context buffer)."""
+        if not (_cached_kv_on() and ctx.is_cuda):
+            return
+        src, _ = _padded_ctx(ctx)
+        for blk in self.modules():
+            if isinstance(blk, BasicTransformerBlock):
+                a = blk.attn2
+                if pf.attention_ok(ctx, a.heads, a.head_dim, 1, src.shape[1]):
+                    a.context_kv(src)
+                if xattn.layer_usable(a, ctx, ctx.dtype):
+                    xattn.context_operands(a, blk.norm2, ctx, ctx.dtype)      # the one-launch cross-attention's per-context fragment streams
+                    if xattn.pre_usable(blk.attn1.to_out[0]):
+                        xattn.out_projection_operand(blk.attn1.to_out[0], ctx.dtype)      # ... and the prologue's (the self-attention's output projection; per layer, not per context)
 
 
 def synthetic_init_(model: nn.Module, seed: int = 0, out_scale: float = 1.0) -> nn.Module:
@@ -932,8 +896,7 @@ def synthetic_init_(model: nn.Module, seed: int = 0, out_scale: float = 1.0) -> 
 def load_diffusers_state_dict(model: nn.Module, weight_dir: str) -> nn.Module:
     """Load the UNet weights of a diffusers-layout directory (`<weight_dir>/unet/diffusion_pytorch_model.*`: safetensors, sharded safetensors or .bin,
     checkpoint.load_component_state_dict); parameter names match this module 1:1, strictly both ways."""
-    from .checkpoint import load_component_state_dict
-    sd = dict(load_component_state_dict(weight_dir, "unet"))
+    sd = dict(checkpoint.load_component_state_dict(weight_dir, "unet"))
     own = dict(model.named_parameters())
     for k, v in list(sd.items()):               # SD 1.x: proj_in / proj_out stored as 1x1 convolutions
         if k in own and v.dim() == 4 and own[k].dim() == 2 and v.shape[2:] == (1, 1):
@@ -941,8 +904,7 @@ def load_diffusers_state_dict(model: nn.Module, weight_dir: str) -> nn.Module:
     missing, unexpected = model.load_state_dict(sd, strict=False)
     if missing or unexpected:
         raise RuntimeError(f"state dict mismatch: missing {missing[:5]}..., unexpected {unexpected[:5]}...")
-    from .graph import weights_changed
-    weights_changed()                            # captured graphs of this model (graph.GraphedEpsModel) re-check the parameters before their next replay
+    graph.weights_changed()                          # captured graphs of this model (graph.GraphedEpsModel) re-check the parameters before their next replay
     return model
 
 

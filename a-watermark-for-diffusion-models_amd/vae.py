@@ -11,11 +11,14 @@ path and its cost, while watermark accuracy through decode->encode is only meani
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Sequence
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import checkpoint, pf
 
 SCALING_FACTOR = 0.18215  # extract.py:42
 
@@ -26,17 +29,16 @@ USE_PF = True
 FALLBACKS = {}        # (reason -> count) of GPU half-precision calls that ran the plain-torch module path instead of the hand-written kernels
 
 
-STRICT = __import__("os").environ.get("GSW_STRICT_KERNELS", "1") != "0"      # leaving the hand-written path raises (see unet.STRICT); 0 / --strict_kernels 0: warn and count instead
+STRICT = os.environ.get("GSW_STRICT_KERNELS", "1") != "0"      # leaving the hand-written path raises (see unet.STRICT); 0 / --strict_kernels 0: warn and count instead
 
 
 def _fell_off(what: str, x: torch.Tensor) -> None:
     """A half-precision device tensor is about to run the plain-torch path (MIOpen / hipBLASLt / aotriton): say so, once per reason."""
-    if USE_PF and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16):
+    if USE_PF and pf.half_gpu(x):
         why = f"{what}: input {tuple(x.shape)} {x.dtype} is off the padded-flat path (fp16 / bf16; H, W multiples of 8; mid-block tokens % 8; channel counts multiples of 64)"
         if STRICT:
             raise RuntimeError("gswm vae (strict kernels): " + why + " -- pass --strict_kernels 0 to allow the library kernels")
         if why not in FALLBACKS:
-            import warnings
             warnings.warn("gswm vae: " + why + " -- running the plain torch modules", RuntimeWarning, stacklevel=3)
         FALLBACKS[why] = FALLBACKS.get(why, 0) + 1
 
@@ -44,7 +46,6 @@ def _fell_off(what: str, x: torch.Tensor) -> None:
 def _pw(conv: nn.Conv2d, cin_pad: int = 0, cout_pad: int = 0):
     """Packed [N, 9*C] weight (+ bias) of a convolution, optionally zero-padded to `cin_pad` input / `cout_pad` output channels
     (the 3- / 4- / 8-channel edges of the VAE ride on one 64-wide tile)."""
-    from .pf import cached, pack_conv_weight
 
     def build():
         w, b = conv.weight.detach(), conv.bias.detach()
@@ -53,15 +54,14 @@ def _pw(conv: nn.Conv2d, cin_pad: int = 0, cout_pad: int = 0):
         if cout_pad and w.shape[0] < cout_pad:
             w = torch.cat([w, w.new_zeros(cout_pad - w.shape[0], *w.shape[1:])], dim=0)
             b = torch.cat([b, b.new_zeros(cout_pad - b.shape[0])])
-        return pack_conv_weight(w), b.contiguous()
+        return pf.pack_conv_weight(w), b.contiguous()
 
-    return cached(conv, "_gsw_packed", (conv.weight, conv.bias), build)
+    return pf.cached(conv, "_gsw_packed", (conv.weight, conv.bias), build)
 
 
 def _pw_out_folded(conv_out: nn.Conv2d, post: nn.Conv2d):
     """conv_out followed by a 1x1 convolution (`quant_conv(encoder(x))`, extract.py:41 -> diffusers AutoencoderKL.encode) as ONE 3x3
     convolution: W' = W_post W_out per tap, b' = W_post b_out + b_post (composed in fp32, rounded once), zero-padded to 64 outputs."""
-    from .pf import cached, pack_conv_weight
 
     def build():
         wp = post.weight.detach().float()[:, :, 0, 0]
@@ -69,16 +69,15 @@ def _pw_out_folded(conv_out: nn.Conv2d, post: nn.Conv2d):
         b = wp @ conv_out.bias.detach().float() + post.bias.detach().float()
         w = torch.cat([w, w.new_zeros(64 - w.shape[0], *w.shape[1:])], dim=0).to(conv_out.weight.dtype)
         b = torch.cat([b, b.new_zeros(64 - b.shape[0])]).to(conv_out.weight.dtype)
-        return pack_conv_weight(w), b.contiguous()
+        return pf.pack_conv_weight(w), b.contiguous()
 
-    return cached(conv_out, "_gsw_folded", (conv_out.weight, conv_out.bias, post.weight, post.bias), build)
+    return pf.cached(conv_out, "_gsw_folded", (conv_out.weight, conv_out.bias, post.weight, post.bias), build)
 
 
 def _pw_in_folded(conv_in: nn.Conv2d, pre: nn.Conv2d):
     """A 1x1 convolution followed by conv_in (`decoder(post_quant_conv(z))`, diffusers AutoencoderKL.decode) as ONE 3x3 convolution over
     [z | 1]: W'[:, c] = W_in W_pre[:, c] per tap, and the 1x1 bias rides on a constant-one input channel (weights W_in b_pre per tap) --
     exact at the image border too, where the zero padding applies to the 1x1 output, not to its input."""
-    from .pf import cached, pack_conv_weight
 
     def build():
         wi = conv_in.weight.detach().float()
@@ -86,18 +85,13 @@ def _pw_in_folded(conv_in: nn.Conv2d, pre: nn.Conv2d):
         w = torch.einsum("oikl,ic->ockl", wi, wp)
         w1 = torch.einsum("oikl,i->okl", wi, bp)[:, None]
         w = torch.cat([w, w1, w.new_zeros(w.shape[0], 64 - w.shape[1] - 1, *w.shape[2:])], dim=1).to(conv_in.weight.dtype)
-        return pack_conv_weight(w), conv_in.bias.detach().contiguous()
+        return pf.pack_conv_weight(w), conv_in.bias.detach().contiguous()
 
-    return cached(conv_in, "_gsw_folded", (conv_in.weight, conv_in.bias, pre.weight, pre.bias), build)
-
-
-def _gn_pf(x, norm: nn.GroupNorm, act=True, tokens=False):
-    from .pf import groupnorm_pf
-    return groupnorm_pf(x, norm.weight, norm.bias, norm.num_groups, norm.eps, act=act, tokens=tokens)
+    return pf.cached(conv_in, "_gsw_folded", (conv_in.weight, conv_in.bias, pre.weight, pre.bias), build)
 
 
 def _pf_ok(x: torch.Tensor) -> bool:
-    return USE_PF and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and x.shape[-1] % 8 == 0 and x.shape[-2] % 8 == 0
+    return USE_PF and pf.half_gpu(x) and x.shape[-1] % 8 == 0 and x.shape[-2] % 8 == 0
 
 
 def _convs_fit_pf(module: nn.Module) -> bool:
@@ -112,9 +106,8 @@ def _convs_fit_pf(module: nn.Module) -> bool:
 
 def _to_pf64(x: torch.Tensor, ones_channel: bool = False):
     """NCHW tensor with < 64 channels -> PF tensor with 64 channels (zero-filled; ones_channel: channel C of every real pixel is 1)."""
-    from .pf import PF
     B, C, H, W = x.shape
-    p = PF.zeros(B, H, W, 64, x.dtype, x.device)
+    p = pf.PF.zeros(B, H, W, 64, x.dtype, x.device)
     p.interior[..., :C].copy_(x.permute(0, 2, 3, 1))
     if ones_channel:
         p.interior[..., C].fill_(1.0)
@@ -136,11 +129,10 @@ class VaeResnet(nn.Module):
         return (x if self.conv_shortcut is None else self.conv_shortcut(x)) + h
 
     def forward_pf(self, x):
-        from .pf import conv_pf
-        h = conv_pf(_gn_pf(x, self.norm1), *_pw(self.conv1))
-        h = _gn_pf(h, self.norm2)
-        sc = x if self.conv_shortcut is None else conv_pf(x, *_pw(self.conv_shortcut), ksize=1)
-        return conv_pf(h, *_pw(self.conv2), resid=sc)                   # residual add in the GEMM epilogue
+        h = pf.conv_pf(pf.gn_pf(x, self.norm1), *_pw(self.conv1))
+        h = pf.gn_pf(h, self.norm2)
+        sc = x if self.conv_shortcut is None else pf.conv_pf(x, *_pw(self.conv_shortcut), ksize=1)
+        return pf.conv_pf(h, *_pw(self.conv2), resid=sc)                   # residual add in the GEMM epilogue
 
 
 class VaeAttention(nn.Module):
@@ -160,20 +152,19 @@ class VaeAttention(nn.Module):
         return x + self.to_out[0](o).transpose(1, 2).reshape(b, c, h, w)
 
     def forward_pf(self, x):
-        from .pf import attention_single_head, cached, gemm
-        y = _gn_pf(x, self.group_norm, act=False, tokens=True)          # GroupNorm writes dense tokens [B, H*W, C]
+        y = pf.gn_pf(x, self.group_norm, act=False, tokens=True)          # GroupNorm writes dense tokens [B, H*W, C]
         C, S = x.C, x.H * x.W
         if C % 64 or S % 8:          # (Encoder._pf_tokens_ok / _pf_ok keep such inputs on the plain-torch path with a loud warning)
             raise RuntimeError(f"VaeAttention: {C} channels x {S} tokens is off the hand-written path (channels % 64, tokens % 8)")
         # q | k from one GEMM over the tokens, V^T from a transposing GEMM, softmax(q k^T) v per image on the matmul engine, and the output
         # projection + residual written straight into the PF tensor's interior rows
-        wqk, bqk = cached(self, "_gsw_wqk", (self.to_q.weight, self.to_k.weight, self.to_q.bias, self.to_k.bias),
+        wqk, bqk = pf.cached(self, "_gsw_wqk", (self.to_q.weight, self.to_k.weight, self.to_q.bias, self.to_k.bias),
                           lambda: (torch.cat([self.to_q.weight.detach(), self.to_k.weight.detach()]).contiguous(),
                                    torch.cat([self.to_q.bias.detach(), self.to_k.bias.detach()]).contiguous()))
-        qk = gemm(y, wqk, bqk)
-        vt = gemm(y, self.to_v.weight.detach(), self.to_v.bias.detach(), mode="trans", tokens=S)
-        o = attention_single_head(qk[..., :C], qk[..., C:], vt)
-        gemm(o, self.to_out[0].weight.detach(), self.to_out[0].bias.detach(), resid=x.rows, mode="tok2pf", tokens=S, width=x.W, out=x.rows, stats_for=x)
+        qk = pf.gemm(y, wqk, bqk)
+        vt = pf.gemm(y, self.to_v.weight.detach(), self.to_v.bias.detach(), mode="trans", tokens=S)
+        o = pf.attention_single_head(qk[..., :C], qk[..., C:], vt)
+        pf.gemm(o, self.to_out[0].weight.detach(), self.to_out[0].bias.detach(), resid=x.rows, mode="tok2pf", tokens=S, width=x.W, out=x.rows, stats_for=x)
         return x
 
 
@@ -199,8 +190,7 @@ class _Down(nn.Module):
         return self.conv(F.pad(x, (0, 1, 0, 1)))     # diffusers' asymmetric padding for the VAE downsampler
 
     def forward_pf(self, x):
-        from .pf import conv_pf
-        return conv_pf(x, *_pw(self.conv), stride=2, pad_after_only=True)
+        return pf.conv_pf(x, *_pw(self.conv), stride=2, pad_after_only=True)
 
 
 class _Up(nn.Module):
@@ -212,18 +202,17 @@ class _Up(nn.Module):
         return self.conv(F.interpolate(x, scale_factor=2.0, mode="nearest"))
 
     def forward_pf(self, x):
-        from .pf import PF, cached, conv_pf, conv_up2x_fusable, conv_up2x_pf, pack_upsample_weight
-        if conv_up2x_fusable(x, self.conv.out_channels):
+        if pf.conv_up2x_fusable(x, self.conv.out_channels):
             # sub-pixel form (gsw_conv_up2x_pf, as in the UNet): four 2x2 convolutions of the LOW-resolution tensor -- 2.25x fewer FLOPs, no upsampled
             # intermediate, no copy kernels.  The three upsamplers are 56 % of the decoder's FLOPs in the 3x3-on-upsampled form.
-            w4 = cached(self, "_gsw_up4", (self.conv.weight,), lambda: pack_upsample_weight(self.conv.weight))
-            return conv_up2x_pf(x, w4, self.conv.bias)
-        up = PF.zeros(x.B, 2 * x.H, 2 * x.W, x.C, x.buf.dtype, x.buf.device)
+            w4 = pf.cached(self, "_gsw_up4", (self.conv.weight,), lambda: pf.pack_upsample_weight(self.conv.weight))
+            return pf.conv_up2x_pf(x, w4, self.conv.bias)
+        up = pf.PF.zeros(x.B, 2 * x.H, 2 * x.W, x.C, x.buf.dtype, x.buf.device)
         xi, g = x.interior, up.grid
         for dy in (0, 1):
             for dx in (0, 1):
                 g[:, 1 + dy:1 + dy + 2 * x.H:2, 1 + dx:1 + dx + 2 * x.W:2, :].copy_(xi)
-        return conv_pf(up, *_pw(self.conv))
+        return pf.conv_pf(up, *_pw(self.conv))
 
 
 class _EncBlock(nn.Module):
@@ -289,12 +278,11 @@ class Encoder(nn.Module):
         return ((x.shape[-2] // f) * (x.shape[-1] // f)) % 8 == 0
 
     def forward_pf(self, x, post: nn.Conv2d = None):
-        from .pf import conv_pf
-        h = conv_pf(_to_pf64(x), *_pw(self.conv_in, cin_pad=64))
+        h = pf.conv_pf(_to_pf64(x), *_pw(self.conv_in, cin_pad=64))
         for b in self.down_blocks:
             h = b.forward_pf(h)
-        h = _gn_pf(self.mid_block.forward_pf(h), self.conv_norm_out)
-        y = conv_pf(h, *(_pw(self.conv_out, cout_pad=64) if post is None else _pw_out_folded(self.conv_out, post)))
+        h = pf.gn_pf(self.mid_block.forward_pf(h), self.conv_norm_out)
+        y = pf.conv_pf(h, *(_pw(self.conv_out, cout_pad=64) if post is None else _pw_out_folded(self.conv_out, post)))
         return y.interior[..., : self.conv_out.out_channels].permute(0, 3, 1, 2).contiguous()
 
 
@@ -322,12 +310,11 @@ class Decoder(nn.Module):
         return _convs_fit_pf(self)
 
     def forward_pf(self, z, pre: nn.Conv2d = None):
-        from .pf import conv_pf
-        h0 = conv_pf(_to_pf64(z), *_pw(self.conv_in, cin_pad=64)) if pre is None else conv_pf(_to_pf64(z, ones_channel=True), *_pw_in_folded(self.conv_in, pre))
+        h0 = pf.conv_pf(_to_pf64(z), *_pw(self.conv_in, cin_pad=64)) if pre is None else pf.conv_pf(_to_pf64(z, ones_channel=True), *_pw_in_folded(self.conv_in, pre))
         h = self.mid_block.forward_pf(h0)
         for b in self.up_blocks:
             h = b.forward_pf(h)
-        y = conv_pf(_gn_pf(h, self.conv_norm_out), *_pw(self.conv_out, cout_pad=64))
+        y = pf.conv_pf(pf.gn_pf(h, self.conv_norm_out), *_pw(self.conv_out, cout_pad=64))
         return y.interior[..., : self.conv_out.out_channels].permute(0, 3, 1, 2).contiguous()
 
 
@@ -381,8 +368,7 @@ def synthetic_init_(model: nn.Module, seed: int = 0) -> nn.Module:
 
 
 def load_diffusers_state_dict(model: nn.Module, weight_dir: str) -> nn.Module:
-    from .checkpoint import load_component_state_dict
-    sd = load_component_state_dict(weight_dir, "vae")          # safetensors, sharded safetensors or .bin
+    sd = checkpoint.load_component_state_dict(weight_dir, "vae")          # safetensors, sharded safetensors or .bin
     # older diffusers checkpoints name the mid-block attention projections query/key/value/proj_attn
     ren = {"query": "to_q", "key": "to_k", "value": "to_v", "proj_attn": "to_out.0"}
     fixed = {}

@@ -23,12 +23,13 @@ Two more launches of the same transposed-stream family live here, both built on 
 """
 from __future__ import annotations
 
-import ctypes as _C
-from typing import Optional, Tuple
+import os
+from typing import Optional
 
 import torch
 
 from . import _native as N
+from . import pf
 from .codec import _dt, _stream_ptr
 
 CHANNELS = 320            # the level gsw_xattn_fused serves (SD 2.1: 64 x 64 latents; SD 1.5: the first level)
@@ -37,7 +38,7 @@ KEY_SLOTS = 96            # three 32-key blocks in the first product (the second
 HEAD_ELEMS = 11 * 5120    # 60 + 50 fragments of 512 elements
 V_FLOATS = KEY_SLOTS
 LOG2E = 1.4426950408889634
-ENABLED = __import__("os").environ.get("GSW_XATTN_FUSED", "1") != "0"      # A/B switch: 0 = the three-launch path (query projection, attention kernel, output projection)
+ENABLED = os.environ.get("GSW_XATTN_FUSED", "1") != "0"      # A/B switch: 0 = the three-launch path (query projection, attention kernel, output projection)
 
 
 def _column_of(nb: torch.Tensor, m: torch.Tensor) -> torch.Tensor:
@@ -98,7 +99,7 @@ def pack_stream(Ap: torch.Tensor, v: torch.Tensor, Bm: torch.Tensor):
 
 
 PRE_CHUNKS = 21           # gsw_xattn_fused_pre's prologue stream: twenty 16-channel k-steps of the self-attention's output projection + its bias
-PRE_ENABLED = __import__("os").environ.get("GSW_XATTN_PRE", "1") != "0"      # A/B switch: 0 = the self-attention's output projection stays its own launch
+PRE_ENABLED = os.environ.get("GSW_XATTN_PRE", "1") != "0"      # A/B switch: 0 = the self-attention's output projection stays its own launch
 
 
 def pack_out_projection(w: torch.Tensor, b: Optional[torch.Tensor], dtype: torch.dtype) -> torch.Tensor:
@@ -175,12 +176,22 @@ def context_operands(attn, norm, ctx: torch.Tensor, dtype: torch.dtype):
     return ent[1], ent[2], ent[3]
 
 
+def layer_usable(attn, ctx: torch.Tensor, dtype: torch.dtype) -> bool:
+    """The context-and-layer half of `usable` (what prepare_context can know before any activation exists): 320 channels in and out, at most 79 context tokens,
+    no projection biases besides to_out's, activations of `dtype`"""
+    return (ENABLED and dtype in (torch.float16, torch.bfloat16) and ctx.dim() == 3 and ctx.shape[1] <= MAX_KEYS and attn.to_q.bias is None
+            and attn.to_k.bias is None and attn.to_v.bias is None and attn.to_q.in_features == CHANNELS and attn.to_out[0].out_features == CHANNELS)
+
+
 def usable(x: torch.Tensor, attn, ctx: torch.Tensor) -> bool:
-    """gsw_xattn_fused serves this call: 320 channels, whole 128-row tiles per image, at most 79 context tokens, no projection biases besides to_out's"""
-    return (ENABLED and x.is_cuda and x.dim() == 3 and x.dtype in (torch.float16, torch.bfloat16) and x.is_contiguous() and x.shape[-1] == CHANNELS
-            and x.shape[1] % 128 == 0 and ctx.dim() == 3 and ctx.shape[1] <= MAX_KEYS and attn.to_q.bias is None and attn.to_k.bias is None
-            and attn.to_v.bias is None and attn.to_q.in_features == CHANNELS and attn.to_out[0].out_features == CHANNELS
+    """gsw_xattn_fused serves this call: layer_usable, and the activations are contiguous device tokens [B, whole 128-row tiles, 320] within the 32-bit row count"""
+    return (layer_usable(attn, ctx, x.dtype) and x.is_cuda and x.dim() == 3 and x.is_contiguous() and x.shape[-1] == CHANNELS and x.shape[1] % 128 == 0
             and ctx.shape[0] % x.shape[0] == 0 and x.shape[0] * x.shape[1] < (1 << 31) // max(1, ctx.shape[0] // x.shape[0]))
+
+
+def pre_usable(to_out) -> bool:
+    """the self-attention's output projection `to_out` can run as the prologue of the one-launch cross-attention (fused(..., pre_o=, pre_w=))"""
+    return PRE_ENABLED and tuple(to_out.weight.shape) == (CHANNELS, CHANNELS)
 
 
 def fused(x: torch.Tensor, stat: Optional[torch.Tensor], blob: torch.Tensor, v: torch.Tensor, index: Optional[torch.Tensor], out_images: int, heads: int,
@@ -216,7 +227,6 @@ def fused(x: torch.Tensor, stat: Optional[torch.Tensor], blob: torch.Tensor, v: 
         raise ValueError("xattn.fused: index must be int32 [out_images]")
     y = torch.empty((out_images, S, C), dtype=x.dtype, device=x.device) if out is None else out
     ostat = torch.empty((out_images * S, 2), dtype=torch.float32, device=x.device) if eps_out is not None else None
-    from . import pf
     tm = pf.CONV_TIMER
     with torch.cuda.device(x.device):
         e0 = tm.start() if tm is not None else None
@@ -236,14 +246,13 @@ def fused(x: torch.Tensor, stat: Optional[torch.Tensor], blob: torch.Tensor, v: 
 
 
 # ---- GroupNorm + proj_in of a transformer at the 320-channel level as one launch (gsw_gn_proj_tokens, csrc/gswm_xattn.hip): the normalised tokens are never stored
-GNPROJ_ENABLED = __import__("os").environ.get("GSW_GN_PROJ_FUSED", "1") != "0"      # A/B switch: 0 = gsw_gn_pf_apply (tokens) + the engine's 320 x 320 GEMM
+GNPROJ_ENABLED = os.environ.get("GSW_GN_PROJ_FUSED", "1") != "0"      # A/B switch: 0 = gsw_gn_pf_apply (tokens) + the engine's 320 x 320 GEMM
 
 
 def gn_proj_usable(x, norm, lin) -> bool:
     """x: a PF tensor (pf.PF) whose producing launch left GroupNorm column records; norm: the transformer's GroupNorm; lin: its proj_in (nn.Linear)"""
-    from . import pf
     C = getattr(x, "C", 0)
-    return (GNPROJ_ENABLED and C == CHANNELS and x.buf.is_cuda and x.buf.dtype in (torch.float16, torch.bfloat16) and pf.FUSE_GN_STATS and pf._stats_usable(x)
+    return (GNPROJ_ENABLED and C == CHANNELS and pf.half_gpu(x.buf) and pf.FUSE_GN_STATS and pf._stats_usable(x)
             and not pf._gn_fused_ok(x.B, x.H, x.W, C, norm.num_groups) and x.W % 32 == 0 and (x.H * x.W) % 128 == 0 and (C // norm.num_groups) % 2 == 0 and C % norm.num_groups == 0
             and x.B * x.H * x.W < (1 << 31) and tuple(lin.weight.shape[:2]) == (CHANNELS, CHANNELS) and lin.weight.numel() == CHANNELS * CHANNELS
             and lin.weight.dtype == x.buf.dtype and norm.weight.dtype == x.buf.dtype)
@@ -252,7 +261,6 @@ def gn_proj_usable(x, norm, lin) -> bool:
 def gn_proj(x, norm, lin, eps_next: Optional[float] = None) -> torch.Tensor:
     """tokens [B, H W, 320] = GroupNorm(x) Wp^T + b from the PF tensor x and the column records of the launch that produced it; eps_next: leave the (rstd, -rstd mean)
     of the token rows on the result for the LayerNorm that follows (`_gsw_lnstat`, what pf.ln_stat returns)"""
-    from . import pf
     if not x.buf.is_cuda:
         raise RuntimeError("xattn.gn_proj: device tensors only; there is no CPU fallback")
     dev, dt, st = x.buf.device, x.buf.dtype, x.stats
