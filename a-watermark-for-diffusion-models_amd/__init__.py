@@ -9,7 +9,7 @@ through the `gswm_amd` loader module at the repo root:
 from . import _native  # noqa: F401
 from . import codec  # noqa: F401
 
-__all__ = ["codec", "gs_insert", "extract", "comfy", "ddim", "dist"]
+__all__ = ["codec", "gs_insert", "extract", "comfy", "ddim", "dist", "distortions"]
 
 
 def __getattr__(name):  # lazy sub-modules (keep `import gswm_amd` light)

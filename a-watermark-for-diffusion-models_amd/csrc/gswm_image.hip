@@ -4,6 +4,8 @@
 //   G1   modified_stable_diffusion_gs `decode_image` / `torch_to_numpy` / numpy_to_pil        gsw_tensor_to_image
 //   D    distortions:131-233: JPEG quality QF ("compression"), Lanczos "scaling", brightness,
 //        contrast, togray, invert, flips, additive Gaussian noise                            gsw_jpeg_roundtrip, gsw_image_pointwise
+//   D    distortions:107-137,207-222: rotation, resizedcrop, erasing, randomcrop             gsw_affine_nearest, gsw_resample_plan +
+//                                                                                            gsw_crop_resize, gsw_box_mask
 //
 // All of it is byte / integer work bounded by HBM: one pass reads 3 B/pixel and writes 3 B/pixel (6 B when the output is the
 // fp16 CHW tensor the VAE encoder consumes).  The arithmetic restates, bit for bit, what Pillow (Resample.c, Blend.c, Convert.c)
@@ -18,6 +20,9 @@
 //                                       the whole RGB->YCbCr(+2x2 box) -> FDCT -> quantise -> dequantise -> IDCT chain in 64 registers.
 //   gsw_jpeg_finish_kernel            : triangle ("fancy") chroma upsampling + YCbCr->RGB + output conversion, one thread per pixel.
 //   gsw_image_pointwise_kernel        : the point-wise attacks; contrast's mean grey level comes from gsw_image_lsum_kernel.
+//   gsw_affine_nearest_kernel         : Geometry.c affine_fixed (rotation), per-image 16.16 coefficient rows, one thread per pixel.
+//   gsw_box_mask_kernel               : keep or black out one rectangle per image (randomcrop, erasing).
+//   gsw_crop_h_kernel                 : crop + horizontal resample pass (crop row staged in LDS); gsw_resample_v_kernel follows.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -516,6 +521,87 @@ __global__ __launch_bounds__(256) void gsw_boxblur_v_kernel(const uint8_t* __res
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// geometric attacks (distortions:107-137,207-222)
+// ---------------------------------------------------------------------------------------------------------------------------
+// Geometry.c affine_fixed: nearest neighbour in 16.16 fixed point, one thread per output pixel.  cf[b] = (a0, a1, a2, a3, a4, a5):
+// xin = (a2 + y a1 + x a0) >> 16, yin = (a5 + y a4 + x a3) >> 16 in wrapping 32-bit arithmetic (what Pillow's running sums give);
+// a source index outside the image gives black.  The transpose fast paths of Image.rotate are coefficient rows too.  grid (H, B)
+__global__ __launch_bounds__(256) void gsw_affine_nearest_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, const int32_t* __restrict__ cf, int H, int W,
+                                                                 int mode) {
+    const int y = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const int32_t* c = cf + b * 6;
+    const uint32_t a0 = (uint32_t)c[0], a3 = (uint32_t)c[3];
+    const uint32_t xr = (uint32_t)c[2] + (uint32_t)y * (uint32_t)c[1], yr = (uint32_t)c[5] + (uint32_t)y * (uint32_t)c[4];
+    const uint8_t* img = in + b * (int64_t)H * W * 3;
+    for (int x = threadIdx.x; x < W; x += blockDim.x) {
+        const int xin = (int32_t)(xr + (uint32_t)x * a0) >> 16, yin = (int32_t)(yr + (uint32_t)x * a3) >> 16;
+        uint32_t r = 0, g = 0, bl = 0;
+        if (xin >= 0 && xin < W && yin >= 0 && yin < H) {
+            const uint8_t* p = img + ((int64_t)yin * W + xin) * 3;
+            r = p[0]; g = p[1]; bl = p[2];
+        }
+        store_px(out, mode, b, y, x, H, W, 0, 3, r);
+        store_px(out, mode, b, y, x, H, W, 1, 3, g);
+        store_px(out, mode, b, y, x, H, W, 2, 3, bl);
+    }
+}
+
+// one rectangle per image, box[b] = (top, left, height, width).  keep_inside != 0: the rectangle is kept and the rest is black
+// (randomcrop: the crop pasted onto a black canvas at its own place); keep_inside == 0: the rectangle is black (erasing, value 0).
+// grid (H, B); a black pixel reads nothing
+__global__ __launch_bounds__(256) void gsw_box_mask_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, const int32_t* __restrict__ boxes, int H, int W,
+                                                           int keep_inside, int mode) {
+    const int y = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const int32_t* bx = boxes + b * 4;
+    const int i0 = bx[0], j0 = bx[1], bh = bx[2], bw = bx[3];
+    const bool row_in = y >= i0 && y - i0 < bh;
+    const uint8_t* img = in + (b * H + y) * (int64_t)W * 3;
+    for (int x = threadIdx.x; x < W; x += blockDim.x) {
+        const bool inside = row_in && x >= j0 && x - j0 < bw;
+        uint32_t r = 0, g = 0, bl = 0;
+        if (inside == (keep_inside != 0)) {
+            const uint8_t* p = img + (int64_t)x * 3;
+            r = p[0]; g = p[1]; bl = p[2];
+        }
+        store_px(out, mode, b, y, x, H, W, 0, 3, r);
+        store_px(out, mode, b, y, x, H, W, 1, 3, g);
+        store_px(out, mode, b, y, x, H, W, 2, 3, bl);
+    }
+}
+
+// horizontal pass of a crop then resize: row y of the crop (origin org[b] = (top, left), ch x cw) of image b -> tmp [B, ch, Wout, 3] u8,
+// Pillow's fixed-point horizontal resample with the crop row staged once in LDS; kk == NULL: a plain copy (Pillow skips the pass when
+// the width is kept).  The host checks the boxes; the clamps only keep a bad origin inside the image.  grid (ch, B)
+__global__ __launch_bounds__(256) void gsw_crop_h_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ tmp, const int32_t* __restrict__ org,
+                                                         const int32_t* __restrict__ bounds, const int32_t* __restrict__ kk, int ksize, int H, int W, int ch,
+                                                         int cw, int Wout) {
+    extern __shared__ uint8_t row[];
+    const int y = blockIdx.x;
+    const int64_t b = blockIdx.y;
+    const int sy = min(max(org[2 * b] + y, 0), H - 1), sx = min(max(org[2 * b + 1], 0), W - cw);
+    const uint8_t* src = in + ((b * H + sy) * (int64_t)W + sx) * 3;
+    uint8_t* dst = tmp + (b * ch + y) * (int64_t)Wout * 3;
+    const int nb = cw * 3;
+    if (!kk) {
+        for (int o = threadIdx.x; o < nb; o += blockDim.x) dst[o] = src[o];
+        return;
+    }
+    for (int i = threadIdx.x; i < nb; i += blockDim.x) row[i] = src[i];
+    __syncthreads();
+    for (int o = threadIdx.x; o < Wout * 3; o += blockDim.x) {
+        const int xx = o / 3, c = o - xx * 3;
+        const int xmin = bounds[2 * xx], xmax = bounds[2 * xx + 1];
+        const int32_t* k = kk + (int64_t)xx * ksize;
+        const uint8_t* p = row + xmin * 3 + c;
+        int32_t ss = 1 << (PRECISION_BITS - 1);
+        for (int x = 0; x < xmax; ++x) ss += (int32_t)p[x * 3] * k[x];
+        dst[o] = (uint8_t)clip8(ss >> PRECISION_BITS);
+    }
+}
+
 double sinc_filter(double x) {
     if (x == 0.0) return 1.0;
     x = x * M_PI;
@@ -527,21 +613,22 @@ double lanczos_filter(double x) {
     return 0.0;
 }
 
+double bilinear_filter(double x) {
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
+}
+
 bool mode_ok(int m) { return m == GSW_IMG_U8_HWC || m == GSW_IMG_F16_CHW || m == GSW_IMG_F32_CHW; }
 
-}  // namespace
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// host C ABI
-// ---------------------------------------------------------------------------------------------------------------------------
-int gsw_lanczos_plan(int in_size, int out_size, int32_t* bounds, int32_t* kk, int kk_capacity) {
-    // Resample.c precompute_coeffs (double, libm sin) + normalize_coeffs_8bpc for the whole-image box.  Returns ksize (> 0), or a
-    // negative gsw_status.  bounds == kk == NULL: size query only.
+// Resample.c precompute_coeffs (double, libm sin) + normalize_coeffs_8bpc for the whole-image box.  Returns ksize (> 0), or a
+// negative gsw_status.  bounds == kk == NULL: size query only.
+int resample_plan(double (*filter)(double), double filter_support, int in_size, int out_size, int32_t* bounds, int32_t* kk, int kk_capacity) {
     if (in_size <= 0 || out_size <= 0) return -GSW_ERR_BAD_ARG;
     double scale, filterscale;
     filterscale = scale = (double)in_size / out_size;
     if (filterscale < 1.0) filterscale = 1.0;
-    const double support = 3.0 * filterscale;
+    const double support = filter_support * filterscale;
     const int ksize = (int)std::ceil(support) * 2 + 1;
     if (!bounds && !kk) return ksize;
     if (!bounds || !kk || (int64_t)kk_capacity < (int64_t)out_size * ksize) return -GSW_ERR_BAD_ARG;
@@ -557,7 +644,7 @@ int gsw_lanczos_plan(int in_size, int out_size, int32_t* bounds, int32_t* kk, in
         xmax -= xmin;
         int32_t* k = kk + (int64_t)xx * ksize;
         for (int x = 0; x < xmax; ++x) {
-            w[x] = lanczos_filter((x + xmin - center + 0.5) * ss);
+            w[x] = filter((x + xmin - center + 0.5) * ss);
             ww += w[x];
         }
         for (int x = 0; x < xmax; ++x) {
@@ -569,6 +656,21 @@ int gsw_lanczos_plan(int in_size, int out_size, int32_t* bounds, int32_t* kk, in
         bounds[2 * xx + 1] = xmax;
     }
     return ksize;
+}
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// host C ABI
+// ---------------------------------------------------------------------------------------------------------------------------
+int gsw_lanczos_plan(int in_size, int out_size, int32_t* bounds, int32_t* kk, int kk_capacity) {
+    return resample_plan(lanczos_filter, 3.0, in_size, out_size, bounds, kk, kk_capacity);
+}
+
+int gsw_resample_plan(int filter, int in_size, int out_size, int32_t* bounds, int32_t* kk, int kk_capacity) {
+    if (filter == GSW_RESAMPLE_LANCZOS) return resample_plan(lanczos_filter, 3.0, in_size, out_size, bounds, kk, kk_capacity);
+    if (filter == GSW_RESAMPLE_BILINEAR) return resample_plan(bilinear_filter, 1.0, in_size, out_size, bounds, kk, kk_capacity);
+    return -GSW_ERR_BAD_ARG;
 }
 
 int gsw_resize_lanczos(const uint8_t* in_dev, int B, int Hin, int Win, void* out_dev, int Hout, int Wout, int out_mode, uint8_t* tmp_dev,
@@ -600,6 +702,49 @@ int gsw_resize_lanczos(const uint8_t* in_dev, int B, int Hin, int Win, void* out
         hipLaunchKernelGGL(gsw_resample_v_kernel, dim3(Hout, B), dim3(256), 0, st, src, out_dev, vbounds_dev, vkk_dev, vksize, Hin, Hout, Wout, 3, out_mode);
     else
         hipLaunchKernelGGL(gsw_image_convert_kernel, dim3(Hout, B), dim3(256), 0, st, src, out_dev, Hout, Wout, 3, out_mode);
+    GSW_IMG_LAUNCH_CHECK();
+    return GSW_OK;
+}
+
+int gsw_affine_nearest(const uint8_t* in_dev, int B, int H, int W, const int32_t* coeffs_dev, void* out_dev, int out_mode, void* stream) {
+    if (!in_dev || !out_dev || !coeffs_dev || B <= 0 || H <= 0 || W <= 0 || !mode_ok(out_mode)) return GSW_ERR_BAD_ARG;
+    if (B > 65535) return GSW_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(gsw_affine_nearest_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, coeffs_dev, H, W, out_mode);
+    GSW_IMG_LAUNCH_CHECK();
+    return GSW_OK;
+}
+
+int gsw_box_mask(const uint8_t* in_dev, int B, int H, int W, const int32_t* boxes_dev, int keep_inside, void* out_dev, int out_mode, void* stream) {
+    if (!in_dev || !out_dev || !boxes_dev || B <= 0 || H <= 0 || W <= 0 || !mode_ok(out_mode)) return GSW_ERR_BAD_ARG;
+    if (B > 65535) return GSW_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(gsw_box_mask_kernel, dim3(H, B), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, boxes_dev, H, W, keep_inside, out_mode);
+    GSW_IMG_LAUNCH_CHECK();
+    return GSW_OK;
+}
+
+int gsw_crop_resize(const uint8_t* in_dev, int B, int H, int W, const int32_t* origins_dev, int crop_h, int crop_w, void* out_dev, int Hout, int Wout,
+                    int out_mode, uint8_t* tmp_dev, const int32_t* hbounds_dev, const int32_t* hkk_dev, int hksize, const int32_t* vbounds_dev,
+                    const int32_t* vkk_dev, int vksize, void* stream) {
+    if (!in_dev || !out_dev || !origins_dev || !tmp_dev || B <= 0 || H <= 0 || W <= 0 || Hout <= 0 || Wout <= 0 || !mode_ok(out_mode)) return GSW_ERR_BAD_ARG;
+    if (crop_h <= 0 || crop_w <= 0 || crop_h > H || crop_w > W) return GSW_ERR_BAD_ARG;
+    const bool need_h = Wout != crop_w, need_v = Hout != crop_h;                 // Resample.c ImagingResample: a pass is skipped when the size is kept
+    if ((need_h && (!hbounds_dev || !hkk_dev || hksize <= 0)) || (need_v && (!vbounds_dev || !vkk_dev || vksize <= 0))) return GSW_ERR_BAD_ARG;
+    if (B > 65535 || (int64_t)crop_w * 3 > 160 * 1024) return GSW_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    // crop (+ horizontal pass) into tmp_dev [B, crop_h, Wout, 3], then the vertical pass (or the plain conversion) into out_dev
+    const size_t lds = need_h ? (size_t)crop_w * 3 : 0;
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute((const void*)gsw_crop_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) { g_img_hip_error = (int)e; return GSW_ERR_HIP; }
+    }
+    hipLaunchKernelGGL(gsw_crop_h_kernel, dim3(crop_h, B), dim3(256), lds, st, in_dev, tmp_dev, origins_dev, need_h ? hbounds_dev : nullptr, need_h ? hkk_dev : nullptr,
+                       hksize, H, W, crop_h, crop_w, Wout);
+    GSW_IMG_LAUNCH_CHECK();
+    if (need_v)
+        hipLaunchKernelGGL(gsw_resample_v_kernel, dim3(Hout, B), dim3(256), 0, st, (const uint8_t*)tmp_dev, out_dev, vbounds_dev, vkk_dev, vksize, crop_h, Hout, Wout, 3,
+                           out_mode);
+    else
+        hipLaunchKernelGGL(gsw_image_convert_kernel, dim3(Hout, B), dim3(256), 0, st, (const uint8_t*)tmp_dev, out_dev, Hout, Wout, 3, out_mode);
     GSW_IMG_LAUNCH_CHECK();
     return GSW_OK;
 }

@@ -445,6 +445,38 @@ typedef enum gsw_pointwise_op {
 int gsw_image_pointwise(const uint8_t* rgb_dev, int B, int H, int W, int op, float strength, uint64_t seed, uint64_t image_index0,
                         void* out_dev, int out_mode, uint64_t* workspace_dev, void* stream);
 
+/* Geometric attacks of distortions:107-137,207-222 (rotation, resizedcrop, erasing, randomcrop).  One launch per batch (two for the
+ * crop and resize); the per-image tables are device arrays, so nothing here synchronises with the host. */
+
+/* Pillow's resampling filters, numbered as PIL.Image.Resampling numbers them. */
+typedef enum gsw_resample_filter {
+    GSW_RESAMPLE_LANCZOS = 1,
+    GSW_RESAMPLE_BILINEAR = 2
+} gsw_resample_filter;
+
+/* gsw_lanczos_plan for any filter of gsw_resample_filter (Resample.c precompute_coeffs + normalize_coeffs_8bpc); for LANCZOS the
+ * same arrays as gsw_lanczos_plan.  Pure host function. */
+int gsw_resample_plan(int filter, int in_size, int out_size, int32_t* bounds, int32_t* kk, int kk_capacity);
+
+/* distortions:107-113 "rotation": `img.rotate(angle, NEAREST, expand=False, fillcolor=0)` = Geometry.c affine_fixed.
+ * coeffs_dev: int32 [B, 6] = (a0, a1, a2, a3, a4, a5) in 16.16 fixed point per image; output pixel (x, y) reads source
+ * ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16) in wrapping 32-bit arithmetic, black outside the image.  The transpose fast
+ * paths (0, 90, 180, 270 degrees) are integer coefficient rows too.  out_dev must not alias in_dev. */
+int gsw_affine_nearest(const uint8_t* in_dev, int B, int H, int W, const int32_t* coeffs_dev, void* out_dev, int out_mode, void* stream);
+
+/* distortions:126-137 "erasing" (keep_inside = 0: the rectangle becomes 0) and :207-222 "randomcrop" (keep_inside != 0: the rectangle
+ * is kept, everything else becomes 0).  boxes_dev: int32 [B, 4] = (top, left, height, width) per image, inside the image (the
+ * caller checks; an empty box is allowed). */
+int gsw_box_mask(const uint8_t* in_dev, int B, int H, int W, const int32_t* boxes_dev, int keep_inside, void* out_dev, int out_mode, void* stream);
+
+/* distortions:115-124 "resizedcrop": `img.crop((left, top, left + crop_w, top + crop_h)).resize((Wout, Hout), filter)` per image, a
+ * shared crop size and per-image origins_dev int32 [B, 2] = (top, left) inside the image (the caller checks).  Pillow's two passes,
+ * horizontal first, uint8 in between, a pass skipped when its size is kept.  tmp_dev: [B, crop_h, Wout, 3] uint8 scratch.  Plans:
+ * gsw_resample_plan for (crop_w -> Wout) and (crop_h -> Hout); NULL for a skipped pass. */
+int gsw_crop_resize(const uint8_t* in_dev, int B, int H, int W, const int32_t* origins_dev, int crop_h, int crop_w, void* out_dev, int Hout,
+                    int Wout, int out_mode, uint8_t* tmp_dev, const int32_t* hbounds_dev, const int32_t* hkk_dev, int hksize,
+                    const int32_t* vbounds_dev, const int32_t* vkk_dev, int vksize, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
