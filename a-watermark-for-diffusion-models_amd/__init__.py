@@ -5,11 +5,12 @@ through the `gswm_amd` loader module at the repo root:
     import gswm_amd
     from gswm_amd import gs_insert, extract          # drop-in twins of the reference's modules
     from gswm_amd import codec                        # batch-first device API over the C ABI (include/gswm.h)
+    from gswm_amd import trace                        # registry of issued messages: which user made this image, and how sure
 """
 from . import _native  # noqa: F401
 from . import codec  # noqa: F401
 
-__all__ = ["codec", "gs_insert", "extract", "comfy", "ddim", "dist", "distortions"]
+__all__ = ["codec", "gs_insert", "extract", "comfy", "ddim", "dist", "distortions", "trace"]
 
 
 def __getattr__(name):  # lazy sub-modules (keep `import gswm_amd` light)

@@ -20,6 +20,7 @@ GSW_MSG_INLINE_MAX = 256
 GSW_IMG_U8_HWC, GSW_IMG_F16_CHW, GSW_IMG_F32_CHW = 0, 1, 2
 GSW_PW_BRIGHTNESS, GSW_PW_CONTRAST, GSW_PW_INVERT, GSW_PW_GRAY, GSW_PW_HFLIP, GSW_PW_VFLIP, GSW_PW_NOISE = range(7)
 GSW_RESAMPLE_LANCZOS, GSW_RESAMPLE_BILINEAR = 1, 2
+GSW_TRACE_SOFT, GSW_TRACE_HARD = 0, 1
 
 _u8p = C.POINTER(C.c_uint8)
 
@@ -123,6 +124,8 @@ _PROTOTYPES = {
     "gsw_conv3x3_res_pf_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                         C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gsw_conv_up2x_pf_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gsw_trace_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "gsw_trace_topk": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

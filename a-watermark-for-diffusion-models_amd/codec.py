@@ -200,6 +200,52 @@ def bits_to_str(bits_row) -> str:
     return "".join(format(int(b), "08b") for b in bits_row)
 
 
+# ------------------------------------------------------------------------------------------------ tracing (registry search)
+def vote_copies(n_elems: int, message_length: int) -> int:
+    """Votes per message bit: the lattice padded to whole bytes (extract.py:88-92) splits into this many message_length-wide segments.
+    Raises IndexError where `extract_batch` does (the padded bit count is not a multiple of message_length, extract.py:98)."""
+    n, m = int(n_elems), int(message_length)
+    if n <= 0 or m <= 0:
+        raise ValueError("n_elems and message_length must be positive")
+    padded = (n + 7) // 8 * 8
+    if padded % m:
+        raise IndexError("string index out of range")
+    return padded // m
+
+
+def trace_topk(counts: torch.Tensor, copies: int, registry_bits: torch.Tensor, k: int = 1, soft: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k registry rows that best match each image's votes: (idx int32 [B, k], score int32 [B, k]), best first, ties towards the
+    lower row; past the registry's end idx = -1 and score = INT32_MIN.
+
+    counts: int32 [B, M] '1'-vote counts (`extract_batch(..., return_counts=True)`), copies: votes per bit (`vote_copies`),
+    registry_bits: uint8 [U, M/8] messages packed MSB first (`trace.Registry.to_device`).
+    score = sum_t (2 r[t] - 1) w[t] with w = 2 c - copies (soft) or the majority bit as +-1 (hard: score = 2 agree - M)."""
+    _need_gpu(counts, "counts")
+    _need_gpu(registry_bits, "registry_bits")
+    if counts.dtype != torch.int32 or counts.dim() != 2:
+        raise ValueError("counts must be int32 [B, M]")
+    if registry_bits.dtype != torch.uint8 or registry_bits.dim() != 2:
+        raise ValueError("registry_bits must be uint8 [U, M/8]")
+    if registry_bits.device != counts.device:
+        raise RuntimeError(f"registry_bits lives on {registry_bits.device}, expected {counts.device}")
+    B, M = counts.shape
+    U = registry_bits.shape[0]
+    if registry_bits.shape[1] * 8 != M:
+        raise ValueError(f"registry rows hold {registry_bits.shape[1] * 8} bits, counts {M}")
+    k = int(k)
+    lib = N.lib()
+    ws_bytes = lib.gsw_trace_workspace_bytes(B, U, k)
+    if ws_bytes == 0:
+        raise ValueError(f"libgswm: bad argument (B={B}, users={U}, k={k}: need B >= 1, 1 <= users < 2**31, 1 <= k <= 8)")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=counts.device)
+    idx = torch.empty((B, k), dtype=torch.int32, device=counts.device)
+    score = torch.empty((B, k), dtype=torch.int32, device=counts.device)
+    with torch.cuda.device(counts.device):
+        N.check(lib.gsw_trace_topk(counts.data_ptr(), B, M, int(copies), N.GSW_TRACE_SOFT if soft else N.GSW_TRACE_HARD,
+                                   registry_bits.data_ptr(), U, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))
+    return idx, score
+
+
 # ------------------------------------------------------------------------------------------------ X2 / G1 elementwise
 def ddim_step(x: torch.Tensor, model_out: torch.Tensor, a: float, b: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = a*x + b*model_out (fp32 math, one rounding). out may be x (in place)."""

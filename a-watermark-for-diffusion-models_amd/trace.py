@@ -1,0 +1,494 @@
+"""Traceability: given inverted latents and a registry of issued messages, which user made the image -- and how sure are we.
+
+The reference stops at "bit accuracy against the one message you already know" (extract.py:103-110).  A service that issues one
+message per user asks the opposite question: the message is unknown, the candidates are every message ever issued.  This module
+holds the registry (`Registry`), the search (`trace_latents`: `codec.extract_batch` vote counts -> `codec.trace_topk`, one HIP launch
+over the packed registry) and the statistics that turn a score into a false-positive bound, plus a front end
+(`python -m gswm_amd.trace`) on `extract`'s image -> latent -> inversion harness.
+
+Scores.  With c[t] the number of '1' votes of message bit t out of V and r[t] the candidate's bit,
+    soft (default): s = sum_t (2 r[t] - 1) (2 c[t] - V)      the vote margins: a bit that won 64:0 counts more than one that won 33:31
+    hard:           s = 2 agree - M                          agree = bits of the reference's majority vote (ties -> 0) equal to r
+
+Null model (the paper's): for an image that carries no watermark under this key the decrypted signs are independent fair bits.
+* soft: s is a signed sum over all n = M V lattice bits, so for any fixed message s = 2 X - n with X ~ Bin(n, 1/2) EXACTLY, ties and
+  all (`log10_p_soft`).  When the lattice size is not a multiple of 8 the up-to-7 padding bits are keystream, not image; they are fair
+  bits as well, but not the image's.
+* hard: ties -> 0 bias the voted bits when V is even, so agree is not Bin(M, 1/2); it is stochastically dominated by Bin(M, q),
+  q = (1 + C(V, V/2) / 2^V) / 2 (q = 1/2 for odd V), and the tail of that is an upper bound (`log10_p_hard`).
+Both tails are summed as Python integers and converted to a double once, at the end.  Over a registry of U users the reported value is
+the Bonferroni bound min(0, log10 p + log10 U); an image is attributed iff that is <= log10(fpr).
+
+Single key: every candidate shares one ChaCha20 key / nonce.  Per-user keys (one keystream per candidate) are out of scope.
+"""
+from __future__ import annotations
+
+import math
+import os
+import sys
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import codec
+
+INT32_MIN = -2 ** 31
+_LOG10_2 = math.log10(2.0)
+
+
+# ===================================================================================================================== statistics
+def _log10_ratio(num: int, den: int) -> float:
+    """log10(num / den) for integers 0 <= num <= den of any size; the only inexact steps are one correctly rounded division and
+    the logarithm of its result."""
+    if num <= 0:
+        return -math.inf
+    if num >= den:
+        return 0.0
+    if 2 * num > den:                                   # close to 1: go through the complement
+        return math.log1p(-((den - num) / den)) / math.log(10.0)
+    shift = den.bit_length() - num.bit_length()         # (num << shift) / den is in (1/2, 2): no underflow however small the ratio
+    return math.log10((num << shift) / den) - shift * _LOG10_2
+
+
+def _binomial_tail(n: int, x0: int, a: int = 1, b: int = 1) -> int:
+    """sum_{x >= x0} C(n, x) a^x b^(n-x), exact"""
+    x0 = max(int(x0), 0)
+    if x0 > n:
+        return 0
+    c = math.comb(n, x0)
+    if a == 1 and b == 1:
+        total = 0
+        for x in range(x0, n + 1):
+            total += c
+            c = c * (n - x) // (x + 1)
+        return total
+    total = 0
+    pa, pb = a ** x0, [1] * (n - x0 + 1)
+    for i in range(1, n - x0 + 1):
+        pb[i] = pb[i - 1] * b
+    for x in range(x0, n + 1):
+        total += c * pa * pb[n - x]
+        c = c * (n - x) // (x + 1)
+        pa *= a
+    return total
+
+
+def log10_p_soft(score: int, n: int) -> float:
+    """log10 P[S >= score] for S = 2 X - n, X ~ Bin(n, 1/2): the soft score of a fixed message under the null model, n = M V."""
+    score, n = int(score), int(n)
+    if n < 1:
+        raise ValueError("n must be positive")
+    x0 = -((-(score + n)) // 2)                         # ceil((score + n) / 2)
+    return _log10_ratio(_binomial_tail(n, x0), 1 << n)
+
+
+def hard_match_probability(V: int) -> Tuple[int, int]:
+    """q = (1 + C(V, V/2) / 2^V) / 2 as a ratio of integers (1/2 for odd V): the largest probability with which a voted bit of an
+    unwatermarked image equals a given message bit (a tie votes 0, which favours message bits that are 0)."""
+    V = int(V)
+    if V < 1:
+        raise ValueError("V must be positive")
+    if V % 2:
+        return 1, 2
+    return (1 << V) + math.comb(V, V // 2), 1 << (V + 1)
+
+
+def log10_p_hard(agree: int, M: int, V: int) -> float:
+    """Upper bound of log10 P[agree' >= agree] under the null model: the tail of Bin(M, q), q = hard_match_probability(V)."""
+    agree, M = int(agree), int(M)
+    if M < 1:
+        raise ValueError("M must be positive")
+    a, d = hard_match_probability(V)
+    return _log10_ratio(_binomial_tail(M, agree, a, d - a), d ** M)
+
+
+def log10_p_any(log10_p: float, n_users: int) -> float:
+    """Bonferroni bound over a registry: min(0, log10 p + log10 U)"""
+    return min(0.0, log10_p + math.log10(int(n_users)))
+
+
+# ===================================================================================================================== host oracle
+def topk_host(counts, copies: int, registry_bits, k: int, soft: bool = True):
+    """NumPy restatement of `codec.trace_topk` (int64 arithmetic, a stable sort): (idx int32 [B, k], score int32 [B, k]).
+    counts [B, M] '1'-votes, registry_bits uint8 [U, M/8] MSB first.  Shares no code with the device path."""
+    c = np.asarray(counts).astype(np.int64)
+    reg = np.asarray(registry_bits, dtype=np.uint8)
+    B, M = c.shape
+    U = reg.shape[0]
+    V = int(copies)
+    if reg.shape[1] * 8 != M:
+        raise ValueError("registry rows and counts disagree on the message length")
+    w = (2 * c - V) if soft else np.where(2 * c > V, 1, -1).astype(np.int64)
+    scores = np.empty((B, U), dtype=np.int64)
+    step = max(1, (1 << 24) // max(M, 1))
+    for u0 in range(0, U, step):
+        r = np.unpackbits(reg[u0:u0 + step], axis=1, bitorder="big").astype(np.int64)
+        scores[:, u0:u0 + step] = w @ (2 * r - 1).T
+    idx = np.full((B, k), -1, dtype=np.int32)
+    out = np.full((B, k), INT32_MIN, dtype=np.int32)
+    order = np.argsort(-scores, axis=1, kind="stable")[:, :k]          # stable: equal scores keep ascending index
+    m = order.shape[1]
+    idx[:, :m] = order
+    out[:, :m] = np.take_along_axis(scores, order, axis=1)
+    return idx, out
+
+
+# ===================================================================================================================== registry
+def _as_bytes(x, what: str) -> Optional[bytes]:
+    if x is None:
+        return None
+    if isinstance(x, str):
+        return bytes.fromhex(x)
+    if isinstance(x, (bytes, bytearray)):
+        return bytes(x)
+    raise TypeError(f"{what} must be bytes or a hex string")
+
+
+class Registry:
+    """Ordered, unique user_id -> message bytes, all of one length (`message_bytes`, default 32 = what gs_insert embeds)."""
+
+    def __init__(self, message_bytes: int = 32):
+        if int(message_bytes) < 1:
+            raise ValueError("message_bytes must be positive")
+        self.message_bytes = int(message_bytes)
+        self._ids: List[str] = []
+        self._messages: List[bytes] = []
+        self._by_id: Dict[str, int] = {}
+        self._by_message: Dict[bytes, int] = {}
+        self._device_cache = {}
+
+    # -- content
+    def __len__(self) -> int:
+        return len(self._ids)
+
+    @property
+    def message_bits(self) -> int:
+        return 8 * self.message_bytes
+
+    @property
+    def user_ids(self) -> List[str]:
+        return list(self._ids)
+
+    def message(self, user_id: str) -> bytes:
+        return self._messages[self._by_id[user_id]]
+
+    def user_at(self, index: int) -> str:
+        return self._ids[index]
+
+    def message_at(self, index: int) -> bytes:
+        return self._messages[index]
+
+    def add(self, user_id: str, message: Union[str, bytes]) -> int:
+        """Register `message` for `user_id`; returns the row index.  A str is what gs_insert would embed for it
+        (`codec.pad_message`: UTF-8, zero-padded or cut to message_bytes); bytes must have the registry's length."""
+        if not isinstance(user_id, str) or not user_id or any(ch in user_id for ch in "\t\r\n"):
+            raise ValueError(f"user id {user_id!r} must be a non-empty string without tabs or line breaks")
+        if isinstance(message, str):
+            if not message:
+                raise ValueError(f"user {user_id!r}: an empty message string cannot be registered (pad_message would draw random bytes)")
+            msg = codec.pad_message(message, self.message_bytes)
+        elif isinstance(message, (bytes, bytearray)):
+            msg = bytes(message)
+            if len(msg) != self.message_bytes:
+                raise ValueError(f"user {user_id!r}: message has {len(msg)} bytes, the registry holds {self.message_bytes}-byte messages")
+        else:
+            raise TypeError(f"user {user_id!r}: message must be str or bytes")
+        if user_id in self._by_id:
+            raise ValueError(f"user id {user_id!r} is already registered")
+        if msg in self._by_message:
+            raise ValueError(f"user {user_id!r}: message {msg.hex()} is already registered to {self._ids[self._by_message[msg]]!r}")
+        self._by_id[user_id] = self._by_message[msg] = len(self._ids)
+        self._ids.append(user_id)
+        self._messages.append(msg)
+        self._device_cache.clear()
+        return len(self._ids) - 1
+
+    # -- files
+    def save(self, path) -> None:
+        """one `user_id<TAB>message_hex` per line"""
+        with open(path, "w") as f:
+            for uid, msg in zip(self._ids, self._messages):
+                f.write(f"{uid}\t{msg.hex()}\n")
+
+    @classmethod
+    def load(cls, path) -> "Registry":
+        reg = None
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                line = line.rstrip("\r\n")
+                if not line:
+                    continue
+                uid, sep, hx = line.partition("\t")
+                if not sep:
+                    raise ValueError(f"{path}:{no}: expected 'user_id<TAB>message_hex'")
+                try:
+                    msg = bytes.fromhex(hx.strip())
+                except ValueError:
+                    raise ValueError(f"{path}:{no}: message of user {uid!r} is not hexadecimal") from None
+                if reg is None:
+                    reg = cls(len(msg))
+                reg.add(uid, msg)
+        if reg is None:
+            raise ValueError(f"{path}: no registry entries")
+        return reg
+
+    @classmethod
+    def from_info_data(cls, path, key=None, nonce=None) -> "Registry":
+        """The log gs_insert (and the reference, gs_insert.py:68-74) appends per issued watermark -- records of
+        `Time: / key: / nonce: / message: / ------` lines -- read as a registry: the records of the given key and nonce (bytes or hex;
+        None keeps any), repeated messages dropped, ids `info:<record number>` (1-based over ALL records of the file)."""
+        key, nonce = _as_bytes(key, "key"), _as_bytes(nonce, "nonce")
+        reg, rec, number = None, {}, 0
+        with open(path) as f:
+            for line in f:
+                line = line.strip()
+                if line.startswith("-----"):
+                    if "message" in rec:
+                        number += 1
+                        ok = (key is None or rec.get("key") == key.hex()) and (nonce is None or rec.get("nonce") == nonce.hex())
+                        if ok:
+                            msg = bytes.fromhex(rec["message"])
+                            if reg is None:
+                                reg = cls(len(msg))
+                            if msg not in reg._by_message:
+                                reg.add(f"info:{number}", msg)
+                    rec = {}
+                    continue
+                name, sep, value = line.partition(":")
+                if sep and name in ("key", "nonce", "message"):
+                    rec[name] = value.strip().lower()
+        if reg is None:
+            raise ValueError(f"{path}: no record matches the given key / nonce")
+        return reg
+
+    @classmethod
+    def from_file(cls, path, key=None, nonce=None) -> "Registry":
+        """Either format, told apart by the first line"""
+        return cls.from_info_data(path, key, nonce) if detect_format(path) == "info_data" else cls.load(path)
+
+    # -- device
+    def packed(self, message_length: Optional[int] = None) -> np.ndarray:
+        """uint8 [U, message_length / 8]: one message per row, MSB first as the codec packs them; a message_length that is a multiple
+        of the registered length repeats the rows (the embed repeats its message over the lattice in the same way)."""
+        m = self.message_bits if message_length is None else int(message_length)
+        if m <= 0 or m % self.message_bits:
+            raise ValueError(f"message_length {m} is not a multiple of the registered length {self.message_bits}")
+        if not self._ids:
+            raise ValueError("the registry is empty")
+        t = self._device_cache.get(("host", m))
+        if t is None:
+            rows = np.frombuffer(b"".join(self._messages), dtype=np.uint8).reshape(len(self._ids), self.message_bytes)
+            t = self._device_cache[("host", m)] = np.ascontiguousarray(np.tile(rows, (1, m // self.message_bits)))
+        return t
+
+    def to_device(self, device="cuda", message_length: Optional[int] = None):
+        import torch
+        m = self.message_bits if message_length is None else int(message_length)
+        k = (str(torch.device(device)), m)
+        t = self._device_cache.get(k)
+        if t is None:
+            t = self._device_cache[k] = torch.from_numpy(self.packed(m)).to(device)
+        return t
+
+
+def detect_format(path) -> str:
+    """'info_data' when the first non-empty line is a `Time:` line of gs_insert's log, else 'registry'"""
+    with open(path) as f:
+        for line in f:
+            if line.strip():
+                return "info_data" if line.startswith("Time:") and "\t" not in line else "registry"
+    raise ValueError(f"{path} is empty")
+
+
+# ===================================================================================================================== tracing
+@dataclass
+class Candidate:
+    user_id: str
+    index: int
+    score: int
+    agree: int                  # voted bits equal to the candidate's message (what codec.bit_matches gives for it)
+    log10_p_any: float          # Bonferroni bound over the registry
+
+
+@dataclass
+class TraceResult:
+    candidates: List[Candidate] = field(default_factory=list)
+    attributed: Optional[str] = None       # the best candidate's user id if its bound is <= log10(fpr), else None: no registered user
+
+
+def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, message_length: Optional[int] = None, k: int = 1,
+                  fpr: float = 1e-6, soft: bool = True) -> List[Union[TraceResult, ValueError]]:
+    """latents [B, ...] on the device -> one TraceResult per image (best candidate first), or the ValueError the reference raises for
+    that image (a saturated / NaN latent, extract.py:84-86), like `extract.recover_exactracted_message_batch`.
+
+    One vote kernel, one search launch over the packed registry; the host receives the B k pairs (plus the vote's flags and bits)."""
+    import torch
+    from . import _native as N
+    if not 0.0 < float(fpr) <= 1.0:
+        raise ValueError("fpr must be in (0, 1]")
+    M = registry.message_bits if message_length is None else int(message_length)
+    z = latents.contiguous()
+    B = z.shape[0]
+    rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
+    V = codec.vote_copies(z.numel() // max(B, 1), M)
+    reg_dev = registry.to_device(z.device, M)
+    bits, flags, counts = codec.extract_batch(z, key, nonce, M, return_counts=True)
+    idx, score = codec.trace_topk(counts, V, reg_dev, k=k, soft=soft)
+    pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy; flags and voted bits are the vote's own outputs
+    idx_h, score_h = pairs[0], pairs[1]
+    flags_h, bits_h = flags.cpu().numpy(), bits.cpu().numpy()
+    U, limit = len(registry), math.log10(float(fpr))
+    out: List[Union[TraceResult, ValueError]] = []
+    for b in range(B):
+        if flags_h[b] & N.GSW_FLAG_NAN:
+            out.append(ValueError("cannot convert float NaN to integer"))
+            continue
+        if flags_h[b] & N.GSW_FLAG_SATURATED:
+            out.append(ValueError("invalid literal for int() with base 2"))
+            continue
+        res = TraceResult()
+        for j in range(k):
+            i, s = int(idx_h[b, j]), int(score_h[b, j])
+            if i < 0:
+                break
+            agree = M - int(np.unpackbits(bits_h[b] ^ rows[i]).sum())
+            lp = log10_p_soft(s, M * V) if soft else log10_p_hard(agree, M, V)
+            res.candidates.append(Candidate(registry.user_at(i), i, s, agree, log10_p_any(lp, U)))
+        if res.candidates and res.candidates[0].log10_p_any <= limit:
+            res.attributed = res.candidates[0].user_id
+        out.append(res)
+    return out
+
+
+# ===================================================================================================================== front end
+def format_line(name: str, result, message_length: int) -> str:
+    """One line of trace.txt / stdout"""
+    if isinstance(result, Exception):
+        return f"Error processing {name}: {result}"
+    if not result.candidates:
+        return f"{name}, user: none, agreement, nan, log10 p, 0.0"
+    c = result.candidates[0]
+    text = f"{name}, user: {result.attributed if result.attributed is not None else 'none'}, agreement, {c.agree / message_length}, log10 p, {c.log10_p_any:.3f}"
+    for o in result.candidates[1:]:
+        text += f", next: {o.user_id} ({o.agree / message_length}, {o.log10_p_any:.3f})"
+    return text
+
+
+def build_parser():
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m gswm_amd.trace",
+                                description="Trace images to the registered user whose watermark they carry (single GPU, one key for all users; "
+                                            "sharding over --gpus and per-user keys are out of scope of this tool)")
+    p.add_argument("--model_id", default="stabilityai/stable-diffusion-2-1-base")
+    p.add_argument("--images_directory_path", default="", help="The path of directory containing images to process")
+    p.add_argument("--single_image_path", default="")
+    p.add_argument("--key_hex", required=True, help="Hexadecimal key used for encryption")
+    p.add_argument("--nonce_hex", required=True, help="Hexadecimal nonce used for encryption, It will use the fixed part of the key if nonce is none")
+    p.add_argument("--registry", required=True, help="registry file: 'user_id<TAB>message_hex' lines, or the info_data.txt log gs_insert appends "
+                                                      "(told apart by the first line; of a log, the records of this key / nonce are used)")
+    p.add_argument("--fpr", type=float, default=1e-6, help="false-positive rate per image, over the whole registry (Bonferroni)")
+    p.add_argument("--top", type=int, default=1, choices=range(1, 9), metavar="K", help="candidates reported per image (1..8)")
+    p.add_argument("--hard", action="store_true", help="rank by the majority-voted bits instead of the vote margins")
+    p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
+    p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
+    p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
+    p.add_argument("--width", type=int, default=1024, help="Width of the input image")
+    p.add_argument("--height", type=int, default=1024, help="Height of the input image")
+    p.add_argument("--message_length", type=int, default=None, help="Length of the message in bits (default: the registry's own length; a multiple of it "
+                                                                     "repeats the registered messages, which weakens --hard)")
+    p.add_argument("--allow_synthetic_weights", action="store_true", help="run without a checkpoint (pipeline tests / benchmarks only)")
+    p.add_argument("--batch_size", type=int, default=16, help="images per device batch")
+    p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
+                   help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
+    return p
+
+
+def _trace_files(files: Sequence[str], args, registry: Registry) -> list:
+    """files -> outcomes in order (TraceResult or the exception that file raised): decode on host threads, invert and trace in device
+    batches; a batch that raises is redone image by image so that each reports its own error (extract._recover_items does the same)."""
+    from concurrent.futures import ThreadPoolExecutor
+    from . import extract as X
+
+    def decode(f):
+        try:
+            return X.decode_image_file(f)
+        except Exception as e:
+            return e
+
+    def run(arrs):
+        latents = X.invert_decoded_images(arrs, args)
+        return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard)
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
+        decoded = list(pool.map(decode, files))
+    out = list(decoded)
+    ready = [i for i, r in enumerate(decoded) if not isinstance(r, Exception)]
+    for k0 in range(0, len(ready), int(args.batch_size)):
+        idx = ready[k0:k0 + int(args.batch_size)]
+        try:
+            results = run([decoded[i] for i in idx])
+        except Exception:
+            results = []
+            for i in idx:
+                try:
+                    results += run([decoded[i]])
+                except Exception as e:
+                    results.append(e)
+        for i, r in zip(idx, results):
+            out[i] = r
+    return out
+
+
+def _report(job, outcomes, args, registry: Registry, synthetic: bool) -> None:
+    from . import extract as X
+    from datetime import datetime
+    M = args.message_length
+    with open(os.path.join(job.path, "trace.txt"), "a") as out:
+        bar = "=" * 40
+        fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("key_hex", args.key_hex), ("nonce_hex", args.nonce_hex), ("registry", args.registry),
+                  ("users", len(registry)), ("message_length", M), ("statistic", "hard" if args.hard else "soft"), ("fpr", args.fpr),
+                  ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
+        out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
+        if synthetic:
+            out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the attributions below are not meaningful\n")
+        for f, r in zip(job.files, outcomes):
+            line = format_line(f if isinstance(r, Exception) else os.path.basename(f), r, M)
+            print(line)
+            out.write(line + "\n")
+        out.write(bar + "Batch End" + bar + "\n")
+
+
+def main(argv=None):
+    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    from . import extract as X
+    args.key = bytes.fromhex(args.key_hex)
+    args.nonce = bytes.fromhex(args.nonce_hex) if args.nonce_hex != "" else bytes.fromhex(args.key_hex[16:48])
+    registry = Registry.from_file(args.registry, args.key, args.nonce)
+    if args.message_length is None:
+        args.message_length = registry.message_bits
+    registry.packed(args.message_length)                 # a message_length the registry cannot be tiled to fails here, before any model loads
+    synthetic = X._no_checkpoint(args.model_id)
+    with X._strictness(args, synthetic):
+        if args.images_directory_path != "":
+            script = X._plan(args)
+            jobs = [j for kind, j in script if kind == "job"]
+            if any(j.files for j in jobs):
+                X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))      # fail before touching any result file
+            for kind, x in script:
+                if kind == "banner":
+                    print("=" * 20 + x + "=" * 20)
+                elif x.files:
+                    _report(x, _trace_files(x.files, args, registry), args, registry, synthetic)
+        elif args.single_image_path != "":
+            if synthetic:
+                X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))
+                print(f"{X.SYNTHETIC_MARKER}: '{args.model_id}' is not a local checkpoint, the attribution below is not meaningful", file=sys.stderr)
+            r = _trace_files([args.single_image_path], args, registry)[0]
+            print(format_line(args.single_image_path if isinstance(r, Exception) else os.path.basename(args.single_image_path), r, args.message_length))
+        else:
+            print("Please set the argument 'images_directory_path' or 'single_image_path'")
+
+
+if __name__ == "__main__":
+    main()

@@ -477,6 +477,35 @@ int gsw_crop_resize(const uint8_t* in_dev, int B, int H, int W, const int32_t* o
                     int Wout, int out_mode, uint8_t* tmp_dev, const int32_t* hbounds_dev, const int32_t* hkk_dev, int hksize,
                     const int32_t* vbounds_dev, const int32_t* vkk_dev, int vksize, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Tracing: which registered message does an extracted watermark belong to (additive entry points: nothing above changes and
+ * gsw_version() stays 500).
+ *
+ *   counts_dev   : uint32 [B, msg_bits], the counts output of gsw_extract ('1' votes per bit); copies = votes per bit
+ *                  (padded lattice bits / msg_bits, one number per call since gsw_extract refuses ragged lattices)
+ *   registry_dev : uint8 [n_users, msg_bits / 8], one issued message per row, packed as the codec packs messages
+ *                  (bit t -> byte t >> 3, bit 7 - (t & 7))
+ *   weights      : GSW_TRACE_SOFT  w = 2 c - copies (the vote margin);  GSW_TRACE_HARD  w = +1 if c > copies / 2 else -1 (the
+ *                  reference's strict majority, ties -> 0), in which case score = 2 agree - msg_bits
+ *   score[b, u]  = sum_t (2 r[u, t] - 1) w[b, t], an exact int32
+ *   idx_dev / score_dev : int32 [B, k], the k best users per image by score, descending, ties towards the lower index; past
+ *                  n_users (n_users < k): idx = -1, score = INT32_MIN
+ *   workspace_dev: gsw_trace_workspace_bytes(B, n_users, k) bytes owned by the caller (partial lists; no state is kept between calls
+ *                  and the result does not depend on the launch geometry)
+ *
+ * The scores go through the int8 matrix pipe with the registry bits expanded in registers; the [B, n_users] score matrix is never
+ * written and the registry is read packed, once per tile of up to 64 images (fewer when copies > 127 or msg_bits > 1024).  Exact for
+ * every copies up to 2 000 000 (int8 planes in base 128).  Registries of 2^19 rows and more are searched twice inside the call (a
+ * leading sample first, whose k-th best score bounds the full search from below); the answer is the same.
+ * GSW_ERR_BAD_ARG: null pointer, B < 1, msg_bits outside 8..2048 or not a multiple of 8, copies < 1, k outside 1..8, n_users outside
+ * 1..2^31-1, unknown mode.  GSW_ERR_UNSUPPORTED: msg_bits * copies >= 2^31, soft mode with copies > 2 000 000, B > 1 048 560.
+ * gsw_trace_workspace_bytes returns 0 for arguments gsw_trace_topk refuses. */
+#define GSW_TRACE_SOFT 0
+#define GSW_TRACE_HARD 1
+size_t gsw_trace_workspace_bytes(int B, int64_t n_users, int k);
+int gsw_trace_topk(const uint32_t* counts_dev, int B, int msg_bits, int copies, int mode, const uint8_t* registry_dev, int64_t n_users, int k,
+                   int32_t* idx_dev, int32_t* score_dev, void* workspace_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
