@@ -246,6 +246,68 @@ def trace_topk(counts: torch.Tensor, copies: int, registry_bits: torch.Tensor, k
     return idx, score
 
 
+# ------------------------------------------------------------------------------------------------ tracing (records with their own keys)
+KEYED_RECORD_HEAD = 48          # key[32] | nonce16[16], then the message
+
+
+def keyed_record_stride(msg_bytes: int) -> int:
+    """Bytes per row of a keyed registry: key | nonce | message, padded to a multiple of 16."""
+    return (KEYED_RECORD_HEAD + int(msg_bytes) + 15) // 16 * 16
+
+
+def sign_pack(z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """X3 alone: the quantised sign bits of latents z [B, ...] (fp16/bf16/fp32/fp64), packed MSB first, before any decryption:
+    (signs uint8 [B, n/8], flags int32 [B]); flags as `extract_batch` (a saturated element packs as 1, a NaN as 0).
+    n must be a multiple of 8."""
+    _need_gpu(z, "z")
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    if n < 8 or n % 8:
+        raise ValueError(f"sign_pack needs a lattice of a multiple of 8 elements per image (got {n})")
+    signs = torch.empty((B, n // 8), dtype=torch.uint8, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_sign_pack(z.data_ptr(), _dt(z.dtype), signs.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
+    return signs, flags
+
+
+def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k records whose codeword best matches each image's sign bits: (idx int32 [B, k], score int32 [B, k]), best first, ties
+    towards the lower row; past the registry's end idx = -1 and score = INT32_MIN.
+
+    signs: uint8 [B, n_bits / 8] (`sign_pack`), records: uint8 [U, stride] rows key[32] | nonce[16] | message[msg_bytes]
+    (`trace.KeyedRegistry.to_device`; stride >= 48 + msg_bytes, a multiple of 16).  The codeword of a record is what `embed_batch`
+    plants for its key, nonce and message; score = n_bits - 2 popcount(signs ^ codeword).  Raises IndexError when n_bits is not a
+    multiple of 8 msg_bytes (as `extract_batch` does for such a message length)."""
+    _need_gpu(signs, "signs")
+    _need_gpu(records, "records")
+    if signs.dtype != torch.uint8 or signs.dim() != 2:
+        raise ValueError("signs must be uint8 [B, n_bits / 8]")
+    if records.dtype != torch.uint8 or records.dim() != 2:
+        raise ValueError("records must be uint8 [U, stride]")
+    if records.device != signs.device:
+        raise RuntimeError(f"records lives on {records.device}, expected {signs.device}")
+    B, U, stride = signs.shape[0], records.shape[0], records.shape[1]
+    n_bits, msg_bytes, k = int(n_bits), int(msg_bytes), int(k)
+    if signs.shape[1] * 8 != n_bits:
+        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
+    if not 1 <= msg_bytes <= N.GSW_MSG_INLINE_MAX:
+        raise ValueError(f"msg_bytes {msg_bytes} is outside 1..{N.GSW_MSG_INLINE_MAX}")
+    if stride < KEYED_RECORD_HEAD + msg_bytes or stride % 16:
+        raise ValueError(f"record rows of {stride} bytes cannot hold key | nonce | {msg_bytes}-byte message at a multiple of 16")
+    lib = N.lib()
+    ws_bytes = lib.gsw_trace_keyed_workspace_bytes(B, U, k)
+    if ws_bytes == 0:
+        raise ValueError(f"libgswm: bad argument (B={B}, records={U}, k={k}: need B >= 1, 1 <= records < 2**31, 1 <= k <= 8)")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=signs.device)
+    idx = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    score = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    with torch.cuda.device(signs.device):
+        N.check(lib.gsw_trace_keyed_topk(signs.data_ptr(), B, n_bits, records.data_ptr(), stride, msg_bytes, U, k,
+                                         idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))
+    return idx, score
+
+
 # ------------------------------------------------------------------------------------------------ X2 / G1 elementwise
 def ddim_step(x: torch.Tensor, model_out: torch.Tensor, a: float, b: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = a*x + b*model_out (fp32 math, one rounding). out may be x (in place)."""

@@ -44,62 +44,7 @@ struct GswMsgInline {
     uint8_t b[GSW_MSG_INLINE_MAX];
 };
 
-// ------------------------------------------------------------------------------------------------
-// ChaCha20, four lanes per 64-byte block.
-// Lane q of a quad holds column q of the 4x4 state (a = row0[q], b = row1[q], c = row2[q], d = row3[q]).
-// The column round is lane-local; for the diagonal round rows 1..3 are rotated by 1..3 lanes inside the
-// quad with DPP quad_perm (no LDS, no extra latency beyond a VALU move), then rotated back.
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t rotl32(uint32_t x, int n) { return __builtin_rotateleft32(x, n); }
-
-template <int CTRL>
-__device__ __forceinline__ uint32_t quad_perm(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
-}
-// quad_perm selectors: lane i reads lane sel[i]
-#define QP_ROT1 0x39  // [1,2,3,0]
-#define QP_ROT2 0x4E  // [2,3,0,1]
-#define QP_ROT3 0x93  // [3,0,1,2]
-
-#define CHACHA_QR(a, b, c, d) \
-    a += b; d = rotl32(d ^ a, 16); \
-    c += d; b = rotl32(b ^ c, 12); \
-    a += b; d = rotl32(d ^ a, 8);  \
-    c += d; b = rotl32(b ^ c, 7);
-
-// Computes ChaCha20 blocks [first_block, first_block + nblocks) into ks_words[nblocks*16] (LDS), using every lane
-// of the workgroup in quads.  All lanes of a participating quad are active together (4 | blockDim, tid-contiguous).
-// The cipher words are taken BY VALUE (SGPRs): handing the by-value kernel-argument struct around by reference
-// makes clang materialise it in scratch.
-struct CipherRegs {
-    uint32_t k0, k1, k2, k3, k4, k5, k6, k7, n0, n1, n2, n3;
-};
-#define GSW_CIPHER_REGS(ck) CipherRegs{(ck).key[0], (ck).key[1], (ck).key[2], (ck).key[3], (ck).key[4], (ck).key[5], \
-                                       (ck).key[6], (ck).key[7], (ck).nonce[0], (ck).nonce[1], (ck).nonce[2], (ck).nonce[3]}
-
-__device__ __forceinline__ void chacha20_blocks_to_lds(const CipherRegs ck, uint64_t first_block, uint32_t nblocks,
-                                                       uint32_t* ks_words) {
-    const uint32_t tid = threadIdx.x;
-    const uint32_t col = tid & 3u;
-    const uint32_t a0 = col == 0 ? 0x61707865u : col == 1 ? 0x3320646eu : col == 2 ? 0x79622d32u : 0x6b206574u;
-    const uint32_t b0 = col == 0 ? ck.k0 : col == 1 ? ck.k1 : col == 2 ? ck.k2 : ck.k3;
-    const uint32_t c0 = col == 0 ? ck.k4 : col == 1 ? ck.k5 : col == 2 ? ck.k6 : ck.k7;
-    const uint64_t ctr_base = ((uint64_t)ck.n1 << 32) | ck.n0;
-    for (uint32_t blk = tid >> 2; blk < nblocks; blk += blockDim.x >> 2) {
-        const uint64_t ctr = ctr_base + first_block + (uint64_t)blk;
-        const uint32_t d0 = col == 0 ? (uint32_t)ctr : col == 1 ? (uint32_t)(ctr >> 32) : col == 2 ? ck.n2 : ck.n3;
-        uint32_t a = a0, b = b0, c = c0, d = d0;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            CHACHA_QR(a, b, c, d)
-            b = quad_perm<QP_ROT1>(b); c = quad_perm<QP_ROT2>(c); d = quad_perm<QP_ROT3>(d);
-            CHACHA_QR(a, b, c, d)
-            b = quad_perm<QP_ROT3>(b); c = quad_perm<QP_ROT2>(c); d = quad_perm<QP_ROT1>(d);
-        }
-        uint32_t* o = ks_words + blk * 16 + col;
-        o[0] = a + a0; o[4] = b + b0; o[8] = c + c0; o[12] = d + d0;
-    }
-}
+#include "gswm_chacha.h"   // ChaCha20, four lanes per 64-byte block: CipherRegs, chacha20_blocks_to_lds
 
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-R (in-kernel uniform source; NOT reference behaviour -- the reference draws from numpy's
@@ -931,6 +876,26 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_generic_kernel(ExtractArgs
     }
 }
 
+// X3 alone: the cipher bytes of the quantised signs (no decryption, no vote), the operand of the keyed registry search (gswm_keyed.hip).
+// One thread per byte; the flags of an image are OR-ed into flags_out[b], which the caller zeroes.
+template <typename Src>
+__global__ __launch_bounds__(GSW_WG) void gsw_sign_pack_kernel(Src src, Thr thr, uint8_t* __restrict__ signs, uint32_t* __restrict__ flags_out,
+                                                               uint32_t nbytes, int B) {
+    const uint32_t j = blockIdx.x * GSW_WG + threadIdx.x;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        uint32_t flags = 0;
+        if (j < nbytes) {
+            const size_t byte = (size_t)b * nbytes + j;
+            signs[byte] = (uint8_t)src.byte8(byte << 3, thr, flags);
+        }
+        if (__any(flags != 0)) {
+            uint32_t f = flags;
+            for (int s = 32; s > 0; s >>= 1) f |= __shfl_xor(f, s, 64);
+            if ((threadIdx.x & 63u) == 0) atomicOr(&flags_out[b], f);
+        }
+    }
+}
+
 // X6: matches between recovered bits and the reference message over the first nb bits
 __global__ __launch_bounds__(64) void gsw_bit_matches_kernel(const uint8_t* __restrict__ bits, uint32_t row_bytes,
                                                             const uint8_t* __restrict__ ref, uint32_t nb, uint32_t* __restrict__ matches, int B) {
@@ -1442,6 +1407,30 @@ int gsw_extract(const void* z_dev, int z_dtype, const uint8_t key[32], const uin
         case GSW_BF16: return launch_extract(a, SrcPlain<__hip_bfloat16>{(const __hip_bfloat16*)z_dev}, st);
         case GSW_F64: return launch_extract(a, SrcPlain<double>{(const double*)z_dev}, st);
         default: return GSW_ERR_BAD_ARG;
+    }
+}
+
+template <typename Src>
+static int launch_sign_pack(const Src& src, int dtype, uint8_t* signs_dev, uint32_t* flags_dev, int B, uint32_t nbytes, hipStream_t st) {
+    GSW_HIP(hipMemsetAsync(flags_dev, 0, (size_t)B * sizeof(uint32_t), st));
+    const dim3 grid((nbytes + GSW_WG - 1) / GSW_WG, (uint32_t)std::min(B, 65535));
+    hipLaunchKernelGGL((gsw_sign_pack_kernel<Src>), grid, dim3(GSW_WG), 0, st, src, make_thr(dtype), signs_dev, flags_dev, nbytes, B);
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
+int gsw_sign_pack(const void* z_dev, int z_dtype, uint8_t* signs_dev, uint32_t* flags_dev, int B, int64_t n_elems, void* stream) {
+    if (!z_dev || !signs_dev || !flags_dev || B < 0 || n_elems < 1) return GSW_ERR_BAD_ARG;
+    if (z_dtype != GSW_F32 && z_dtype != GSW_F16 && z_dtype != GSW_BF16 && z_dtype != GSW_F64) return GSW_ERR_BAD_ARG;
+    if ((n_elems & 7) || n_elems > (int64_t)0x7FFFFFF0) return GSW_ERR_UNSUPPORTED;
+    if (B == 0) return GSW_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nbytes = (uint32_t)(n_elems / 8);
+    switch (z_dtype) {
+        case GSW_F32: return launch_sign_pack(SrcPlain<float>{(const float*)z_dev}, z_dtype, signs_dev, flags_dev, B, nbytes, st);
+        case GSW_F16: return launch_sign_pack(SrcPlain<__half>{(const __half*)z_dev}, z_dtype, signs_dev, flags_dev, B, nbytes, st);
+        case GSW_BF16: return launch_sign_pack(SrcPlain<__hip_bfloat16>{(const __hip_bfloat16*)z_dev}, z_dtype, signs_dev, flags_dev, B, nbytes, st);
+        default: return launch_sign_pack(SrcPlain<double>{(const double*)z_dev}, z_dtype, signs_dev, flags_dev, B, nbytes, st);
     }
 }
 

@@ -41,6 +41,7 @@
 #include <cstdint>
 
 #include "../../include/gswm.h"
+#include "gswm_topk.h"   // TR_LIST, TR_EMPTY, make_key, list_insert, merge_from_lane_xor
 
 extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip; read by gsw_last_hip_error()
 
@@ -54,8 +55,6 @@ constexpr int TR_WG = 256;               // 4 waves
 constexpr int TR_UT = 4;                 // user tiles (of 16) per wave and pass
 constexpr int TR_PASS_USERS = 4 * TR_UT * 16;   // users a workgroup covers per pass
 constexpr int TR_MAX_GRID_X = 512;       // user ranges (two workgroups per CU)
-constexpr int TR_LIST = 8;               // entries of a running list (k <= 8)
-constexpr int64_t TR_EMPTY = INT64_MIN;  // score INT32_MIN, index -1
 constexpr uint32_t TR_MAX_LDS = 160u * 1024u - 64u;
 
 struct TraceArgs {
@@ -79,33 +78,6 @@ __device__ __forceinline__ int weight_of(uint32_t c, int V, int hard) {
     const int ci = (int)min(c, (uint32_t)V);
     if (hard) return (2 * ci > V) ? 1 : -1;          // strict majority, ties -> 0 (extract.py:99)
     return 2 * ci - V;
-}
-
-// keep the 8 largest keys, L[0] the largest
-__device__ __forceinline__ void list_insert(int64_t (&L)[TR_LIST], int64_t key) {
-    if (key > L[TR_LIST - 1]) {
-        L[TR_LIST - 1] = key;
-#pragma unroll
-        for (int j = TR_LIST - 1; j > 0; --j) {
-            const int64_t a = L[j - 1], b = L[j];
-            const bool sw = b > a;
-            L[j - 1] = sw ? b : a;
-            L[j] = sw ? a : b;
-        }
-    }
-}
-
-__device__ __forceinline__ int64_t make_key(int r1, int64_t u) {
-    return (int64_t)(((uint64_t)(uint32_t)r1 << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)u));
-}
-
-// fold the list of lane ^ step into this lane's (both lanes end with the same list)
-__device__ __forceinline__ void merge_from_lane_xor(int64_t (&L)[TR_LIST], int step) {
-    int64_t other[TR_LIST];
-#pragma unroll
-    for (int j = 0; j < TR_LIST; ++j) other[j] = __shfl_xor((long long)L[j], step);
-#pragma unroll
-    for (int j = 0; j < TR_LIST; ++j) list_insert(L, other[j]);
 }
 
 __device__ __forceinline__ uint2 load_row_qword(const TraceArgs& a, int64_t u, int byte0) {

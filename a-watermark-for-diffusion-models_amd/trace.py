@@ -19,7 +19,15 @@ Null model (the paper's): for an image that carries no watermark under this key 
 Both tails are summed as Python integers and converted to a double once, at the end.  Over a registry of U users the reported value is
 the Bonferroni bound min(0, log10 p + log10 U); an image is attributed iff that is <= log10(fpr).
 
-Single key: every candidate shares one ChaCha20 key / nonce.  Per-user keys (one keystream per candidate) are out of scope.
+Single key (`Registry`, `trace_latents`): every candidate shares one ChaCha20 key / nonce.
+
+Per-record keys (`KeyedRegistry`, `trace_latents_keyed`, `--per_record_keys`): what gs_insert logs when key and nonce are left blank --
+a fresh random key and nonce per run, so the log is a list of (key, nonce, message) triples.  Decrypting the image under a record's
+key and comparing with its message is the same as comparing the image's quantised sign bits h with the record's codeword
+e = keystream(key, nonce) XOR (message repeated), the cipher bits the embed plants: s = n - 2 popcount(h XOR e).  The image is
+quantised and packed once (`codec.sign_pack`) and one launch (`codec.trace_keyed_topk`) generates every record's keystream in
+registers.  For records that share one key s IS the soft score above; under the null model s = 2 X - n, X ~ Bin(n, 1/2) exactly for
+any fixed record and any key, so `log10_p_soft` and the Bonferroni bound carry over.  Only the soft statistic exists across keys.
 """
 from __future__ import annotations
 
@@ -134,7 +142,36 @@ def topk_host(counts, copies: int, registry_bits, k: int, soft: bool = True):
     return idx, out
 
 
+def keyed_topk_host(signs, codewords, k: int):
+    """NumPy restatement of `codec.trace_keyed_topk` that takes the codewords as an argument (int64 arithmetic, a stable sort):
+    signs uint8 [B, n/8], codewords uint8 [U, n/8] (the packed cipher bits of each record, e.g. np.packbits of the oracle's
+    `cipher_bits`) -> (idx int32 [B, k], score int32 [B, k]), score = n - 2 popcount(signs ^ codeword).  Shares no code with the device path."""
+    h = np.asarray(signs, dtype=np.uint8)
+    e = np.asarray(codewords, dtype=np.uint8)
+    if h.ndim != 2 or e.ndim != 2 or h.shape[1] != e.shape[1]:
+        raise ValueError("sign rows and codewords disagree on the lattice size")
+    B, U, n = h.shape[0], e.shape[0], 8 * h.shape[1]
+    hb = np.unpackbits(h, axis=1).astype(np.int64)
+    scores = np.empty((B, U), dtype=np.int64)
+    step = max(1, (1 << 24) // max(n, 1))
+    for u0 in range(0, U, step):
+        eb = np.unpackbits(e[u0:u0 + step], axis=1).astype(np.int64)
+        scores[:, u0:u0 + step] = (2 * hb - 1) @ (2 * eb - 1).T              # agreeing bits minus differing bits = n - 2 popcount(h ^ e)
+    idx = np.full((B, k), -1, dtype=np.int32)
+    out = np.full((B, k), INT32_MIN, dtype=np.int32)
+    order = np.argsort(-scores, axis=1, kind="stable")[:, :k]
+    m = order.shape[1]
+    idx[:, :m] = order
+    out[:, :m] = np.take_along_axis(scores, order, axis=1)
+    return idx, out
+
+
 # ===================================================================================================================== registry
+def _check_user_id(user_id) -> None:
+    if not isinstance(user_id, str) or not user_id or any(ch in user_id for ch in "\t\r\n"):
+        raise ValueError(f"user id {user_id!r} must be a non-empty string without tabs or line breaks")
+
+
 def _as_bytes(x, what: str) -> Optional[bytes]:
     if x is None:
         return None
@@ -182,8 +219,7 @@ class Registry:
     def add(self, user_id: str, message: Union[str, bytes]) -> int:
         """Register `message` for `user_id`; returns the row index.  A str is what gs_insert would embed for it
         (`codec.pad_message`: UTF-8, zero-padded or cut to message_bytes); bytes must have the registry's length."""
-        if not isinstance(user_id, str) or not user_id or any(ch in user_id for ch in "\t\r\n"):
-            raise ValueError(f"user id {user_id!r} must be a non-empty string without tabs or line breaks")
+        _check_user_id(user_id)
         if isinstance(message, str):
             if not message:
                 raise ValueError(f"user {user_id!r}: an empty message string cannot be registered (pad_message would draw random bytes)")
@@ -220,8 +256,8 @@ class Registry:
                 if not line:
                     continue
                 uid, sep, hx = line.partition("\t")
-                if not sep:
-                    raise ValueError(f"{path}:{no}: expected 'user_id<TAB>message_hex'")
+                if not sep or "\t" in hx:                # (bytes.fromhex skips tabs: a keyed registry would load as one long message)
+                    raise ValueError(f"{path}:{no}: expected 'user_id<TAB>message_hex'" + (" (a registry with per-record keys? see KeyedRegistry)" if sep else ""))
                 try:
                     msg = bytes.fromhex(hx.strip())
                 except ValueError:
@@ -239,25 +275,14 @@ class Registry:
         `Time: / key: / nonce: / message: / ------` lines -- read as a registry: the records of the given key and nonce (bytes or hex;
         None keeps any), repeated messages dropped, ids `info:<record number>` (1-based over ALL records of the file)."""
         key, nonce = _as_bytes(key, "key"), _as_bytes(nonce, "nonce")
-        reg, rec, number = None, {}, 0
-        with open(path) as f:
-            for line in f:
-                line = line.strip()
-                if line.startswith("-----"):
-                    if "message" in rec:
-                        number += 1
-                        ok = (key is None or rec.get("key") == key.hex()) and (nonce is None or rec.get("nonce") == nonce.hex())
-                        if ok:
-                            msg = bytes.fromhex(rec["message"])
-                            if reg is None:
-                                reg = cls(len(msg))
-                            if msg not in reg._by_message:
-                                reg.add(f"info:{number}", msg)
-                    rec = {}
-                    continue
-                name, sep, value = line.partition(":")
-                if sep and name in ("key", "nonce", "message"):
-                    rec[name] = value.strip().lower()
+        reg = None
+        for number, rec_key, rec_nonce, message in _info_data_records(path):
+            if (key is None or rec_key == key.hex()) and (nonce is None or rec_nonce == nonce.hex()):
+                msg = bytes.fromhex(message)
+                if reg is None:
+                    reg = cls(len(msg))
+                if msg not in reg._by_message:
+                    reg.add(f"info:{number}", msg)
         if reg is None:
             raise ValueError(f"{path}: no record matches the given key / nonce")
         return reg
@@ -293,12 +318,186 @@ class Registry:
 
 
 def detect_format(path) -> str:
-    """'info_data' when the first non-empty line is a `Time:` line of gs_insert's log, else 'registry'"""
+    """'info_data' when the first non-empty line is a `Time:` line of gs_insert's log, 'keyed_registry' when it has the four columns
+    `KeyedRegistry.save` writes, else 'registry'"""
     with open(path) as f:
         for line in f:
             if line.strip():
-                return "info_data" if line.startswith("Time:") and "\t" not in line else "registry"
+                if line.startswith("Time:") and "\t" not in line:
+                    return "info_data"
+                return "keyed_registry" if line.rstrip("\r\n").count("\t") == 3 else "registry"
     raise ValueError(f"{path} is empty")
+
+
+def _info_data_records(path):
+    """(record number, key_hex, nonce_hex, message_hex) of every record of a gs_insert log that has a message, numbered from 1"""
+    rec, number = {}, 0
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if line.startswith("-----"):
+                if "message" in rec:
+                    number += 1
+                    yield number, rec.get("key"), rec.get("nonce"), rec["message"]
+                rec = {}
+                continue
+            name, sep, value = line.partition(":")
+            if sep and name in ("key", "nonce", "message"):
+                rec[name] = value.strip().lower()
+
+
+class KeyedRegistry:
+    """Ordered user_id -> (key, nonce, message) records, each with its own ChaCha20 key and nonce: unique ids, unique triples, all
+    messages of one length (`message_bytes`, default 32 = what gs_insert embeds)."""
+
+    def __init__(self, message_bytes: int = 32):
+        if not 1 <= int(message_bytes) <= 256:
+            raise ValueError("message_bytes must be in 1..256")
+        self.message_bytes = int(message_bytes)
+        self._ids: List[str] = []
+        self._records: List[Tuple[bytes, bytes, bytes]] = []
+        self._by_id: Dict[str, int] = {}
+        self._by_record: Dict[Tuple[bytes, bytes, bytes], int] = {}
+        self._device_cache = {}
+
+    # -- content
+    def __len__(self) -> int:
+        return len(self._ids)
+
+    @property
+    def message_bits(self) -> int:
+        return 8 * self.message_bytes
+
+    @property
+    def user_ids(self) -> List[str]:
+        return list(self._ids)
+
+    @property
+    def n_keys(self) -> int:
+        """distinct (key, nonce) pairs"""
+        return len({(k, n) for k, n, _ in self._records})
+
+    def record(self, user_id: str) -> Tuple[bytes, bytes, bytes]:
+        return self._records[self._by_id[user_id]]
+
+    def user_at(self, index: int) -> str:
+        return self._ids[index]
+
+    def record_at(self, index: int) -> Tuple[bytes, bytes, bytes]:
+        return self._records[index]
+
+    def add(self, user_id: str, key: Union[str, bytes], nonce: Union[str, bytes], message: Union[str, bytes]) -> int:
+        """Register (key, nonce, message) for `user_id`; returns the row index.  key (32 bytes) and nonce (16 bytes) are bytes or hex
+        strings; a str message is what gs_insert would embed for it (`codec.pad_message`), bytes must have the registry's length."""
+        _check_user_id(user_id)
+        try:
+            key, nonce = _as_bytes(key, "key"), _as_bytes(nonce, "nonce")
+        except ValueError:
+            raise ValueError(f"user {user_id!r}: key and nonce must be hexadecimal") from None
+        if key is None or len(key) != 32:
+            raise ValueError(f"user {user_id!r}: the ChaCha20 key must be 32 bytes")
+        if nonce is None or len(nonce) != 16:
+            raise ValueError(f"user {user_id!r}: the ChaCha20 nonce must be 16 bytes")
+        if isinstance(message, str):
+            if not message:
+                raise ValueError(f"user {user_id!r}: an empty message string cannot be registered (pad_message would draw random bytes)")
+            msg = codec.pad_message(message, self.message_bytes)
+        elif isinstance(message, (bytes, bytearray)):
+            msg = bytes(message)
+            if len(msg) != self.message_bytes:
+                raise ValueError(f"user {user_id!r}: message has {len(msg)} bytes, the registry holds {self.message_bytes}-byte messages")
+        else:
+            raise TypeError(f"user {user_id!r}: message must be str or bytes")
+        if user_id in self._by_id:
+            raise ValueError(f"user id {user_id!r} is already registered")
+        rec = (key, nonce, msg)
+        if rec in self._by_record:
+            raise ValueError(f"user {user_id!r}: this key, nonce and message {msg.hex()} are already registered to {self._ids[self._by_record[rec]]!r}")
+        self._by_id[user_id] = self._by_record[rec] = len(self._ids)
+        self._ids.append(user_id)
+        self._records.append(rec)
+        self._device_cache.clear()
+        return len(self._ids) - 1
+
+    # -- files
+    def save(self, path) -> None:
+        """one `user_id<TAB>key_hex<TAB>nonce_hex<TAB>message_hex` per line"""
+        with open(path, "w") as f:
+            for uid, (key, nonce, msg) in zip(self._ids, self._records):
+                f.write(f"{uid}\t{key.hex()}\t{nonce.hex()}\t{msg.hex()}\n")
+
+    @classmethod
+    def load(cls, path) -> "KeyedRegistry":
+        reg = None
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                line = line.rstrip("\r\n")
+                if not line:
+                    continue
+                cols = line.split("\t")
+                if len(cols) != 4:
+                    raise ValueError(f"{path}:{no}: expected 'user_id<TAB>key_hex<TAB>nonce_hex<TAB>message_hex'")
+                try:
+                    key, nonce, msg = (bytes.fromhex(c.strip()) for c in cols[1:])
+                except ValueError:
+                    raise ValueError(f"{path}:{no}: record of user {cols[0]!r} is not hexadecimal") from None
+                if reg is None:
+                    reg = cls(len(msg))
+                reg.add(cols[0], key, nonce, msg)
+        if reg is None:
+            raise ValueError(f"{path}: no registry entries")
+        return reg
+
+    @classmethod
+    def from_info_data(cls, path) -> "KeyedRegistry":
+        """EVERY record of the log gs_insert appends per issued watermark, each under its own key and nonce; ids `info:<record number>`
+        (numbered as `Registry.from_info_data` numbers them), repeated (key, nonce, message) triples dropped."""
+        reg = None
+        for number, key, nonce, message in _info_data_records(path):
+            if key is None or nonce is None:
+                raise ValueError(f"{path}: record {number} has no key / nonce")
+            rec = (bytes.fromhex(key), bytes.fromhex(nonce), bytes.fromhex(message))
+            if reg is None:
+                reg = cls(len(rec[2]))
+            if rec not in reg._by_record:
+                reg.add(f"info:{number}", *rec)
+        if reg is None:
+            raise ValueError(f"{path}: no records")
+        return reg
+
+    @classmethod
+    def from_file(cls, path) -> "KeyedRegistry":
+        """gs_insert's log or the four-column format, told apart by the first line"""
+        fmt = detect_format(path)
+        if fmt == "registry":
+            raise ValueError(f"{path}: 'user_id<TAB>message_hex' lines carry no keys: this is a single-key registry (trace without --per_record_keys)")
+        return cls.from_info_data(path) if fmt == "info_data" else cls.load(path)
+
+    # -- device
+    @property
+    def record_stride(self) -> int:
+        return codec.keyed_record_stride(self.message_bytes)
+
+    def packed(self) -> np.ndarray:
+        """uint8 [U, record_stride]: a row is key[32] | nonce[16] | message, zero-padded to a multiple of 16 bytes
+        (the record rows of `codec.trace_keyed_topk`)"""
+        if not self._ids:
+            raise ValueError("the registry is empty")
+        t = self._device_cache.get("host")
+        if t is None:
+            t = np.zeros((len(self._ids), self.record_stride), dtype=np.uint8)
+            flat = np.frombuffer(b"".join(k + n + m for k, n, m in self._records), dtype=np.uint8)
+            t[:, :48 + self.message_bytes] = flat.reshape(len(self._ids), 48 + self.message_bytes)
+            self._device_cache["host"] = t
+        return t
+
+    def to_device(self, device="cuda"):
+        import torch
+        k = str(torch.device(device))
+        t = self._device_cache.get(k)
+        if t is None:
+            t = self._device_cache[k] = torch.from_numpy(self.packed()).to(device)
+        return t
 
 
 # ===================================================================================================================== tracing
@@ -361,6 +560,62 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
     return out
 
 
+def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: float = 1e-6) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents` against a registry whose records carry their own keys: latents [B, ...] on the device -> one TraceResult per
+    image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
+
+    One quantise-and-pack kernel, one search launch over the record rows (every record's keystream is generated inside it); the host
+    receives the B k (index, score) pairs and the flags.  score = n - 2 popcount(signs ^ codeword), whose null distribution is that of
+    the soft score (`log10_p_soft(score, n)`), Bonferroni over the records.  `Candidate.agree` is the reference's voted-bit agreement
+    under that candidate's own key: `codec.extract_batch` + `codec.bit_matches` for the reported candidates only, grouped by key."""
+    import torch
+    from . import _native as N
+    if not 0.0 < float(fpr) <= 1.0:
+        raise ValueError("fpr must be in (0, 1]")
+    z = latents.contiguous()
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    M = registry.message_bits
+    codec.vote_copies(n, M)                              # (a lattice the messages do not tile fails here, as extract_batch would)
+    rec_dev = registry.to_device(z.device)
+    signs, flags = codec.sign_pack(z)
+    idx, score = codec.trace_keyed_topk(signs, n, rec_dev, registry.message_bytes, k=k)
+    pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy
+    idx_h, score_h = pairs[0], pairs[1]
+    flags_h = flags.cpu().numpy()
+    U, limit = len(registry), math.log10(float(fpr))
+    out: List[Union[TraceResult, ValueError]] = []
+    reported: Dict[Tuple[bytes, bytes], Dict[bytes, List[Tuple[int, Candidate]]]] = {}      # (key, nonce) -> message -> (image, candidate)
+    for b in range(B):
+        if flags_h[b] & N.GSW_FLAG_NAN:
+            out.append(ValueError("cannot convert float NaN to integer"))
+            continue
+        if flags_h[b] & N.GSW_FLAG_SATURATED:
+            out.append(ValueError("invalid literal for int() with base 2"))
+            continue
+        res = TraceResult()
+        for j in range(k):
+            i, s = int(idx_h[b, j]), int(score_h[b, j])
+            if i < 0:
+                break
+            c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(log10_p_soft(s, n), U))
+            key, nonce, msg = registry.record_at(i)
+            reported.setdefault((key, nonce), {}).setdefault(msg, []).append((b, c))
+            res.candidates.append(c)
+        if res.candidates and res.candidates[0].log10_p_any <= limit:
+            res.attributed = res.candidates[0].user_id
+        out.append(res)
+    for (key, nonce), by_message in reported.items():
+        images = sorted({b for pairs_ in by_message.values() for b, _ in pairs_})
+        row = {b: r for r, b in enumerate(images)}
+        bits, _ = codec.extract_batch(z[torch.tensor(images, device=z.device)].contiguous(), key, nonce, M)
+        for msg, pairs_ in by_message.items():
+            agree = codec.bit_matches(bits, M, msg).cpu().numpy()
+            for b, c in pairs_:
+                c.agree = int(agree[row[b]])
+    return out
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result, message_length: int) -> str:
     """One line of trace.txt / stdout"""
@@ -377,16 +632,34 @@ def format_line(name: str, result, message_length: int) -> str:
 
 def build_parser():
     import argparse
-    p = argparse.ArgumentParser(prog="python -m gswm_amd.trace",
-                                description="Trace images to the registered user whose watermark they carry (single GPU, one key for all users; "
-                                            "sharding over --gpus and per-user keys are out of scope of this tool)")
+
+    class Parser(argparse.ArgumentParser):
+        def parse_args(self, args=None, namespace=None):
+            a = super().parse_args(args, namespace)
+            if a.per_record_keys:
+                if a.hard:
+                    self.error("--hard cannot be combined with --per_record_keys: only the soft statistic exists across keys")
+                if a.key_hex is not None or a.nonce_hex is not None:
+                    self.error("--per_record_keys takes every key and nonce from the registry: drop --key_hex / --nonce_hex")
+            elif a.key_hex is None or a.nonce_hex is None:
+                self.error("the following arguments are required: --key_hex, --nonce_hex (or --per_record_keys with a registry that carries them)")
+            return a
+
+    p = Parser(prog="python -m gswm_amd.trace",
+               description="Trace images to the registered user whose watermark they carry (single GPU; one key for all users, or per-user keys "
+                           "with --per_record_keys: the log gs_insert writes when key and nonce are left blank; sharding over --gpus is out of "
+                           "scope of this tool)")
     p.add_argument("--model_id", default="stabilityai/stable-diffusion-2-1-base")
     p.add_argument("--images_directory_path", default="", help="The path of directory containing images to process")
     p.add_argument("--single_image_path", default="")
-    p.add_argument("--key_hex", required=True, help="Hexadecimal key used for encryption")
-    p.add_argument("--nonce_hex", required=True, help="Hexadecimal nonce used for encryption, It will use the fixed part of the key if nonce is none")
+    p.add_argument("--key_hex", default=None, help="Hexadecimal key used for encryption (required unless --per_record_keys)")
+    p.add_argument("--nonce_hex", default=None, help="Hexadecimal nonce used for encryption, It will use the fixed part of the key if nonce is none "
+                                                     "(required unless --per_record_keys)")
     p.add_argument("--registry", required=True, help="registry file: 'user_id<TAB>message_hex' lines, or the info_data.txt log gs_insert appends "
                                                       "(told apart by the first line; of a log, the records of this key / nonce are used)")
+    p.add_argument("--per_record_keys", action="store_true",
+                   help="every record of --registry carries its own key and nonce: ALL records of an info_data.txt log, or "
+                        "'user_id<TAB>key_hex<TAB>nonce_hex<TAB>message_hex' lines (soft statistic only)")
     p.add_argument("--fpr", type=float, default=1e-6, help="false-positive rate per image, over the whole registry (Bonferroni)")
     p.add_argument("--top", type=int, default=1, choices=range(1, 9), metavar="K", help="candidates reported per image (1..8)")
     p.add_argument("--hard", action="store_true", help="rank by the majority-voted bits instead of the vote margins")
@@ -404,7 +677,7 @@ def build_parser():
     return p
 
 
-def _trace_files(files: Sequence[str], args, registry: Registry) -> list:
+def _trace_files(files: Sequence[str], args, registry) -> list:
     """files -> outcomes in order (TraceResult or the exception that file raised): decode on host threads, invert and trace in device
     batches; a batch that raises is redone image by image so that each reports its own error (extract._recover_items does the same)."""
     from concurrent.futures import ThreadPoolExecutor
@@ -418,6 +691,8 @@ def _trace_files(files: Sequence[str], args, registry: Registry) -> list:
 
     def run(arrs):
         latents = X.invert_decoded_images(arrs, args)
+        if args.per_record_keys:
+            return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr)
         return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard)
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
@@ -440,14 +715,16 @@ def _trace_files(files: Sequence[str], args, registry: Registry) -> list:
     return out
 
 
-def _report(job, outcomes, args, registry: Registry, synthetic: bool) -> None:
+def _report(job, outcomes, args, registry, synthetic: bool) -> None:
     from . import extract as X
     from datetime import datetime
     M = args.message_length
     with open(os.path.join(job.path, "trace.txt"), "a") as out:
         bar = "=" * 40
-        fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("key_hex", args.key_hex), ("nonce_hex", args.nonce_hex), ("registry", args.registry),
-                  ("users", len(registry)), ("message_length", M), ("statistic", "hard" if args.hard else "soft"), ("fpr", args.fpr),
+        keyed = [("keys", registry.n_keys)] if args.per_record_keys else []
+        fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("key_hex", "per record" if keyed else args.key_hex),
+                  ("nonce_hex", "per record" if keyed else args.nonce_hex), ("registry", args.registry),
+                  ("users", len(registry)), *keyed, ("message_length", M), ("statistic", "hard" if args.hard else "soft"), ("fpr", args.fpr),
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
@@ -462,12 +739,19 @@ def _report(job, outcomes, args, registry: Registry, synthetic: bool) -> None:
 def main(argv=None):
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     from . import extract as X
-    args.key = bytes.fromhex(args.key_hex)
-    args.nonce = bytes.fromhex(args.nonce_hex) if args.nonce_hex != "" else bytes.fromhex(args.key_hex[16:48])
-    registry = Registry.from_file(args.registry, args.key, args.nonce)
-    if args.message_length is None:
+    if args.per_record_keys:
+        registry = KeyedRegistry.from_file(args.registry)
+        if args.message_length not in (None, registry.message_bits):
+            raise ValueError(f"--message_length {args.message_length}: with --per_record_keys the length is the registry's own ({registry.message_bits})")
         args.message_length = registry.message_bits
-    registry.packed(args.message_length)                 # a message_length the registry cannot be tiled to fails here, before any model loads
+        registry.packed()
+    else:
+        args.key = bytes.fromhex(args.key_hex)
+        args.nonce = bytes.fromhex(args.nonce_hex) if args.nonce_hex != "" else bytes.fromhex(args.key_hex[16:48])
+        registry = Registry.from_file(args.registry, args.key, args.nonce)
+        if args.message_length is None:
+            args.message_length = registry.message_bits
+        registry.packed(args.message_length)             # a message_length the registry cannot be tiled to fails here, before any model loads
     synthetic = X._no_checkpoint(args.model_id)
     with X._strictness(args, synthetic):
         if args.images_directory_path != "":

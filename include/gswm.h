@@ -506,6 +506,31 @@ size_t gsw_trace_workspace_bytes(int B, int64_t n_users, int k);
 int gsw_trace_topk(const uint32_t* counts_dev, int B, int msg_bits, int copies, int mode, const uint8_t* registry_dev, int64_t n_users, int k,
                    int32_t* idx_dev, int32_t* score_dev, void* workspace_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Tracing against a registry whose records carry their own ChaCha20 key and nonce (what gs_insert logs when key and nonce are
+ * left blank).  Additive: gsw_version() stays 500.
+ *
+ * X3 alone: y = int(norm.cdf(float64(z)) * 2) per element, packed MSB first (bit i -> byte i >> 3, bit 7 - (i & 7)); the quantiser and the
+ * flags are gsw_extract's own (same thresholds, same GSW_FLAG_*; a saturated element packs as 1, a NaN as 0).  signs_dev [B, n_elems / 8].
+ * n_elems % 8 != 0 (or n_elems > 0x7FFFFFF0) -> GSW_ERR_UNSUPPORTED; null pointer, unknown dtype, B < 0, n_elems < 1 -> GSW_ERR_BAD_ARG. */
+int gsw_sign_pack(const void* z_dev, int z_dtype, uint8_t* signs_dev, uint32_t* flags_dev, int B, int64_t n_elems, void* stream);
+
+/* records_dev: uint8 [n_records, record_stride], 16-byte aligned; a row is key[32] | nonce16[16] | msg[msg_bytes]; record_stride >= 48 + msg_bytes, % 16 == 0.
+ * codeword of a record = the cipher bits gsw_embed plants for it over n_bits lattice bits (keystream of its key and nonce16, initial counter
+ *                        and carry as gsw_keystream, XOR its message repeated), generated in registers: no codeword is ever stored.
+ * score = n_bits - 2 popcount(signs[b] ^ codeword[u]), an exact int32; for records that share one key and nonce it is gsw_trace_topk's
+ *         GSW_TRACE_SOFT score of the same messages on gsw_extract's counts.
+ * out: the k best records per image by (score descending, index ascending), idx = -1 / score = INT32_MIN past the end -- gsw_trace_topk's
+ *      conventions; workspace_dev: gsw_trace_keyed_workspace_bytes(B, n_records, k) bytes owned by the caller; the result does not depend on
+ *      the launch geometry.
+ * GSW_ERR_BAD_ARG: null pointer, B < 1, k outside 1..8, msg_bytes outside 1..256, n_bits < 1, n_records outside 1..2^31-1, a bad stride or
+ * alignment of records_dev.  GSW_ERR_RAGGED: n_bits is not a multiple of 8 msg_bytes (the reference's vote raises IndexError there).
+ * GSW_ERR_UNSUPPORTED: n_bits > 1 048 576 (one image's sign row is staged in 128 KiB of LDS), B > 65535.
+ * gsw_trace_keyed_workspace_bytes returns 0 for B, n_records, k that gsw_trace_keyed_topk refuses. */
+size_t gsw_trace_keyed_workspace_bytes(int B, int64_t n_records, int k);
+int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
+                         int64_t n_records, int k, int32_t* idx_dev, int32_t* score_dev, void* workspace_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
