@@ -583,6 +583,15 @@ template <> struct Store8<__hip_bfloat16> {
     }
 };
 
+// z = a x + b e of a DDIM update, in fp32 and as ONE value for every kernel that forms it.  The empty asm keeps hipcc from folding the conversion to fp16 into the
+// multiply-add (v_fma_mixlo_f16 rounds the exact sum once; the fp32 sum rounded again differs from that next to a tie), which it did in some inlined copies and
+// not in others: the fused last step (SrcDdim) and gsw_ddim_step then stored different bits for the same operands.
+static __device__ __forceinline__ float ddim_z(float a, float x, float b, float e) {
+    float z = fmaf(b, e, a * x);
+    asm volatile("" : "+v"(z));
+    return z;
+}
+
 template <typename T>
 struct SrcDdim {  // z = round_T(a*x + b*e): the last inversion step fused into the vote
     typedef T elem_t;
@@ -595,7 +604,7 @@ struct SrcDdim {  // z = round_T(a*x + b*e): the last inversion step fused into 
         Load8<T>::ld(x + off, xv);
         Load8<T>::ld(e + off, ev);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) zv[k] = fmaf(b, ev[k], a * xv[k]);
+        for (int k = 0; k < 8; ++k) zv[k] = ddim_z(a, xv[k], b, ev[k]);
         if constexpr (std::is_same<T, float>::value) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) w[k] = __float_as_uint(zv[k]);
@@ -617,12 +626,12 @@ struct SrcDdim {  // z = round_T(a*x + b*e): the last inversion step fused into 
         Load8<T>::ld(x + off, xv);
         Load8<T>::ld(e + off, ev);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) zv[k] = round_to<T>(fmaf(b, ev[k], a * xv[k]));
+        for (int k = 0; k < 8; ++k) zv[k] = round_to<T>(ddim_z(a, xv[k], b, ev[k]));
         if (zout) Store8<T>::st(zout + off, zv);
         return quantise8(zv, t, flags);
     }
     __device__ __forceinline__ uint32_t bit1(size_t off, const Thr& t, uint32_t& flags) const {
-        const float v = round_to<T>(fmaf(b, Load8<T>::ld1(e + off), a * Load8<T>::ld1(x + off)));
+        const float v = round_to<T>(ddim_z(a, Load8<T>::ld1(x + off), b, Load8<T>::ld1(e + off)));
         if (zout) {
             float tmp = v;
             if constexpr (sizeof(T) == 4) reinterpret_cast<float*>(zout)[off] = tmp;
@@ -931,7 +940,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_ddim_step_kernel(const T* __restri
             for (int k = 0; k < 8; ++k) ev[k] = fmaf(g, tv[k] - ev[k], ev[k]);
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) zv[k] = fmaf(b, ev[k], a * xv[k]);
+        for (int k = 0; k < 8; ++k) zv[k] = ddim_z(a, xv[k], b, ev[k]);
         Store8<T>::st(out + (i << 3), zv);
     }
     // tail (< 8 elements)
@@ -939,7 +948,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_ddim_step_kernel(const T* __restri
         for (uint64_t i = (nvec << 3) + threadIdx.x; i < n; i += GSW_WG) {
             float ev = Load8<T>::ld1(e0 + i);
             if (CFG) { const float tv = Load8<T>::ld1(e1 + i); ev = fmaf(g, tv - ev, ev); }
-            const float z = fmaf(b, ev, a * Load8<T>::ld1(x + i));
+            const float z = ddim_z(a, Load8<T>::ld1(x + i), b, ev);
             if constexpr (sizeof(T) == 4) reinterpret_cast<float*>(out)[i] = z;
             else if constexpr (std::is_same<T, __half>::value) out[i] = __float2half_rn(z);
             else out[i] = __float2bfloat16(z);

@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from poison import NAN, Ledger, poisoned
+
 pytestmark = pytest.mark.gpu
 
 
@@ -226,10 +228,11 @@ def test_gn_only_convolution_skips_the_border_and_groupnorm_does_not_care(G, B, 
     y0 = pf.conv_pf(X, Wp, b)
     assert y0.border_valid and y0.stats is not None
     ref = pf.groupnorm_pf(y0, gamma, beta, 32, 1e-5)
-    # poison fresh allocations so that an unwritten border is not accidentally zero
-    junk = torch.full((y0.buf.numel(),), float("nan"), dtype=torch.float16, device="cuda")
-    del junk
-    y1 = pf.conv_pf(X, Wp, b, gn_only=True)
+    # the output comes NaN-filled (tests/poison.py), so that an unwritten border is never accidentally zero
+    ledger = Ledger(NAN)
+    with poisoned(ledger):
+        y1 = pf.conv_pf(X, Wp, b, gn_only=True)
+    ledger.check()                                                    # ... and nothing was stored outside it
     assert y1.stats is not None and not y1.border_valid
     assert torch.equal(y1.interior, y0.interior)
     out = pf.groupnorm_pf(y1, gamma, beta, 32, 1e-5)
