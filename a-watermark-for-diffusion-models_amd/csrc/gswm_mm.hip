@@ -1827,7 +1827,12 @@ int gsw_mm_launch(MMArgs& a, int dtype, void* stream, GswMmExtras* ex) {
         const int64_t t_w = tm_w * tn_w, t_n = (((int64_t)a.M + 255) / 256) * tiles_n;
         const double cost_w = 1.77 * (double)((t_w + cus - 1) / cus), cost_n = (double)((t_n + cus - 1) / cus);
         const bool fits = t_w >= cus && cost_w <= 0.995 * cost_n && a.P >= p_min && a.M >= 2048;
-        wide = legal && (bm_cfg == 512 || (bm_cfg == 0 && wide_env != 0 && fits));
+        // the wide dense-row / GEGLU producer (AFF in the kernel) steps from one 64-row piece to the next by seg[0]'s row stride, pinned in a scalar register for
+        // the whole launch: an A operand in several K segments stays on the narrow tiles there, and a caller that FORCES the wide tile is told so
+        // (a launch the plan split along K has returned above: the split kernels are narrow and segment-aware)
+        const bool aff_multi = epi_k != 1 && a.nseg > 1;
+        if (aff_multi && legal && bm_cfg == 512) return GSW_ERR_UNSUPPORTED;
+        wide = legal && !aff_multi && (bm_cfg == 512 || (bm_cfg == 0 && wide_env != 0 && fits));
     }
     const int BMt = wide ? 256 : BM, BNt = wide ? 320 : BN;
     const int64_t tiles_nt = (a.N + BNt - 1) / BNt;
@@ -1863,13 +1868,18 @@ int gsw_gemm_strided(const void* x_dev, int64_t ldx, const void* w_dev, int64_t 
     return gsw_gemm_ex(x_dev, ldx, w_dev, ldw, bias_dev, resid_dev, ldr, y_dev, ldy, M, K, N, mode, S, Wimg, dtype, nullptr, stream);
 }
 
-int gsw_gemm_ex(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* bias_dev, const void* resid_dev, int64_t ldr, void* y_dev, int64_t ldy,
-                int64_t M, int K, int N, int mode, int S, int Wimg, int dtype, GswMmExtras* ex, void* stream) {
-    if (!x_dev || !w_dev || !y_dev || M <= 0 || K <= 0 || N <= 0) return GSW_ERR_BAD_ARG;
+// The dense entry points: an A operand of one column block (x1_dev == nullptr, K1 == 0) or two ([x0 | x1], W [N][K0 + K1]: segment 1's weights start at column K0)
+static int mm_gemm_dense(const void* x0_dev, int64_t ld0, int K0, const void* x1_dev, int64_t ld1, int K1, const void* w_dev, int64_t ldw, const void* bias_dev,
+                         const void* resid_dev, int64_t ldr, void* y_dev, int64_t ldy, int64_t M, int N, int mode, int S, int Wimg, int dtype, GswMmExtras* ex, void* stream) {
+    const bool two = x1_dev != nullptr;
+    const int64_t K = (int64_t)K0 + K1;
+    if (!x0_dev || !w_dev || !y_dev || M <= 0 || K0 <= 0 || (two && K1 <= 0) || N <= 0) return GSW_ERR_BAD_ARG;
     if (mode != GSW_GEMM_PLAIN && mode != GSW_GEMM_GEGLU && mode != GSW_GEMM_TRANS && mode != GSW_GEMM_TOK2PF) return GSW_ERR_BAD_ARG;
-    if (K % 64 || N % 8 || (mode == GSW_GEMM_GEGLU && N % 160) || M > 0x7FFFFF00 || ldx < K || ldw < K || (ldx & 7) || (ldw & 7) || (ldy & 7) || (ldr & 7)
-        || M * ldx >= ((int64_t)1 << 40) || (int64_t)N * ldw >= ((int64_t)1 << 31) || ldx >= ((int64_t)1 << 31) || ldy >= ((int64_t)1 << 31) || ldr >= ((int64_t)1 << 31))
+    if (two && mode != GSW_GEMM_PLAIN && mode != GSW_GEMM_TOK2PF) return GSW_ERR_UNSUPPORTED;
+    if (K0 % 64 || K1 % 64 || N % 8 || (mode == GSW_GEMM_GEGLU && N % 160) || M > 0x7FFFFF00 || ld0 < K0 || ldw < K || (ld0 & 7) || (ldw & 7) || (ldy & 7) || (ldr & 7)
+        || M * ld0 >= ((int64_t)1 << 40) || (int64_t)N * ldw >= ((int64_t)1 << 31) || ld0 >= ((int64_t)1 << 31) || ldy >= ((int64_t)1 << 31) || ldr >= ((int64_t)1 << 31))
         return GSW_ERR_UNSUPPORTED;
+    if (two && (ld1 < K1 || (ld1 & 7) || M * ld1 >= ((int64_t)1 << 40) || ld1 >= ((int64_t)1 << 31))) return GSW_ERR_UNSUPPORTED;
     if (mode == GSW_GEMM_GEGLU && resid_dev) return GSW_ERR_UNSUPPORTED;
     if ((mode == GSW_GEMM_PLAIN || mode == GSW_GEMM_GEGLU) && ((uintptr_t)bias_dev & 15u)) return GSW_ERR_BAD_ARG;       // fetched by 16-byte LDS-DMA pieces
     if (mode == GSW_GEMM_TRANS && (resid_dev || S <= 0 || (S & 7) || M % S)) return GSW_ERR_UNSUPPORTED;
@@ -1877,8 +1887,10 @@ int gsw_gemm_ex(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, 
     const int64_t ncols = mode == GSW_GEMM_GEGLU ? N / 2 : N;
     if (mode != GSW_GEMM_TRANS && (ldy < ncols || (resid_dev && ldr < ncols))) return GSW_ERR_BAD_ARG;
     MMArgs a;
-    for (int i = 0; i < 3; ++i) a.seg[i] = MMSeg{x_dev, (int32_t)ldx, K / 64, 1, 1, 0, 0, 0};
-    a.nseg = 1; a.P = K / 64;
+    for (int i = 0; i < 3; ++i) a.seg[i] = MMSeg{x0_dev, (int32_t)ld0, K0 / 64, 1, 1, 0, 0, 0};
+    a.nseg = 1;
+    if (two) { a.seg[1] = MMSeg{x1_dev, (int32_t)ld1, K1 / 64, 1, 1, 0, 0, K0}; a.nseg = 2; }
+    a.P = (int32_t)(K / 64);
     a.w = w_dev; a.ldw = (int32_t)ldw;
     a.M = (int32_t)M; a.N = N;
     a.bias = bias_dev; a.rowbias = nullptr; a.resid = resid_dev; a.y = y_dev; a.colstats = nullptr; a.y2 = nullptr; a.n_rows = 0;
@@ -1890,6 +1902,17 @@ int gsw_gemm_ex(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, 
     else if (mode == GSW_GEMM_TRANS) a.mode = MM_MODE_TRANS;
     else if (mode == GSW_GEMM_TOK2PF) { a.mode = MM_MODE_TOK2PF; a.Wp = Wimg + 2; a.Hp = S / Wimg + 2; }
     return gsw_mm_launch(a, dtype, stream, ex);
+}
+
+int gsw_gemm_ex(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* bias_dev, const void* resid_dev, int64_t ldr, void* y_dev, int64_t ldy,
+                int64_t M, int K, int N, int mode, int S, int Wimg, int dtype, GswMmExtras* ex, void* stream) {
+    return mm_gemm_dense(x_dev, ldx, K, nullptr, 0, 0, w_dev, ldw, bias_dev, resid_dev, ldr, y_dev, ldy, M, N, mode, S, Wimg, dtype, ex, stream);
+}
+
+int gsw_gemm2_ex(const void* x0_dev, int64_t ld0, int K0, const void* x1_dev, int64_t ld1, int K1, const void* w_dev, int64_t ldw, const void* bias_dev,
+                 const void* resid_dev, int64_t ldr, void* y_dev, int64_t ldy, int64_t M, int N, int mode, int S, int Wimg, int dtype, GswMmExtras* ex, void* stream) {
+    if (!x1_dev) return GSW_ERR_BAD_ARG;
+    return mm_gemm_dense(x0_dev, ld0, K0, x1_dev, ld1, K1, w_dev, ldw, bias_dev, resid_dev, ldr, y_dev, ldy, M, N, mode, S, Wimg, dtype, ex, stream);
 }
 
 int gsw_gemm_qkv(const void* x_dev, const void* w_dev, const void* bias_dev, void* rows_dev, void* trans_dev, int64_t M, int K, int N_rows, int N,

@@ -57,13 +57,14 @@ MAX_ENTRIES = 8         # captured (shape, dtype, context shape, switches) entri
 
 def _switches():
     """Everything outside the arguments that decides WHICH launches a forward makes: captured graphs are keyed by it."""
-    from . import pf, unet as U, _native as N
+    from . import pf, unet as U, xattn as X, _native as N
     import ctypes as C
     tr, sm = C.c_int(0), C.c_int(0)
     N.lib().gsw_mm_get_config(C.byref(tr), C.byref(sm))
     return (U.FUSED_KERNELS, U.USE_PF, U.UPSAMPLE_SUBPIXEL, U.CACHE_CONTEXT_KV, U.FUSED_QK, U.FUSED_QKV, U.OWN_ATTENTION, U.OWN_GEMM, U.TEMB_TABLE,
             U.CONV_OUT_DIRECT_MAX_PIXELS, U.CFG_SHARED_PREFIX, pf.FUSE_GN_STATS, pf.GN_FUSED_MAX_WGS, pf.GN_FUSED_MAX_PIXELS, pf.FOLD_LN, pf.FOLD_LN_MIN_ROWS, pf.SPLITK_MAX,
-            pf.SPLITK_BYTES, pf.SMALL_GEMM_MAX_ROWS, pf.ATTN_KEY_SPLIT, tr.value, sm.value)
+            pf.SPLITK_BYTES, pf.SMALL_GEMM_MAX_ROWS, pf.ATTN_KEY_SPLIT, U.FOLD_FF_OUT, X.ENABLED, X.PRE_ENABLED, X.GNPROJ_ENABLED,
+            tr.value, sm.value)
 
 
 class _Entry:

@@ -554,6 +554,50 @@ def gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     return y
 
 
+def gemm2(x0: torch.Tensor, x1: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, resid: Optional[torch.Tensor] = None, mode: str = "tok2pf",
+          tokens: int = 0, width: int = 0, out: Optional[torch.Tensor] = None, stats_for: Optional["PF"] = None) -> torch.Tensor:
+    """[x0 | x1] @ w[N, K0 + K1]^T + bias (+ resid) in ONE engine launch (gsw_gemm2_ex): the A operand is two dense tensors with the same rows, walked as two K
+    segments -- what a product of two linear maps folded into one weight needs (unet.Transformer2DModel: proj_out(x + ff.net[2](h))).
+    mode "tok2pf" as pf.gemm's (`out` the `.rows` view of a PF tensor, resid may be `out`, stats_for gets the column records); "plain" -> [..., N] (+ resid)."""
+    if x0.dtype not in (torch.float16, torch.bfloat16):
+        raise ValueError(f"gemm2: fp16 / bf16 only (got {x0.dtype})")
+    if mode not in ("plain", "tok2pf"):
+        raise ValueError(f"gemm2: mode plain | tok2pf (got {mode!r})")
+    _same(x0, x0, "x0")
+    K0, K1 = x0.shape[-1], x1.shape[-1]
+    M = x0.numel() // K0
+    _same(x1, x0, "x1", M * K1)
+    Nn = w.shape[0]
+    _same(w, x0, "w", Nn * (K0 + K1))
+    _same(bias, x0, "bias", Nn)
+    if mode == "plain":
+        _same(resid, x0, "resid", M * Nn)
+        y = torch.empty((*x0.shape[:-1], Nn), dtype=x0.dtype, device=x0.device) if out is None else out
+        _same(y, x0, "out", M * Nn)
+    else:
+        if out is None or tokens <= 0 or width <= 0 or tokens % width or M % tokens:
+            raise ValueError("gemm2: tok2pf needs out (PF rows), tokens = H*W and width = W")
+        y = out
+        rows = (M // tokens) * (tokens // width + 2) * (width + 2)
+        _same(y, x0, "out", rows * Nn)
+        _same(resid, x0, "resid", rows * Nn)
+    tm = CONV_TIMER
+    with torch.cuda.device(x0.device):
+        e0 = tm.start() if tm is not None else None
+        armed = _colstats_arm(M, Nn, x0.device, geom=(M // tokens, tokens // width, width)) if (stats_for is not None and mode == "tok2pf") else None
+        ex = _extras(x0.device, colstats=None if armed is None else armed[0])
+        N.check(N.lib().gsw_gemm2_ex(x0.data_ptr(), K0, K0, x1.data_ptr(), K1, K1, w.data_ptr(), K0 + K1, bias.data_ptr() if bias is not None else None,
+                                     resid.data_ptr() if resid is not None else None, Nn, y.data_ptr(), Nn, M, Nn, GEMM_MODES[mode], tokens, width,
+                                     _dt(x0.dtype), _C.byref(ex), _stream_ptr()))
+        if stats_for is not None:
+            stats_for.stats = _colstats_collect(armed, ex)
+        if tm is not None:        # bucketed with the dense linears; bytes: both A blocks, the weight, the output (+ the residual)
+            K = K0 + K1
+            tm.stop(e0, ("gsw_mm_kernel", M, K, Nn, mode + "2" + ("+res" if resid is not None else "")) if tm.by_shape else "gsw_mm_kernel", 2.0 * M * K * Nn,
+                    nbytes=2.0 * (M * K + Nn * K + M * Nn * (2 if resid is not None else 1)))
+    return y
+
+
 # ---- LayerNorm folded into the consuming GEMM (gsw_gemm_ln): LN(x) W^T + b = rstd (x W'^T) + nrm u + v, W' = W diag(gamma), u = W' 1, v = W beta + b
 FOLD_LN = True
 FOLD_LN_MIN_ROWS = int(os.environ.get("GSW_FOLD_LN_MIN_ROWS", "1024"))       # below that the consumers would rather take the split-K form, which the folded epilogue does not have

@@ -74,6 +74,10 @@ OWN_ATTENTION = True  # attention with head_dim 40 / 64 / 80 / 160, any query co
 OWN_GEMM = True       # every dense linear layer (q / k / v / out projections, proj_in / proj_out, feed-forward, time embedding) on the
                       # hand-written matmul engine (gsw_gemm, csrc/gswm_mm.hip) with bias / residual / GEGLU / V^T epilogues fused in
 
+FOLD_FF_OUT = os.environ.get("GSW_FOLD_FF_OUT", "1") != "0"      # Transformer2DModel: the last block's ff.net[2] folded into proj_out -- one two-segment GEMM
+                      # [h | x] [Wp W2 | Wp]^T + (Wp b2 + bp) scattered into the PF tensor instead of two launches with the stream between them written and re-read
+                      # (pf.gemm2 / gsw_gemm2_ex; engine path only: the small-batch kernel keeps the two launches).  0 = the two launches (A/B)
+
 FALLBACKS = {}        # (reason -> count) of GPU half-precision calls that left the hand-written path; bench and the full-size tests assert it stays empty
 
 # Leaving the hand-written path (a shape off the engine's K % 64 / N % 8 grid, attention keys % 8, a lattice the padded-flat layout does not take) RAISES by default: a
@@ -449,12 +453,16 @@ class BasicTransformerBlock(nn.Module):
         _, n = codec.add_layernorm(x, None, self.norm2.weight, self.norm2.bias, self.norm2.eps)
         return self.attn2(n, ctx, resid=x)
 
-    def forward(self, x, ctx, dup: bool = False):
+    def forward(self, x, ctx, dup: bool = False, ff_split: bool = False):
         """dup (classifier-free guidance, see UNet2DCondition.forward): x [B, S, C], ctx [2B, ...] -> [2B, S, C]; self-attention and the cross-attention
-        queries are computed once on the B rows the two halves share."""
+        queries are computed once on the B rows the two halves share.
+        ff_split (fused path only; Transformer2DModel's last block): stop in front of ff.net[2] and return (h, x) -- the GEGLU hidden tensor and the residual
+        stream -- for a caller that folds net[2] into the linear map that follows (the block's result would be x + ff.net[2](h))."""
         if dup and not self.dup_ok(x, ctx):
             x, dup = torch.cat([x, x], dim=0), False
         if not self.fused_ok(x):
+            if ff_split:
+                raise RuntimeError("BasicTransformerBlock: ff_split is a form of the fused path")
             x = x + self.attn1(self.norm1(x))
             x = x + self.attn2(self.norm2(x), ctx)
             return x + self.ff(self.norm3(x))
@@ -478,9 +486,23 @@ class BasicTransformerBlock(nn.Module):
         inner4 = self.ff.net[2].in_features
         st = pf.ln_stat(x, self.norm3.eps) if (inner4 % 80 == 0 and _own_gemm_ok(x, x.shape[-1], 2 * inner4)) else None
         if st is not None:
+            if ff_split:
+                return pf.gemm_ln(x, st, *self.ff._folded(self.norm3), mode="geglu"), x
             return self.ff.forward_ln(x, st, self.norm3, resid=x)
         _, n = codec.add_layernorm(x, None, self.norm3.weight, self.norm3.bias, self.norm3.eps)
+        if ff_split:
+            return self.ff.net[0](n), x
         return self.ff(n, resid=x)
+
+
+def fold_ff_out(w2: torch.Tensor, b2: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor):
+    """Two linear maps with nothing between them as one: proj_out(x + ff.net[2](h)) = [h | x] W_cat^T + b' with W_cat = [Wp W2 | Wp] ([C, 5C]) and
+    b' = Wp b2 + bp.  The products are formed in fp32 (fp64 parameters: fp64) and rounded ONCE to the parameters' dtype."""
+    acc = torch.float64 if wp.dtype == torch.float64 else torch.float32
+    wpf, w2f = wp.detach().to(acc), w2.detach().to(acc)
+    w_cat = torch.cat([wpf @ w2f, wpf], dim=1).to(wp.dtype).contiguous()
+    b = (wpf @ b2.detach().to(acc) + bp.detach().to(acc)).to(wp.dtype).contiguous()
+    return w_cat, b
 
 
 class Transformer2DModel(nn.Module):
@@ -500,6 +522,22 @@ class Transformer2DModel(nn.Module):
         y = self.proj_out(y).reshape(b, h, w, c).permute(0, 3, 1, 2)
         return x + y
 
+    def _ff_out_folded(self):
+        """fold_ff_out of the last block's ff.net[2] and proj_out, cached on the module (keyed by the four parameters)"""
+        l2, po = self.transformer_blocks[-1].ff.net[2], self.proj_out
+        return pf.cached(self, "_gsw_ff_out", (l2.weight, l2.bias, po.weight, po.bias), lambda: fold_ff_out(l2.weight, l2.bias, po.weight, po.bias))
+
+    def _ff_out_fold_ok(self, y, dup: bool) -> bool:
+        """The last block's ff.net[2] and proj_out run as one two-segment launch (FOLD_FF_OUT): tokens y [B, S, C] on the fused block path, both linears on
+        the matmul engine -- the small-batch kernel (at most pf.SMALL_GEMM_MAX_ROWS rows) keeps the two launches."""
+        C = self.proj_out.in_features
+        if not (FOLD_FF_OUT and len(self.transformer_blocks) > 0 and C % 64 == 0):
+            return False
+        l2 = self.transformer_blocks[-1].ff.net[2]
+        rows = y.shape[0] * y.shape[1] * (2 if dup else 1)
+        return (BasicTransformerBlock.fused_ok(y) and l2.bias is not None and self.proj_out.bias is not None and l2.out_features == C and l2.in_features % 64 == 0
+                and self.proj_out.out_features == C and rows > pf.SMALL_GEMM_MAX_ROWS and _own_gemm_ok(y, l2.in_features, C) and _own_gemm_ok(y, C, C))
+
     def forward_pf(self, x, ctx, dup: bool = False):
         """dup: x holds B images, ctx 2B contexts -> a PF tensor of 2B images (see UNet2DCondition.forward)"""
         if xattn.gn_proj_usable(x, self.norm, self.proj_in):
@@ -507,11 +545,19 @@ class Transformer2DModel(nn.Module):
             y = xattn.gn_proj(x, self.norm, self.proj_in, eps_next=self.transformer_blocks[0].norm1.eps)
         else:
             y = _lin(pf.gn_pf(x, self.norm, act=False, tokens=True), self.proj_in, rowstats=True)      # GroupNorm writes dense tokens directly
+        last = len(self.transformer_blocks) - 1
+        fold = self._ff_out_fold_ok(y, dup)
         for i, blk in enumerate(self.transformer_blocks):
-            y = blk(y, ctx, dup=dup and i == 0)
+            y = blk(y, ctx, dup=dup and i == 0, ff_split=fold and i == last)
         if dup:
             x = pf.dup_pf(x)
-        if _own_gemm_ok(y, self.proj_out.in_features, self.proj_out.out_features):
+        if fold:
+            # proj_out(y + ff.net[2](h)) + residual as ONE launch over the two A operands (h, y): the last block's output is never written.  net[2]'s row
+            # records are not requested either -- nothing normalises the stream behind the last block
+            h, y = y
+            w, b = self._ff_out_folded()
+            pf.gemm2(h.contiguous(), y.contiguous(), w, b, resid=x.rows, mode="tok2pf", tokens=x.H * x.W, width=x.W, out=x.rows, stats_for=x)
+        elif _own_gemm_ok(y, self.proj_out.in_features, self.proj_out.out_features):
             w, b = _wb(self.proj_out, y)        # proj_out + residual written straight into the PF tensor's interior rows (x has no other reader)
             pf.gemm(y.contiguous(), w, b, resid=x.rows, mode="tok2pf", tokens=x.H * x.W, width=x.W, out=x.rows, stats_for=x)
         else:
@@ -932,7 +978,8 @@ def count_cfg_shared_prefix_flops(model: nn.Module, h: int = 64, w: int = 64) ->
 
 
 def count_flops_per_image(model: nn.Module, h: int = 64, w: int = 64, ctx_len: int = 77, ctx_dim: Optional[int] = None) -> int:
-    """Forward FLOPs for one image (2 x MACs of conv / linear / attention), via torch's FlopCounterMode on meta tensors."""
+    """Forward FLOPs for one image (2 x MACs of conv / linear / attention), via torch's FlopCounterMode on meta tensors.
+    (FOLD_FF_OUT changes nothing here: the folded launch's 2 M 5C C FLOPs are those of ff.net[2] and proj_out together.)"""
     from torch.utils.flop_counter import FlopCounterMode
     import copy
     m = copy.deepcopy(model).to("meta")

@@ -201,6 +201,20 @@ typedef struct GswMmExtras {
 /* gsw_gemm_strided / gsw_gemm_ln / gsw_conv_pf / gsw_conv3x3_res_pf / gsw_conv_up2x_pf with extras (ex may be NULL; the plain entry points ARE ex = NULL). */
 int gsw_gemm_ex(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* bias_dev, const void* resid_dev, int64_t ldr, void* y_dev, int64_t ldy,
                 int64_t M, int K, int N, int mode, int S, int Wimg, int dtype, GswMmExtras* ex, void* stream);
+/* Dense GEMM whose A operand lies in TWO column blocks (additive: the version stays 500): Y = [x0 | x1] W^T (+ bias + resid), x0 [M][ld0] with K0 columns,
+ * x1 [M][ld1] with K1 columns, W [N][K0 + K1] (the columns that multiply x1 start at K0).  The engine walks the two blocks as K segments with their own row
+ * strides, like the three-segment convolution of the resnet tail, so a product of two linear maps folded into one weight -- Transformer2DModel's
+ * proj_out(x + ff.net[2](h)) = [h | x] [Wp W2 | Wp]^T + (Wp b2 + bp) -- runs as ONE launch and the intermediate tensor is never written.
+ *   mode GSW_GEMM_TOK2PF : as the one-operand entry (in-place resid == y, column records through ex); every tiling of the PF-row epilogue, the 256 x 320 tile included.
+ *        GSW_GEMM_PLAIN  : dense rows (+ resid), on the 128- / 256-row tiles only: the wide tile's dense-row producer addresses ONE dense operand, so a two-block
+ *                          launch never takes it by itself, and where the caller forces it (gsw_mm_config tile_rows = 512) on a shape it is legal for
+ *                          (M % 256 == 0, N % 320 == 0) the call returns GSW_ERR_UNSUPPORTED without launching -- unless the plan splits the launch
+ *                          along K (a workspace in ex and few output tiles): a split launch runs the narrow split kernels whatever the tile knob
+ *                          says, with one block or two, and succeeds.
+ *        GSW_GEMM_GEGLU / GSW_GEMM_TRANS : GSW_ERR_UNSUPPORTED.
+ * Validation as the one-operand entry, per block: K0 % 64, K1 % 64, ld_i >= K_i, ld_i % 8, ldw >= K0 + K1 (else GSW_ERR_UNSUPPORTED); x1_dev NULL: GSW_ERR_BAD_ARG. */
+int gsw_gemm2_ex(const void* x0_dev, int64_t ld0, int K0, const void* x1_dev, int64_t ld1, int K1, const void* w_dev, int64_t ldw, const void* bias_dev,
+                 const void* resid_dev, int64_t ldr, void* y_dev, int64_t ldy, int64_t M, int N, int mode, int S, int Wimg, int dtype, GswMmExtras* ex, void* stream);
 int gsw_gemm_ln_ex(const void* x_dev, const float* ln_stat_dev, const void* w_dev, const float* u_dev, const float* v_dev, void* y_dev, int64_t M, int K, int N,
                    int mode, int S, int dtype, GswMmExtras* ex, void* stream);
 int gsw_conv_pf_ex(const void* x_dev, const void* w_dev, const void* bias_dev, const void* rowbias_dev, int ld_rowbias, const void* resid_dev, void* y_dev,
