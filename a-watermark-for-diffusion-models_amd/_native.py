@@ -131,6 +131,11 @@ _PROTOTYPES = {
     "gsw_sign_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
     "gsw_trace_keyed_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "gsw_trace_keyed_topk": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsw_embed_l": (C.c_int, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                              C.c_int, C.c_int, C.c_int64, C.c_uint32, C.c_int, C.c_void_p]),
+    "gsw_extract_l": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "gsw_quant_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
 }
 
 _lib = None

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .quant_table import THRESHOLDS
 
 _DTYPES = {torch.float32: N.GSW_F32, torch.float16: N.GSW_F16, torch.bfloat16: N.GSW_BF16, torch.float64: N.GSW_F64}
 
@@ -59,6 +60,22 @@ def _check_key_nonce(key: bytes, nonce: bytes):
         raise ValueError("ChaCha20 nonce must be 16 bytes (128 bits)")
 
 
+WINDOWS = (1, 2, 4)             # supported --l: cipher bits per lattice element (windows that never straddle a byte)
+
+
+def check_window(l) -> int:
+    """The window size `l` as an int, or ValueError: 1, 2 and 4 are supported ("Multi-bit windows")."""
+    if isinstance(l, bool) or not isinstance(l, (int, np.integer)) or int(l) not in WINDOWS:
+        raise ValueError(f"l must be one of {WINDOWS} (cipher bits per lattice element), got {l!r}")
+    return int(l)
+
+
+def quant_thresholds(l: int) -> np.ndarray:
+    """The 2**l - 1 float64 decision thresholds of y = int(norm.cdf(float64(z)) * 2**l): y == (z >= thresholds).sum().  The table the
+    kernels are compiled with: tools/gen_quant_thresholds.py writes quant_table.py and csrc/quant_thresholds.inc from one bisection."""
+    return np.array(THRESHOLDS[check_window(l)], dtype=np.float64)
+
+
 # ------------------------------------------------------------------------------------------------ E1: host-side prep
 def pad_message(message: str, msg_bytes: int = 32) -> bytes:
     """gs_insert.py:9-20 / nodes.py:68-76: UTF-8, zero-pad or truncate to msg_bytes; empty -> os.urandom."""
@@ -98,14 +115,17 @@ def keystream(key: bytes, nonce: bytes, nbytes: int, device="cuda") -> torch.Ten
 # ------------------------------------------------------------------------------------------------ E3-E6
 def embed_batch(key: bytes, nonce: bytes, k: bytes, batch: int, shape: Sequence[int], *, u: Optional[torch.Tensor] = None,
                 seed: int = 0, image_index0: int = 0, dtype: torch.dtype = torch.float32, fast: bool = False,
-                device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                device="cuda", out: Optional[torch.Tensor] = None, l: int = 1) -> torch.Tensor:
     """Watermarked initial latents Z_s_T, shape [batch, *shape] (shape = (4, H/8, W/8)).
 
     u: optional float64 device tensor [batch, prod(shape)] of uniforms (the reference's np.random.uniform draws) for
        bit-parity with gs_insert.py:62-64; None -> in-kernel Philox4x32-7 keyed by (seed, image_index0 + b, element).
     fast: fp32 inverse-CDF core (|dz| <= 1e-5) instead of Cephes fp64.
+    l: cipher bits per element (1, 2 or 4): z = ndtri((u + y) / 2**l) with y the element's l-bit window of the message repeated over
+       n * l bits; for l > 1 the stored value is the nearest one of `dtype` that still quantises to y.
     """
     _check_key_nonce(key, nonce)
+    l = check_window(l)
     n = 1
     for s in shape:
         n *= int(s)
@@ -121,9 +141,14 @@ def embed_batch(key: bytes, nonce: bytes, k: bytes, batch: int, shape: Sequence[
         if u.dtype != torch.float64 or u.numel() != batch * n:
             raise ValueError("u must be float64 with batch*n_elems entries")
         u_ptr = u.data_ptr()
+    mode = N.GSW_EMBED_FAST_F32 if fast else N.GSW_EMBED_EXACT_F64
     with torch.cuda.device(out.device):
-        N.check(N.lib().gsw_embed(key, nonce, k, len(k), u_ptr, seed & (2**64 - 1), image_index0, out.data_ptr(), _dt(out.dtype),
-                                  batch, n, N.GSW_EMBED_FAST_F32 if fast else N.GSW_EMBED_EXACT_F64, _stream_ptr()))
+        if l == 1:
+            N.check(N.lib().gsw_embed(key, nonce, k, len(k), u_ptr, seed & (2**64 - 1), image_index0, out.data_ptr(), _dt(out.dtype),
+                                      batch, n, mode, _stream_ptr()))
+        else:
+            N.check(N.lib().gsw_embed_l(key, nonce, k, len(k), u_ptr, seed & (2**64 - 1), image_index0, out.data_ptr(), _dt(out.dtype),
+                                        batch, n, mode, l, _stream_ptr()))
     return out
 
 
@@ -163,14 +188,16 @@ def mt19937_uniform(n: int, rng=None, *, device="cuda") -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ X3-X5
-def extract_batch(z: torch.Tensor, key: bytes, nonce: bytes, message_length: int, *, return_counts: bool = False):
-    """Recover the message from latents z [B, ...] (any of fp16/bf16/fp32/fp64).
+def extract_batch(z: torch.Tensor, key: bytes, nonce: bytes, message_length: int, *, return_counts: bool = False, l: int = 1):
+    """Recover the message from latents z [B, ...] (any of fp16/bf16/fp32/fp64); l: cipher bits per element (1, 2 or 4), the
+    lattice then holds n * l bits and each message bit gets n * l / message_length votes.
 
     Returns (bits uint8 [B, ceil(M/8)] MSB-first, flags int32 [B]) (+ counts int32 [B, M] '1'-votes).
     flags != 0 marks images for which the reference raises ValueError (saturated cdf / NaN), extract.py:84-86.
     Raises IndexError when the reference would (padded bit count not a multiple of message_length).
     """
     _check_key_nonce(key, nonce)
+    l = check_window(l)
     _need_gpu(z, "z")
     B = z.shape[0]
     n = z.numel() // max(B, 1)
@@ -179,8 +206,12 @@ def extract_batch(z: torch.Tensor, key: bytes, nonce: bytes, message_length: int
     flags = torch.empty((B,), dtype=torch.int32, device=z.device)
     counts = torch.empty((B, M), dtype=torch.int32, device=z.device) if return_counts else None
     with torch.cuda.device(z.device):
-        N.check(N.lib().gsw_extract(z.data_ptr(), _dt(z.dtype), key, nonce, M, bits.data_ptr(),
-                                    counts.data_ptr() if return_counts else None, flags.data_ptr(), B, n, _stream_ptr()))
+        if l == 1:
+            N.check(N.lib().gsw_extract(z.data_ptr(), _dt(z.dtype), key, nonce, M, bits.data_ptr(),
+                                        counts.data_ptr() if return_counts else None, flags.data_ptr(), B, n, _stream_ptr()))
+        else:
+            N.check(N.lib().gsw_extract_l(z.data_ptr(), _dt(z.dtype), key, nonce, M, bits.data_ptr(),
+                                          counts.data_ptr() if return_counts else None, flags.data_ptr(), B, n, l, _stream_ptr()))
     return (bits, flags, counts) if return_counts else (bits, flags)
 
 
@@ -201,13 +232,17 @@ def bits_to_str(bits_row) -> str:
 
 
 # ------------------------------------------------------------------------------------------------ tracing (registry search)
-def vote_copies(n_elems: int, message_length: int) -> int:
+def vote_copies(n_elems: int, message_length: int, l: int = 1) -> int:
     """Votes per message bit: the lattice padded to whole bytes (extract.py:88-92) splits into this many message_length-wide segments.
-    Raises IndexError where `extract_batch` does (the padded bit count is not a multiple of message_length, extract.py:98)."""
+    Raises IndexError where `extract_batch` does (the padded bit count is not a multiple of message_length, extract.py:98).
+    l: cipher bits per element; for l > 1 the lattice holds n_elems * l bits, which must fill whole bytes (ValueError otherwise)."""
     n, m = int(n_elems), int(message_length)
+    l = check_window(l)
     if n <= 0 or m <= 0:
         raise ValueError("n_elems and message_length must be positive")
-    padded = (n + 7) // 8 * 8
+    if l > 1 and (n * l) % 8:
+        raise ValueError(f"a lattice of {n} elements at l = {l} does not fill whole bytes")
+    padded = (n * l + 7) // 8 * 8
     if padded % m:
         raise IndexError("string index out of range")
     return padded // m
@@ -269,6 +304,25 @@ def sign_pack(z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     with torch.cuda.device(z.device):
         N.check(N.lib().gsw_sign_pack(z.data_ptr(), _dt(z.dtype), signs.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
     return signs, flags
+
+
+def quant_pack(z: torch.Tensor, l: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The l-bit form of `sign_pack`: y = int(norm.cdf(float64(z)) * 2**l) per element of latents z [B, ...], l bits each, MSB first:
+    (packed uint8 [B, n * l / 8], flags int32 [B]); a saturated element packs as all ones, a NaN as zeros.  The operand of
+    `trace_keyed_topk` with n_bits = n * l.  l == 1 is `sign_pack`."""
+    l = check_window(l)
+    if l == 1:
+        return sign_pack(z)
+    _need_gpu(z, "z")
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    if n < 1 or (n * l) % 8:
+        raise ValueError(f"quant_pack needs a lattice whose {l}-bit windows fill whole bytes (got {n} elements per image)")
+    packed = torch.empty((B, n * l // 8), dtype=torch.uint8, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_quant_pack(z.data_ptr(), _dt(z.dtype), packed.data_ptr(), flags.data_ptr(), B, n, l, _stream_ptr()))
+    return packed, flags
 
 
 def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1555,3 +1555,8 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
     GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Multi-bit windows (l = 2, 4): gsw_embed_l / gsw_extract_l / gsw_quant_pack, kernels and entry points
+// ------------------------------------------------------------------------------------------------
+#include "gswm_codec_l.inc"

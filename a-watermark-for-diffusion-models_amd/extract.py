@@ -1,8 +1,9 @@
 """Drop-in twin of the recover-bits API of the reference's extract.py (extract.py:72-110), with the per-element
 norm.cdf loop, the ChaCha20 decrypt and the majority vote running as one HIP kernel.
 
-`args` is the reference's argparse namespace: .key (32 bytes), .nonce (16 bytes), .l (must be 1: the reference's
-l > 1 path is non-functional), .message_length.
+`args` is the reference's argparse namespace: .key (32 bytes), .nonce (16 bytes), .l (1, 2 or 4 cipher bits per lattice
+element; the reference's own l > 1 path is non-functional, SURVEY.md section 5, so l = 2, 4 follow DESIGN.md "Multi-bit windows"),
+.message_length.
 """
 from __future__ import annotations
 
@@ -30,17 +31,25 @@ def _to_device_latents(reversed_latents, device):
     return torch.from_numpy(a).to(device).reshape(1, -1)
 
 
+def _window(args) -> int:
+    """args.l as a supported window.  A string or float that counted as l = 1 before windows existed still does (int(l) == 1: a
+    namespace built by hand may carry "1" or 1.0); everything else has to be one of codec.WINDOWS as an int."""
+    l = getattr(args, "l", 1)
+    if isinstance(l, (str, float)) and int(l) == 1:
+        return 1
+    return codec.check_window(l)
+
+
 def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     """extract.py:72-101 -> str of message_length '0'/'1' characters.
 
     Raises ValueError where the reference does (a latent >= 8.2924 saturates norm.cdf so int(y) == 2, or NaN;
     extract.py:84-86) and IndexError when the padded bit count is not a multiple of message_length (extract.py:98).
     """
-    if int(getattr(args, "l", 1)) != 1:
-        raise ValueError("only l == 1 is functional in the reference (extract.py:84-86 breaks for l > 1)")
+    l = _window(args)
     z = _to_device_latents(reversed_latents, device)
     m = int(args.message_length)
-    bits, flags = codec.extract_batch(z, args.key, args.nonce, m)
+    bits, flags = codec.extract_batch(z, args.key, args.nonce, m, l=l)
     f = int(flags[0].item())
     if f & N.GSW_FLAG_NAN:
         raise ValueError("cannot convert float NaN to integer")
@@ -52,8 +61,9 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
 def recover_exactracted_message_batch(latents: torch.Tensor, args):
     """Batch form: latents [B, 4, h, w] on the device -> (list of bit strings or the raised exception per image).
     Mirrors the per-image try/except of extract.py:148-155."""
+    l = _window(args)
     m = int(args.message_length)
-    bits, flags = codec.extract_batch(latents.contiguous(), args.key, args.nonce, m)
+    bits, flags = codec.extract_batch(latents.contiguous(), args.key, args.nonce, m, l=l)
     bits_h, flags_h = bits.cpu().numpy(), flags.cpu().numpy()
     out = []
     for b in range(bits_h.shape[0]):
@@ -554,7 +564,7 @@ def build_parser():
     parser.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     parser.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     parser.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
-    parser.add_argument("--l", default=1, type=int, help="The size of slide windows for m")
+    parser.add_argument("--l", default=1, type=int, help="The size of slide windows for m: cipher bits per lattice element (1, 2 or 4)")
     parser.add_argument("--width", type=int, default=1024, help="Width of the input image")
     parser.add_argument("--height", type=int, default=1024, help="Height of the input image")
     parser.add_argument("--message_length", type=int, default=1024, help="Length of the message in bits")

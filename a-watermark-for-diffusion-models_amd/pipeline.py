@@ -19,7 +19,7 @@ from .ddim import DDIMSchedule, ddim_invert_extract, ddim_sample, ddim_invert
 class GaussianShadingPipeline:
     def __init__(self, eps_model, key: bytes, nonce: bytes, message: bytes, *, height: int = 512, width: int = 512,
                  num_inference_steps: int = 50, dtype: torch.dtype = torch.float16, device="cuda",
-                 ctx_uncond: Optional[torch.Tensor] = None, prediction_type: str = "epsilon"):
+                 ctx_uncond: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", l: int = 1):
         if hasattr(eps_model, "prepare_context"):          # a unet.UNet2DCondition: small batches replay a captured HIP graph of the forward (graph.py)
             from .graph import graphed
             eps_model = graphed(eps_model, clone_output=False)      # the loops of ddim.py consume eps in the scheduler-step kernel right away
@@ -30,11 +30,12 @@ class GaussianShadingPipeline:
         self.schedule = DDIMSchedule(num_inference_steps=num_inference_steps, prediction_type=prediction_type)
         self.ctx_uncond = ctx_uncond
         self.message_length = 8 * len(message)
+        self.l = codec.check_window(l)                      # cipher bits per lattice element, a property of the deployment like the key
 
     # E1-E6
     def embed(self, batch: int, *, seed: int = 0, image_index0: int = 0, fast: bool = True, u: Optional[torch.Tensor] = None) -> torch.Tensor:
         return codec.embed_batch(self.key, self.nonce, self.message, batch, self.shape, u=u, seed=seed, image_index0=image_index0,
-                                 dtype=self.dtype, fast=fast, device=self.device)
+                                 dtype=self.dtype, fast=fast, device=self.device, l=self.l)
 
     # G1
     def _uncond(self, batch: int) -> torch.Tensor:
@@ -54,6 +55,10 @@ class GaussianShadingPipeline:
     # X2 + X3-X5 (prompt "" -> the unconditional context, guidance 1: extract.py:66-69)
     def invert_and_extract(self, x0: torch.Tensor, *, return_latents: bool = False):
         ctx = self._uncond(x0.shape[0])
+        if self.l != 1:                                     # the fused last step votes one bit per element: plain last step, then the l-bit extract
+            z = ddim_invert(self.eps_model, x0, ctx, self.schedule)
+            res = codec.extract_batch(z, self.key, self.nonce, self.message_length, l=self.l)
+            return (*res, z) if return_latents else res
         return ddim_invert_extract(self.eps_model, x0, ctx, self.schedule, self.key, self.nonce, self.message_length,
                                    return_latents=return_latents)
 

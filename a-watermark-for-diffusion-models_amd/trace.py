@@ -517,11 +517,12 @@ class TraceResult:
 
 
 def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, message_length: Optional[int] = None, k: int = 1,
-                  fpr: float = 1e-6, soft: bool = True) -> List[Union[TraceResult, ValueError]]:
+                  fpr: float = 1e-6, soft: bool = True, l: int = 1) -> List[Union[TraceResult, ValueError]]:
     """latents [B, ...] on the device -> one TraceResult per image (best candidate first), or the ValueError the reference raises for
     that image (a saturated / NaN latent, extract.py:84-86), like `extract.recover_exactracted_message_batch`.
 
-    One vote kernel, one search launch over the packed registry; the host receives the B k pairs (plus the vote's flags and bits)."""
+    One vote kernel, one search launch over the packed registry; the host receives the B k pairs (plus the vote's flags and bits).
+    l: cipher bits per lattice element the images were embedded with (a property of the deployment, like the key)."""
     import torch
     from . import _native as N
     if not 0.0 < float(fpr) <= 1.0:
@@ -530,9 +531,9 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
     z = latents.contiguous()
     B = z.shape[0]
     rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
-    V = codec.vote_copies(z.numel() // max(B, 1), M)
+    V = codec.vote_copies(z.numel() // max(B, 1), M, l)
     reg_dev = registry.to_device(z.device, M)
-    bits, flags, counts = codec.extract_batch(z, key, nonce, M, return_counts=True)
+    bits, flags, counts = codec.extract_batch(z, key, nonce, M, return_counts=True, l=l)
     idx, score = codec.trace_topk(counts, V, reg_dev, k=k, soft=soft)
     pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy; flags and voted bits are the vote's own outputs
     idx_h, score_h = pairs[0], pairs[1]
@@ -560,14 +561,15 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
     return out
 
 
-def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: float = 1e-6) -> List[Union[TraceResult, ValueError]]:
+def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: float = 1e-6, l: int = 1) -> List[Union[TraceResult, ValueError]]:
     """`trace_latents` against a registry whose records carry their own keys: latents [B, ...] on the device -> one TraceResult per
     image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
 
     One quantise-and-pack kernel, one search launch over the record rows (every record's keystream is generated inside it); the host
     receives the B k (index, score) pairs and the flags.  score = n - 2 popcount(signs ^ codeword), whose null distribution is that of
     the soft score (`log10_p_soft(score, n)`), Bonferroni over the records.  `Candidate.agree` is the reference's voted-bit agreement
-    under that candidate's own key: `codec.extract_batch` + `codec.bit_matches` for the reported candidates only, grouped by key."""
+    under that candidate's own key: `codec.extract_batch` + `codec.bit_matches` for the reported candidates only, grouped by key.
+    l: cipher bits per lattice element; the codewords then span n l bits."""
     import torch
     from . import _native as N
     if not 0.0 < float(fpr) <= 1.0:
@@ -576,10 +578,11 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     B = z.shape[0]
     n = z.numel() // max(B, 1)
     M = registry.message_bits
-    codec.vote_copies(n, M)                              # (a lattice the messages do not tile fails here, as extract_batch would)
+    codec.vote_copies(n, M, l)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    nb = n * codec.check_window(l)
     rec_dev = registry.to_device(z.device)
-    signs, flags = codec.sign_pack(z)
-    idx, score = codec.trace_keyed_topk(signs, n, rec_dev, registry.message_bytes, k=k)
+    signs, flags = codec.quant_pack(z, l)
+    idx, score = codec.trace_keyed_topk(signs, nb, rec_dev, registry.message_bytes, k=k)
     pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy
     idx_h, score_h = pairs[0], pairs[1]
     flags_h = flags.cpu().numpy()
@@ -598,7 +601,7 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
             i, s = int(idx_h[b, j]), int(score_h[b, j])
             if i < 0:
                 break
-            c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(log10_p_soft(s, n), U))
+            c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(log10_p_soft(s, nb), U))
             key, nonce, msg = registry.record_at(i)
             reported.setdefault((key, nonce), {}).setdefault(msg, []).append((b, c))
             res.candidates.append(c)
@@ -608,7 +611,7 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     for (key, nonce), by_message in reported.items():
         images = sorted({b for pairs_ in by_message.values() for b, _ in pairs_})
         row = {b: r for r, b in enumerate(images)}
-        bits, _ = codec.extract_batch(z[torch.tensor(images, device=z.device)].contiguous(), key, nonce, M)
+        bits, _ = codec.extract_batch(z[torch.tensor(images, device=z.device)].contiguous(), key, nonce, M, l=l)
         for msg, pairs_ in by_message.items():
             agree = codec.bit_matches(bits, M, msg).cpu().numpy()
             for b, c in pairs_:
@@ -670,6 +673,7 @@ def build_parser():
     p.add_argument("--height", type=int, default=1024, help="Height of the input image")
     p.add_argument("--message_length", type=int, default=None, help="Length of the message in bits (default: the registry's own length; a multiple of it "
                                                                      "repeats the registered messages, which weakens --hard)")
+    p.add_argument("--l", type=int, default=1, choices=codec.WINDOWS, help="cipher bits per lattice element the images were embedded with")
     p.add_argument("--allow_synthetic_weights", action="store_true", help="run without a checkpoint (pipeline tests / benchmarks only)")
     p.add_argument("--batch_size", type=int, default=16, help="images per device batch")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
@@ -692,8 +696,9 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
     def run(arrs):
         latents = X.invert_decoded_images(arrs, args)
         if args.per_record_keys:
-            return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr)
-        return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard)
+            return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr, l=args.l)
+        return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard,
+                             l=args.l)
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         decoded = list(pool.map(decode, files))

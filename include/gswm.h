@@ -545,6 +545,32 @@ size_t gsw_trace_keyed_workspace_bytes(int B, int64_t n_records, int k);
 int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
                          int64_t n_records, int k, int32_t* idx_dev, int32_t* score_dev, void* workspace_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Multi-bit windows: extract.py's --l ("the size of slide windows for m"; gs_insert.py:52-53 "can be a value other than 1").  The
+ * reference's own l > 1 path does not run (gs_insert.py:23,58-66 fills 1/l of the lattice; extract.py:84-86 parses decimal digits as
+ * base 2), so the semantics are this library's ("Multi-bit windows").  Additive: gsw_version() stays 500.
+ *
+ *   l       : 1, 2 or 4 (windows that never straddle a byte).  l == 1 IS the entry point without _l, argument for argument.  Any other
+ *             l, and for l > 1 a lattice with (n_elems * l) % 8 != 0 or n_elems * l > 0x7FFFFFF0: GSW_ERR_UNSUPPORTED.
+ *   Nb      = n_elems * l cipher bits per image = the keystream of gsw_keystream XOR the message repeated floor(Nb / (8 msg_bytes)) times
+ *             then zeros, MSB-first within each byte; element i takes bits [i l, i l + l), the first one is the MSB of y_i
+ *   embed   : z_i = ndtri((u_i + y_i) / 2^l), one u per element (u_dev, or the Philox stream of gsw_embed, same addressing); the stored
+ *             value is the representable value of out_dtype nearest to z_i that still quantises to y_i (bin-safe rounding), so a noiseless
+ *             gsw_extract_l returns every count as 0 or copies in every dtype.  u = 0, y = 0 gives -inf.  GSW_EMBED_FAST_F32: |dz| <= 1e-5,
+ *             same y; arguments below the fp32 core's domain take the exact core.
+ *   quantise: y = int(norm.cdf(float64(z)) * 2^l), exactly, for fp16 / bf16 / fp32 / fp64 inputs (2^l - 1 thresholds, csrc/quant_thresholds.inc);
+ *             z >= 8.292361075813597 packs as all ones and sets GSW_FLAG_SATURATED, NaN packs as zeros and sets GSW_FLAG_NAN
+ *   extract : the y of an image written as l bits each, XOR keystream, strict-majority vote in msg_bits-wide segments (ties -> 0);
+ *             counts are exact '1' votes out of copies = Nb / msg_bits; GSW_ERR_RAGGED when that is not whole.  GSW_ERR_UNSUPPORTED when
+ *             keystream + decrypted bits + vote (about Nb / 4 bytes) exceed the LDS of a CU.
+ *   gsw_quant_pack: the l-bit gsw_sign_pack: packed_dev [B, Nb / 8], the operand of gsw_trace_keyed_topk with n_bits = Nb.
+ * Pointers, dtypes, B and stream as in the l = 1 entry points; the same GSW_ERR_BAD_ARG conditions. */
+int gsw_embed_l(const uint8_t key[32], const uint8_t nonce16[16], const uint8_t* msg, int msg_bytes, const double* u_dev, uint64_t seed,
+                uint64_t image_index0, void* out_dev, int out_dtype, int B, int64_t n_elems, uint32_t flags, int l, void* stream);
+int gsw_extract_l(const void* z_dev, int z_dtype, const uint8_t key[32], const uint8_t nonce16[16], int msg_bits, uint8_t* bits_dev,
+                  uint32_t* counts_dev, uint32_t* flags_dev, int B, int64_t n_elems, int l, void* stream);
+int gsw_quant_pack(const void* z_dev, int z_dtype, uint8_t* packed_dev, uint32_t* flags_dev, int B, int64_t n_elems, int l, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
