@@ -47,6 +47,8 @@ _PROTOTYPES = {
     "gsw_ddim_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int64, C.c_void_p]),
     "gsw_ddim_step_cfg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
                                     C.c_int, C.c_int64, C.c_void_p]),
+    "gsw_dpm_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                               C.c_float, C.c_float, C.c_float, C.c_int, C.c_int64, C.c_void_p]),
     "gsw_ddim_step_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_char_p,
                                         C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
                                         C.c_void_p]),

@@ -390,6 +390,41 @@ def ddim_step_cfg(x: torch.Tensor, e_uncond: torch.Tensor, e_text: torch.Tensor,
     return out
 
 
+def _dpm_step(x, e_uncond, e_text, pq, abc, guidance, m_prev, out, m_out):
+    _need_gpu(x, "x")
+    _like(e_uncond, x, "e_uncond" if e_text is not None else "model_out", x.numel())
+    if e_text is not None:
+        _like(e_text, x, "e_text", x.numel())
+    (P, Q), (A, B, C) = pq, abc
+    if m_prev is None and C != 0.0:
+        raise ValueError("dpm_step: a second-order update (C != 0) needs m_prev")
+    if m_prev is not None:
+        _like(m_prev, x, "m_prev", x.numel())
+    if out is None:
+        out = torch.empty_like(x)
+    if m_out is None:
+        m_out = torch.empty_like(x)
+    _like(out, x, "out", x.numel()); _like(m_out, x, "m_out", x.numel())
+    with torch.cuda.device(x.device):
+        N.check(N.lib().gsw_dpm_step(x.data_ptr(), e_uncond.data_ptr(), e_text.data_ptr() if e_text is not None else None,
+                                     m_prev.data_ptr() if m_prev is not None else None, out.data_ptr(), m_out.data_ptr(),
+                                     P, Q, A, B, C, guidance, _dt(x.dtype), x.numel(), _stream_ptr()))
+    return out, m_out
+
+
+def dpm_step(x: torch.Tensor, e: torch.Tensor, pq: Tuple[float, float], abc: Tuple[float, float, float], m_prev: Optional[torch.Tensor] = None, *,
+             out: Optional[torch.Tensor] = None, m_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One DPM-Solver++ multistep scheduler step in one launch: m0 = P x + Q e (the x0 prediction, rounded as `ddim_step(x, e, P, Q)` rounds it),
+    x' = A x + B m0 + C m_prev -> (x', m0).  out may be x and m_out may be m_prev (in place); m_prev is not read when C == 0."""
+    return _dpm_step(x, e, None, pq, abc, 0.0, m_prev, out, m_out)
+
+
+def dpm_step_cfg(x: torch.Tensor, e_uncond: torch.Tensor, e_text: torch.Tensor, pq: Tuple[float, float], abc: Tuple[float, float, float], guidance: float,
+                 m_prev: Optional[torch.Tensor] = None, *, out: Optional[torch.Tensor] = None, m_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`dpm_step` on e = e_uncond + guidance (e_text - e_uncond), the guidance folded into the same launch."""
+    return _dpm_step(x, e_uncond, e_text, pq, abc, guidance, m_prev, out, m_out)
+
+
 def ddim_step_extract(x: torch.Tensor, model_out: torch.Tensor, a: float, b: float, key: bytes, nonce: bytes,
                       message_length: int, *, z_out: Optional[torch.Tensor] = None, return_counts: bool = False):
     """Last inversion step fused with the vote: z = a*x + b*model_out is quantised and voted without a round trip to HBM."""

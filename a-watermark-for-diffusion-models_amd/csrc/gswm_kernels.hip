@@ -957,6 +957,64 @@ __global__ __launch_bounds__(GSW_WG) void gsw_ddim_step_kernel(const T* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// DPM-Solver++ multistep update, the whole scheduler step in one pass:
+//   e = CFG ? e0 + g (e1 - e0) : e0;  m0 = round_T(P x + Q e);  x' = round_T(A x + B m0 + (ORDER2 ? C m_prev : 0))
+// fp32 math; m0 is formed by ddim_z like every other x0 prediction / DDIM update and enters the update AS STORED, so the next step's m_prev is the value
+// this step used.  HBM-bound: (2 + CFG + ORDER2) streams in, 2 out.  x_out may alias x and m_out may alias m_prev (no __restrict__ on those four: m0 does
+// not depend on m_prev, so a restrict-qualified m_out store could legally move above the m_prev load); a thread reads all it needs before it writes.
+// ------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ float dpm_x(float A, float x, float B, float m0, float C, float mp, bool order2) {
+    float z = fmaf(B, m0, A * x);
+    if (order2) z = fmaf(C, mp, z);
+    asm volatile("" : "+v"(z));      // as ddim_z: the conversion to T stays a second rounding in every copy
+    return z;
+}
+
+template <typename T> static __device__ __forceinline__ void store1(T* p, float v) {
+    if constexpr (sizeof(T) == 4) *reinterpret_cast<float*>(p) = v;
+    else if constexpr (std::is_same<T, __half>::value) *p = __float2half_rn(v);
+    else *p = __float2bfloat16(v);
+}
+
+template <typename T, bool CFG, bool ORDER2>
+__global__ __launch_bounds__(GSW_WG) void gsw_dpm_step_kernel(const T* x, const T* __restrict__ e0, const T* __restrict__ e1, const T* m_prev,
+                                                             T* x_out, T* m_out, float P, float Q, float A, float B, float C, float g, uint64_t n) {
+    const uint64_t nvec = n >> 3;
+    const uint64_t stride = (uint64_t)gridDim.x * GSW_WG;
+    for (uint64_t i = (uint64_t)blockIdx.x * GSW_WG + threadIdx.x; i < nvec; i += stride) {
+        float xv[8], ev[8], pv[8], mv[8], zv[8];
+        Load8<T>::ld(x + (i << 3), xv);
+        Load8<T>::ld(e0 + (i << 3), ev);
+        if (CFG) {
+            float tv[8];
+            Load8<T>::ld(e1 + (i << 3), tv);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) ev[k] = fmaf(g, tv[k] - ev[k], ev[k]);
+        }
+        if (ORDER2) Load8<T>::ld(m_prev + (i << 3), pv);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            mv[k] = round_to<T>(ddim_z(P, xv[k], Q, ev[k]));
+            zv[k] = dpm_x(A, xv[k], B, mv[k], C, ORDER2 ? pv[k] : 0.f, ORDER2);
+        }
+        Store8<T>::st(x_out + (i << 3), zv);
+        Store8<T>::st(m_out + (i << 3), mv);
+    }
+    // tail (< 8 elements)
+    if (blockIdx.x == 0) {
+        for (uint64_t i = (nvec << 3) + threadIdx.x; i < n; i += GSW_WG) {
+            float ev = Load8<T>::ld1(e0 + i);
+            if (CFG) { const float tv = Load8<T>::ld1(e1 + i); ev = fmaf(g, tv - ev, ev); }
+            const float xs = Load8<T>::ld1(x + i);
+            const float mp = ORDER2 ? Load8<T>::ld1(m_prev + i) : 0.f;
+            const float m0 = round_to<T>(ddim_z(P, xs, Q, ev));
+            store1<T>(x_out + i, dpm_x(A, xs, B, m0, C, mp, ORDER2));
+            store1<T>(m_out + i, m0);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // UNet elementwise fusions (rows X2 / G1: the eps model's non-GEMM traffic).  rocprofv3 of the SD2.1-shaped UNet on
 // PyTorch-ROCm shows ~30 % of the forward in elementwise / normalisation kernels; these two remove the largest pieces.
 //
@@ -1507,6 +1565,35 @@ int gsw_ddim_step_cfg(const void* x_dev, const void* e_uncond_dev, const void* e
                       float guidance, int dtype, int64_t n, void* stream) {
     if (!e_text_dev) return GSW_ERR_BAD_ARG;
     return ddim_dispatch(x_dev, e_uncond_dev, e_text_dev, out_dev, a, b, guidance, dtype, n, stream);
+}
+
+template <typename T>
+static int launch_dpm(const void* x, const void* e0, const void* e1, const void* mp, void* xo, void* mo, float P, float Q, float A, float B, float C, float g,
+                      int64_t n, hipStream_t st) {
+    const uint64_t nvec = (uint64_t)n >> 3;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nvec + GSW_WG - 1) / GSW_WG, (uint64_t)device_cus() * 8));
+#define GSW_DPM(CFG, O2) hipLaunchKernelGGL((gsw_dpm_step_kernel<T, CFG, O2>), dim3(grid), dim3(GSW_WG), 0, st, (const T*)x, (const T*)e0, (const T*)e1, \
+                                            (const T*)mp, (T*)xo, (T*)mo, P, Q, A, B, C, g, (uint64_t)n)
+    if (e1) { if (mp) GSW_DPM(true, true); else GSW_DPM(true, false); }
+    else    { if (mp) GSW_DPM(false, true); else GSW_DPM(false, false); }
+#undef GSW_DPM
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
+int gsw_dpm_step(const void* x_dev, const void* e_uncond_dev, const void* e_text_dev, const void* m_prev_dev, void* x_out_dev, void* m_out_dev,
+                 float P, float Q, float A, float B, float C, float guidance, int dtype, int64_t n, void* stream) {
+    if (!x_dev || !e_uncond_dev || !x_out_dev || !m_out_dev || n < 0) return GSW_ERR_BAD_ARG;
+    if (dtype != GSW_F32 && dtype != GSW_F16 && dtype != GSW_BF16) return GSW_ERR_BAD_ARG;
+    if (!m_prev_dev && C != 0.0f) return GSW_ERR_BAD_ARG;
+    if (n == 0) return GSW_OK;
+    if (C == 0.0f) m_prev_dev = nullptr;      // first order: m_prev is not read at all (0 * NaN would be NaN)
+    hipStream_t st = (hipStream_t)stream;
+    switch (dtype) {
+        case GSW_F32: return launch_dpm<float>(x_dev, e_uncond_dev, e_text_dev, m_prev_dev, x_out_dev, m_out_dev, P, Q, A, B, C, guidance, n, st);
+        case GSW_F16: return launch_dpm<__half>(x_dev, e_uncond_dev, e_text_dev, m_prev_dev, x_out_dev, m_out_dev, P, Q, A, B, C, guidance, n, st);
+        default: return launch_dpm<__hip_bfloat16>(x_dev, e_uncond_dev, e_text_dev, m_prev_dev, x_out_dev, m_out_dev, P, Q, A, B, C, guidance, n, st);
+    }
 }
 
 

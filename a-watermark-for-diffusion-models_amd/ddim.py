@@ -210,11 +210,17 @@ class DPMSolverInverseSchedule:
 
 
 @torch.no_grad()
-def dpms_invert(eps_model: EpsModel, x0: torch.Tensor, ctx: torch.Tensor, schedule: DPMSolverInverseSchedule) -> torch.Tensor:
-    """X2 with `--scheduler DPMs`: DPM-Solver++(2M) inversion x_0 -> x_T."""
+def dpms_invert(eps_model: EpsModel, x0: torch.Tensor, ctx: torch.Tensor, schedule: DPMSolverInverseSchedule, *, fused: bool = False) -> torch.Tensor:
+    """X2 with `--scheduler DPMs`: DPM-Solver++(2M) inversion x_0 -> x_T.  fused=True runs each step as ONE `gsw_dpm_step` launch (the update is rounded once
+    instead of once per term, so the bits differ from the default's below the storage precision); the default keeps the 2-3 launches per step and their bits."""
     steps = schedule.steps()
     tt = _t_tensors([s[0] for s in steps], x0.device)
     x = x0.clone()
+    if fused:
+        m = torch.empty_like(x)
+        for (t, pq, abc), t_dev in zip(steps, tt):
+            codec.dpm_step(x, eps_model(x, t_dev, ctx), pq, abc, m if abc[2] != 0.0 else None, out=x, m_out=m)
+        return x
     m_prev = None
     for (t, (P, Q), (A, B, C)), t_dev in zip(steps, tt):
         m0 = codec.ddim_step(x, eps_model(x, t_dev, ctx), P, Q)          # x0 prediction of this step
@@ -222,4 +228,107 @@ def dpms_invert(eps_model: EpsModel, x0: torch.Tensor, ctx: torch.Tensor, schedu
         if C != 0.0:
             codec.ddim_step(x, m_prev, 1.0, C, out=x)
         m_prev = m0
+    return x
+
+
+# =====================================================================================================================
+# The forward twin: DPM-Solver++ 2M sampling, what the SD front ends the reference plugs into (WebUI, ComfyUI) default to at 20-30 steps
+# (diffusers' DPMSolverMultistepScheduler: data prediction, midpoint, solver_order 2).  Restated from the published algorithm
+# (Lu et al., "DPM-Solver++"; Karras et al. for the rho-7 sigma spacing) in diffusers' sigma parametrisation; parity unpinned, like the inverse
+# schedule above: diffusers is not available here.  tests/dpm_reference.py restates the solver step by step in float64 and checks the coefficients.
+# The whole step (guidance, x0 prediction, multistep update) is ONE launch of `gsw_dpm_step` (DESIGN.md 4.13).
+# =====================================================================================================================
+@dataclass
+class DPMSolverSchedule:
+    num_inference_steps: int = 20
+    num_train_timesteps: int = 1000
+    prediction_type: str = "epsilon"
+    solver_order: int = 2
+    timestep_spacing: str = "linspace"          # "linspace": linspace(0, 999, S + 1).round()[::-1][:-1]; "leading": the DDIMSchedule list
+    final_sigmas_type: str = "zero"             # "zero": the last step returns the x0 prediction; "sigma_min": it stops at the table's first sigma
+    lower_order_final: bool = True
+    use_karras_sigmas: bool = False
+
+    def __post_init__(self):
+        S, T = self.num_inference_steps, self.num_train_timesteps
+        if not 1 <= S <= T:
+            raise ValueError(f"DPMSolverSchedule: num_inference_steps must be in 1..{T} (got {S})")
+        if self.solver_order not in (1, 2):
+            raise ValueError(f"DPMSolverSchedule: solver_order must be 1 or 2 (got {self.solver_order})")
+        if self.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(self.prediction_type)
+        if self.final_sigmas_type not in ("zero", "sigma_min"):
+            raise ValueError(f"DPMSolverSchedule: final_sigmas_type must be 'zero' or 'sigma_min' (got {self.final_sigmas_type!r})")
+        ac = sd_alphas_cumprod(T)
+        all_sigmas = ((1 - ac) / ac) ** 0.5
+        if self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, S + 1).round()[::-1][:-1].astype(np.int64)
+        elif self.timestep_spacing == "leading":
+            ts = DDIMSchedule(num_inference_steps=S, num_train_timesteps=T).timesteps_desc.astype(np.int64)
+        else:
+            raise ValueError(f"DPMSolverSchedule: timestep_spacing must be 'linspace' or 'leading' (got {self.timestep_spacing!r})")
+        if self.use_karras_sigmas:
+            # rho 7 between the table's last (noisiest) and first sigma; a timestep is the sigma's place in the log-sigma table, rounded: an integer in
+            # [0, T) as the eps model's time-embedding table needs (repeats at the low end are legal).  The coefficients use the Karras sigmas themselves.
+            rho = 7.0
+            hi, lo = all_sigmas[-1] ** (1 / rho), all_sigmas[0] ** (1 / rho)
+            sig = (hi + np.linspace(0, 1, S) * (lo - hi)) ** rho
+            sig[0] = all_sigmas[-1]                          # the ends are the table's own entries, not their seventh root raised again
+            if S > 1:
+                sig[-1] = all_sigmas[0]
+            ts = np.clip(np.interp(np.log(sig), np.log(all_sigmas), np.arange(T, dtype=np.float64)).round(), 0, T - 1).astype(np.int64)
+        else:
+            sig = np.interp(ts, np.arange(T), all_sigmas)
+        self.timesteps = ts.copy()
+        self.sigmas = np.concatenate([sig, [0.0 if self.final_sigmas_type == "zero" else all_sigmas[0]]])
+
+    _alpha_sigma = staticmethod(DPMSolverInverseSchedule._alpha_sigma)
+
+    def steps(self):
+        """[(t, (P, Q), (A, B, C))] in sampling order: m0 = P x + Q model_out (x0 prediction); x' = A x + B m0 + C m1 (m1 = the previous step's m0)."""
+        out = []
+        S = self.num_inference_steps
+        lam = lambda a, s: np.log(a) - np.log(s)
+        for i, t in enumerate(self.timesteps):
+            a_s0, s_s0 = self._alpha_sigma(self.sigmas[i])
+            a_t, s_t = self._alpha_sigma(self.sigmas[i + 1])
+            P, Q = (1.0 / a_s0, -s_s0 / a_s0) if self.prediction_type == "epsilon" else (a_s0, -s_s0)
+            last = i == S - 1
+            if s_t == 0.0:                                   # sigma -> 0: h = inf, e^{-h} = 0: the step lands on the x0 prediction
+                out.append((int(t), (float(P), float(Q)), (0.0, 1.0, 0.0)))
+                continue
+            h = lam(a_t, s_t) - lam(a_s0, s_s0)
+            A = s_t / s_s0
+            k = -a_t * (np.exp(-h) - 1.0)
+            first_order = self.solver_order == 1 or i == 0 or h == 0.0 or (last and self.lower_order_final and S < 15)
+            if first_order:
+                B, C = k, 0.0
+            else:
+                a_s1, s_s1 = self._alpha_sigma(self.sigmas[i - 1])
+                r0 = (lam(a_s0, s_s0) - lam(a_s1, s_s1)) / h
+                B, C = k * (1.0 + 0.5 / r0), -k * 0.5 / r0
+            out.append((int(t), (float(P), float(Q)), (float(A), float(B), float(C))))
+        return out
+
+
+@torch.no_grad()
+def dpms_sample(eps_model: EpsModel, z_T: torch.Tensor, ctx_text: torch.Tensor, schedule: DPMSolverSchedule, *,
+                ctx_uncond: Optional[torch.Tensor] = None, guidance_scale: float = 7.5) -> torch.Tensor:
+    """G1 with DPM-Solver++ 2M: `ddim_sample` with the multistep update -- one `gsw_dpm_step[_cfg]` launch per step, in place on x and on ONE buffer of
+    x0 predictions (this step's prediction overwrites the previous one as it is consumed)."""
+    steps = schedule.steps()
+    tt = _t_tensors([s[0] for s in steps], z_T.device)
+    x = z_T.clone()
+    m = torch.empty_like(x)
+    use_cfg = guidance_scale != 1.0 and ctx_uncond is not None
+    ctx2 = _cfg_contexts(ctx_uncond, ctx_text) if use_cfg else None
+    B = x.shape[0]
+    dup = bool(getattr(eps_model, "supports_cfg_dup", False))      # (see ddim_sample)
+    for (t, pq, abc), t_dev in zip(steps, tt):
+        m_prev = m if abc[2] != 0.0 else None
+        if use_cfg:
+            out = eps_model(x, t_dev, ctx2, cfg_dup=True) if dup else eps_model(torch.cat([x, x], dim=0), t_dev, ctx2)
+            codec.dpm_step_cfg(x, out[:B], out[B:], pq, abc, guidance_scale, m_prev, out=x, m_out=m)
+        else:
+            codec.dpm_step(x, eps_model(x, t_dev, ctx_text), pq, abc, m_prev, out=x, m_out=m)
     return x

@@ -1,4 +1,4 @@
-"""End-to-end Gaussian-Shading path on one GPU: embed -> (G1) DDIM sampling -> (X2) DDIM inversion -> (X3-X5) extract,
+"""End-to-end Gaussian-Shading path on one GPU: embed -> (G1) DDIM or DPM-Solver++ 2M sampling -> (X2) DDIM inversion -> (X3-X5) extract,
 everything resident on the device.
 
 Replaces, for the hot path, the reference's per-image flow (extract.py:46-117: `from_pretrained` per image, `.cpu()` of the
@@ -13,13 +13,18 @@ from typing import Optional
 import torch
 
 from . import codec
-from .ddim import DDIMSchedule, ddim_invert_extract, ddim_sample, ddim_invert
+from .ddim import DDIMSchedule, DPMSolverSchedule, ddim_invert_extract, ddim_sample, ddim_invert, dpms_sample
+
+SAMPLERS = ("ddim", "dpmpp_2m", "dpmpp_2m_karras")
 
 
 class GaussianShadingPipeline:
     def __init__(self, eps_model, key: bytes, nonce: bytes, message: bytes, *, height: int = 512, width: int = 512,
                  num_inference_steps: int = 50, dtype: torch.dtype = torch.float16, device="cuda",
-                 ctx_uncond: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", l: int = 1):
+                 ctx_uncond: Optional[torch.Tensor] = None, prediction_type: str = "epsilon", l: int = 1,
+                 sampler: str = "ddim", num_sampling_steps: Optional[int] = None):
+        if sampler not in SAMPLERS:
+            raise ValueError(f"unknown sampler {sampler!r}: expected one of " + ", ".join(repr(s) for s in SAMPLERS))
         if hasattr(eps_model, "prepare_context"):          # a unet.UNet2DCondition: small batches replay a captured HIP graph of the forward (graph.py)
             from .graph import graphed
             eps_model = graphed(eps_model, clone_output=False)      # the loops of ddim.py consume eps in the scheduler-step kernel right away
@@ -27,7 +32,15 @@ class GaussianShadingPipeline:
         self.key, self.nonce, self.message = key, nonce, message
         self.shape = (4, height // 8, width // 8)
         self.dtype, self.device = dtype, torch.device(device)
-        self.schedule = DDIMSchedule(num_inference_steps=num_inference_steps, prediction_type=prediction_type)
+        self.schedule = DDIMSchedule(num_inference_steps=num_inference_steps, prediction_type=prediction_type)      # inversion / extraction: always DDIM
+        # generation: the chosen sampler; None steps = num_inference_steps for DDIM (the same schedule object as before), 20 for DPM-Solver++ 2M
+        self.sampler = sampler
+        if sampler == "ddim":
+            self.sampling_schedule = self.schedule if num_sampling_steps in (None, num_inference_steps) else \
+                DDIMSchedule(num_inference_steps=num_sampling_steps, prediction_type=prediction_type)
+        else:
+            self.sampling_schedule = DPMSolverSchedule(num_inference_steps=20 if num_sampling_steps is None else num_sampling_steps,
+                                                       prediction_type=prediction_type, use_karras_sigmas=sampler == "dpmpp_2m_karras")
         self.ctx_uncond = ctx_uncond
         self.message_length = 8 * len(message)
         self.l = codec.check_window(l)                      # cipher bits per lattice element, a property of the deployment like the key
@@ -50,7 +63,8 @@ class GaussianShadingPipeline:
 
     def generate(self, z_T: torch.Tensor, ctx_text: torch.Tensor, guidance_scale: float = 7.5) -> torch.Tensor:
         cu = self._uncond(z_T.shape[0]) if guidance_scale != 1.0 else None
-        return ddim_sample(self.eps_model, z_T, ctx_text, self.schedule, ctx_uncond=cu, guidance_scale=guidance_scale)
+        sample = ddim_sample if self.sampler == "ddim" else dpms_sample
+        return sample(self.eps_model, z_T, ctx_text, self.sampling_schedule, ctx_uncond=cu, guidance_scale=guidance_scale)
 
     # X2 + X3-X5 (prompt "" -> the unconditional context, guidance 1: extract.py:66-69)
     def invert_and_extract(self, x0: torch.Tensor, *, return_latents: bool = False):

@@ -121,6 +121,16 @@ int gsw_ddim_step(const void* x_dev, const void* model_out_dev, void* out_dev, f
 int gsw_ddim_step_cfg(const void* x_dev, const void* e_uncond_dev, const void* e_text_dev, void* out_dev, float a,
                       float b, float guidance, int dtype, int64_t n, void* stream);
 
+/* G1 / X2 -- one whole DPM-Solver++ multistep (2M, data prediction, midpoint) scheduler step, sampling or inversion:
+ *   e  = e_text ? e_uncond + g * (e_text - e_uncond) : e_uncond
+ *   m0 = P * x + Q * e                     (the x0 prediction, rounded to `dtype` exactly as gsw_ddim_step[_cfg] rounds it)
+ *   x' = A * x + B * m0 + C * m_prev       (m0 as stored; the C term only when m_prev is given and C != 0)
+ * fp32 math, coefficients precomputed per step on the host in fp64; x' -> x_out_dev, m0 -> m_out_dev.  x_out_dev may alias x_dev,
+ * m_out_dev may alias m_prev_dev.  m_prev_dev is not read when C == 0.  GSW_ERR_BAD_ARG for m_prev_dev == NULL with C != 0. */
+int gsw_dpm_step(const void* x_dev, const void* e_uncond_dev, const void* e_text_dev /* NULL: no guidance */,
+                 const void* m_prev_dev /* NULL: first order */, void* x_out_dev, void* m_out_dev, float P, float Q, float A,
+                 float B, float C, float guidance, int dtype, int64_t n, void* stream);
+
 /* Last inversion step fused with the extract tail: z = a * x + b * model_out is voted on directly (and stored to
  * z_out_dev when non-NULL, in `dtype`, after the same rounding an unfused gsw_ddim_step would apply). */
 int gsw_ddim_step_extract(const void* x_dev, const void* model_out_dev, void* z_out_dev, float a, float b, int dtype,

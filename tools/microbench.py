@@ -30,6 +30,10 @@ for B in (64, 1024, 4096, 16384, 65536):
     x = torch.randn(B, N, device="cuda", dtype=torch.float16); e = torch.randn_like(x); o = torch.empty_like(x)
     row(f"ddim_step f16 B={B}", timeit(lambda: codec.ddim_step(x, e, 1.01, -0.02, out=o)), 3 * 2 * B * N)
     row(f"torch copy_ f16 B={B}", timeit(lambda: o.copy_(x)), 2 * 2 * B * N)
+    # the whole DPM-Solver++ 2M step with guidance, second order, in place: x, e_uncond, e_text, m_prev in, x', m0 out = 6 streams
+    t = torch.randn_like(x); m = torch.randn_like(x); xs = x.clone()
+    row(f"dpm_step f16 cfg order2 B={B}", timeit(lambda: codec.dpm_step_cfg(xs, e, t, (1.01, -0.02), (0.9, 0.15, -0.05), 7.5, m, out=xs, m_out=m)), 6 * 2 * B * N)
+    del t, m, xs
 for B in (4096, 16384, 65536):
     for dt in (torch.float16, torch.float32):
         if a.only and a.only not in "extract": break
