@@ -362,6 +362,83 @@ def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, ms
     return idx, score
 
 
+# ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)
+TILES = (8, 16, 32)             # supported tile edges, in lattice elements
+
+
+def _tiled_operands(packed: torch.Tensor, keys: torch.Tensor, msg_bits: int, shape: Sequence[int], l: int, tile: int):
+    """The checks `tile_agreement` and `vote_tiled` share -> (B, C, h, w, l, tile, msg_bits, th, tw)"""
+    l = check_window(l)
+    if isinstance(tile, bool) or not isinstance(tile, (int, np.integer)) or int(tile) not in TILES:
+        raise ValueError(f"tile must be one of {TILES} (lattice elements per tile edge), got {tile!r}")
+    tile, M = int(tile), int(msg_bits)
+    if len(shape) != 3 or any(int(s) < 1 for s in shape):
+        raise ValueError(f"shape must be the (C, h, w) of one image's lattice, got {tuple(shape)!r}")
+    C, h, w = (int(s) for s in shape)
+    if h % tile or w % tile:
+        raise ValueError(f"a {h} x {w} lattice is not a whole number of {tile} x {tile} tiles")
+    if M < 8 or M % 8:
+        raise ValueError(f"msg_bits must be a positive multiple of 8, got {M}")
+    _need_gpu(packed, "packed")
+    _need_gpu(keys, "keys")
+    if packed.dtype != torch.uint8 or packed.dim() != 2:
+        raise ValueError("packed must be uint8 [B, n * l / 8] (`quant_pack`)")
+    B = packed.shape[0]
+    if B < 1:
+        raise ValueError("packed holds no image")
+    if packed.shape[1] * 8 != C * h * w * l:
+        raise ValueError(f"packed rows hold {packed.shape[1] * 8} bits, a {C} x {h} x {w} lattice at l = {l} has {C * h * w * l}")
+    if keys.dtype != torch.uint8 or tuple(keys.shape) != (B, KEYED_RECORD_HEAD):
+        raise ValueError(f"keys must be uint8 [{B}, {KEYED_RECORD_HEAD}]: key[32] | nonce16[16] per image")
+    if keys.device != packed.device:
+        raise RuntimeError(f"keys lives on {keys.device}, expected {packed.device}")
+    return B, C, h, w, l, tile, M, h // tile, w // tile
+
+
+def tile_agreement(packed: torch.Tensor, keys: torch.Tensor, messages: torch.Tensor, msg_bits: int, shape: Sequence[int], l: int = 1,
+                   tile: int = 8) -> torch.Tensor:
+    """Per tile, how many of an image's quantised bits equal the codeword of a message: int32 [B, h / tile, w / tile].
+
+    packed: uint8 [B, n l / 8] (`quant_pack(z, l)`), keys: uint8 [B, 48] rows key[32] | nonce16[16], one PER IMAGE, messages: uint8
+    [B, msg_bits / 8] MSB first, shape: the (C, h, w) of the lattice.  Tile (ty, tx) holds the elements of all C channels with
+    y // tile == ty and x // tile == tx, n_t = C tile^2 l bits; the codeword is what `embed_batch` plants for that key, nonce and message.
+    One launch; the keystreams are generated inside it.  Raises IndexError when n l is not a multiple of msg_bits (as `extract_batch`
+    does), ValueError for a tile outside (8, 16, 32), a lattice that is not whole tiles or an l outside (1, 2, 4)."""
+    B, C, h, w, l, tile, M, th, tw = _tiled_operands(packed, keys, msg_bits, shape, l, tile)
+    _need_gpu(messages, "messages")
+    if messages.dtype != torch.uint8 or tuple(messages.shape) != (B, M // 8):
+        raise ValueError(f"messages must be uint8 [{B}, {M // 8}]")
+    if messages.device != packed.device:
+        raise RuntimeError(f"messages lives on {messages.device}, expected {packed.device}")
+    agree = torch.empty((B, th, tw), dtype=torch.int32, device=packed.device)
+    with torch.cuda.device(packed.device):
+        N.check(N.lib().gsw_tile_agree(packed.data_ptr(), B, C, h, w, l, tile, keys.data_ptr(), messages.data_ptr(), M, agree.data_ptr(), _stream_ptr()))
+    return agree
+
+
+def vote_tiled(packed: torch.Tensor, keys: torch.Tensor, weights: torch.Tensor, msg_bits: int, shape: Sequence[int], l: int = 1,
+               tile: int = 8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The majority vote with one weight per tile: (bits uint8 [B, msg_bits / 8] MSB first, score int32 [B, msg_bits], wsum int32 [B, msg_bits]).
+
+    Operands as `tile_agreement`; weights: uint16 [B, h / tile, w / tile].  With p_j the decrypted bit j of the image,
+    score[t] = sum over j = t (mod msg_bits) of weight[tile of element j // l] (2 p_j - 1), wsum[t] the same sum of the weights, and
+    bit t = score[t] > 0 (a tie, or no weight at all, gives 0).  Unit weights give `extract_batch`'s bits and score = 2 counts - copies.
+    Raises IndexError / ValueError as `tile_agreement`."""
+    B, C, h, w, l, tile, M, th, tw = _tiled_operands(packed, keys, msg_bits, shape, l, tile)
+    _need_gpu(weights, "weights")
+    if weights.dtype != torch.uint16 or tuple(weights.shape) != (B, th, tw):
+        raise ValueError(f"weights must be uint16 [{B}, {th}, {tw}]")
+    if weights.device != packed.device:
+        raise RuntimeError(f"weights lives on {weights.device}, expected {packed.device}")
+    bits = torch.empty((B, M // 8), dtype=torch.uint8, device=packed.device)
+    score = torch.empty((B, M), dtype=torch.int32, device=packed.device)
+    wsum = torch.empty((B, M), dtype=torch.int32, device=packed.device)
+    with torch.cuda.device(packed.device):
+        N.check(N.lib().gsw_vote_tiled(packed.data_ptr(), B, C, h, w, l, tile, keys.data_ptr(), weights.data_ptr(), M, bits.data_ptr(),
+                                       score.data_ptr(), wsum.data_ptr(), _stream_ptr()))
+    return bits, score, wsum
+
+
 # ------------------------------------------------------------------------------------------------ X2 / G1 elementwise
 def ddim_step(x: torch.Tensor, model_out: torch.Tensor, a: float, b: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = a*x + b*model_out (fp32 math, one rounding). out may be x (in place)."""

@@ -40,6 +40,25 @@ def _window(args) -> int:
     return codec.check_window(l)
 
 
+def _vote(z, args, m: int, l: int):
+    """(bits, flags) of the reference's vote, or with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations)"""
+    if int(getattr(args, "robust", 0) or 0):
+        from . import tamper
+        return tamper.extract_robust(z, args.key, args.nonce, m, l=l, tile=int(getattr(args, "tile", 8)))[:2]
+    return codec.extract_batch(z, args.key, args.nonce, m, l=l)
+
+
+def write_tamper_maps(latents, files, args) -> None:
+    """--tamper_map DIR: the map of every image against --original_message_hex (a message known independently of the image), written as
+    DIR/<image>.tamper.npy / .tamper.png; an image whose latents the reference rejects writes nothing (its error is the vote's to report)."""
+    from . import tamper
+    maps = tamper.tamper_map(latents, args.key, args.nonce, bytes.fromhex(args.original_message_hex), l=_window(args), tile=int(args.tile),
+                             message_length=int(args.message_length))
+    for f, tm in zip(files, maps):
+        if not isinstance(tm, Exception):
+            tamper.save_map(tm, tamper.map_stem(args.tamper_map, f), (args.width, args.height))
+
+
 def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     """extract.py:72-101 -> str of message_length '0'/'1' characters.
 
@@ -49,7 +68,12 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     l = _window(args)
     z = _to_device_latents(reversed_latents, device)
     m = int(args.message_length)
-    bits, flags = codec.extract_batch(z, args.key, args.nonce, m, l=l)
+    if int(getattr(args, "robust", 0) or 0):                 # the tiles are cut from the lattice: the weighted vote needs the image's [C, h, w]
+        shape = tuple(int(d) for d in np.shape(reversed_latents))
+        if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
+            raise ValueError(f"--robust 1 needs the latents of ONE image as [..., C, h, w] (got {shape})")
+        z = z.view(1, *shape[-3:])
+    bits, flags = _vote(z, args, m, l)
     f = int(flags[0].item())
     if f & N.GSW_FLAG_NAN:
         raise ValueError("cannot convert float NaN to integer")
@@ -63,7 +87,7 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
     Mirrors the per-image try/except of extract.py:148-155."""
     l = _window(args)
     m = int(args.message_length)
-    bits, flags = codec.extract_batch(latents.contiguous(), args.key, args.nonce, m, l=l)
+    bits, flags = _vote(latents.contiguous(), args, m, l)
     bits_h, flags_h = bits.cpu().numpy(), flags.cpu().numpy()
     out = []
     for b in range(bits_h.shape[0]):
@@ -325,6 +349,8 @@ def get_result_for_one_image(args):
         load_models(args.model_id, allow_synthetic=_synthetic_allowed(args))
         print(f"{SYNTHETIC_MARKER}: '{args.model_id}' is not a local checkpoint, the bit accuracy below is not meaningful", file=sys.stderr)
     reversed_latents = exactract_latents_batch([args.single_image_path], args)
+    if getattr(args, "tamper_map", None):
+        write_tamper_maps(reversed_latents, [args.single_image_path], args)
     extracted_message_bin = recover_exactracted_message(reversed_latents, args)
     original_message_bin, bit_accuracy = calculate_bit_accuracy(args.original_message_hex, extracted_message_bin)
     print(f"{os.path.basename(args.single_image_path)}\nOriginal Message: {original_message_bin} \nExtracted Message: {extracted_message_bin}\nBit Accuracy: {bit_accuracy}\n")
@@ -390,6 +416,8 @@ def _recover_items(items, args, batch_size, pool=None):
 
     def run(idx):
         latents = invert_decoded_images([decoded[i] for i in idx], args)
+        if getattr(args, "tamper_map", None):
+            write_tamper_maps(latents, [items[i] for i in idx], args)
         return recover_exactracted_message_batch(latents, args)
 
     for k in range(0, len(ready), batch_size):
@@ -575,6 +603,12 @@ def build_parser():
                                                            "one process per GPU, started here unless a launcher (torch.distributed.run) already did")
     parser.add_argument("--preflight", action="store_true", help="(not a reference flag) only check the multi-GPU control plane: per rank device check, RCCL init, one "
                                                                  "broadcast + all_gather_into_tensor + all_reduce under a hard time limit; exit 0 / 3")
+    parser.add_argument("--robust", type=int, choices=[0, 1], default=0,
+                        help="(not a reference flag) 1: decode with the tile-weighted vote (tamper.extract_robust): tiles that do not agree with the decoded "
+                             "message lose their say; 0: the reference's vote")
+    parser.add_argument("--tamper_map", default=None, metavar="DIR",
+                        help="(not a reference flag) write DIR/<image>.tamper.npy / .tamper.png: per tile, the bits that agree with --original_message_hex")
+    parser.add_argument("--tile", type=int, default=8, choices=codec.TILES, help="(not a reference flag) tile edge of --robust / --tamper_map, in lattice elements")
     parser.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                         help="(not a reference flag) 1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning "
                              "(default: 1; 0 opts into the library kernels, counted and warned about once per reason)")

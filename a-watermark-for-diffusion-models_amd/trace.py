@@ -28,6 +28,10 @@ e = keystream(key, nonce) XOR (message repeated), the cipher bits the embed plan
 quantised and packed once (`codec.sign_pack`) and one launch (`codec.trace_keyed_topk`) generates every record's keystream in
 registers.  For records that share one key s IS the soft score above; under the null model s = 2 X - n, X ~ Bin(n, 1/2) exactly for
 any fixed record and any key, so `log10_p_soft` and the Bonferroni bound carry over.  Only the soft statistic exists across keys.
+
+Where (`tamper_tile=`, `--tamper_map DIR`): an attributed image can also be asked WHERE it still carries the record's watermark --
+`TraceResult.tamper`, the per-tile agreement with the attributed record's codeword (`tamper.TamperMap`, one `codec.tile_agreement` launch more
+per batch).  The record comes from the registry, not from the image, so each tile's count has the exact binomial null as well.
 """
 from __future__ import annotations
 
@@ -514,15 +518,38 @@ class Candidate:
 class TraceResult:
     candidates: List[Candidate] = field(default_factory=list)
     attributed: Optional[str] = None       # the best candidate's user id if its bound is <= log10(fpr), else None: no registered user
+    tamper: Optional["TamperMap"] = None   # tamper.TamperMap against the attributed record (tamper_tile=...): where the image still carries it
+
+
+def _attach_tamper_maps(out, z, packed, records, M: int, l: int, tile: int, fpr: float) -> None:
+    """Fill `TraceResult.tamper` of every attributed image: one `codec.tile_agreement` launch over the batch, each image against the
+    (key, nonce, message) of its own best candidate (records[b]; None for an image that was not attributed, whose row is ignored).
+    The message comes from the registry, not from the image, so the counts are Bin(n_t, 1/2) under the null: source "registry"."""
+    from . import tamper as TM
+    if z.dim() != 4:
+        raise ValueError(f"tamper_tile needs latents [B, C, h, w] (got {tuple(z.shape)}): the tiles are cut from the last two dimensions")
+    todo = [b for b, r in enumerate(records) if r is not None]
+    if not todo:
+        return
+    shape = tuple(int(s) for s in z.shape[1:])
+    blank = (bytes(32), bytes(16), bytes(M // 8))
+    rows = [r if r is not None else blank for r in records]
+    agree = codec.tile_agreement(packed, TM.keys_tensor([(k, n) for k, n, _ in rows], z.device), TM._message_rows([m for _, _, m in rows], M, z.device),
+                                 M, shape, l, tile).cpu().numpy()
+    n_t = shape[0] * int(tile) * int(tile) * codec.check_window(l)
+    for b in todo:
+        out[b].tamper = TM.make_map(agree[b], n_t, tile, fpr, "registry")
 
 
 def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, message_length: Optional[int] = None, k: int = 1,
-                  fpr: float = 1e-6, soft: bool = True, l: int = 1) -> List[Union[TraceResult, ValueError]]:
+                  fpr: float = 1e-6, soft: bool = True, l: int = 1, tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
     """latents [B, ...] on the device -> one TraceResult per image (best candidate first), or the ValueError the reference raises for
     that image (a saturated / NaN latent, extract.py:84-86), like `extract.recover_exactracted_message_batch`.
 
     One vote kernel, one search launch over the packed registry; the host receives the B k pairs (plus the vote's flags and bits).
-    l: cipher bits per lattice element the images were embedded with (a property of the deployment, like the key)."""
+    l: cipher bits per lattice element the images were embedded with (a property of the deployment, like the key).
+    tamper_tile: 8, 16 or 32 -> every attributed image also gets `TraceResult.tamper`, the per-tile agreement with its best candidate's
+    codeword (one quantise-and-pack and one `codec.tile_agreement` launch more per batch); None: nothing more runs."""
     import torch
     from . import _native as N
     if not 0.0 < float(fpr) <= 1.0:
@@ -558,10 +585,15 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
         if res.candidates and res.candidates[0].log10_p_any <= limit:
             res.attributed = res.candidates[0].user_id
         out.append(res)
+    if tamper_tile is not None:
+        best = [(key, nonce, bytes(rows[r.candidates[0].index])) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
+        if any(r is not None for r in best):
+            _attach_tamper_maps(out, z, codec.quant_pack(z, l)[0], best, M, l, tamper_tile, fpr)
     return out
 
 
-def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: float = 1e-6, l: int = 1) -> List[Union[TraceResult, ValueError]]:
+def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: float = 1e-6, l: int = 1,
+                        tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
     """`trace_latents` against a registry whose records carry their own keys: latents [B, ...] on the device -> one TraceResult per
     image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
 
@@ -569,7 +601,8 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     receives the B k (index, score) pairs and the flags.  score = n - 2 popcount(signs ^ codeword), whose null distribution is that of
     the soft score (`log10_p_soft(score, n)`), Bonferroni over the records.  `Candidate.agree` is the reference's voted-bit agreement
     under that candidate's own key: `codec.extract_batch` + `codec.bit_matches` for the reported candidates only, grouped by key.
-    l: cipher bits per lattice element; the codewords then span n l bits."""
+    l: cipher bits per lattice element; the codewords then span n l bits.
+    tamper_tile: as in `trace_latents`; the map of an image is taken under its best candidate's OWN key (one launch more per batch)."""
     import torch
     from . import _native as N
     if not 0.0 < float(fpr) <= 1.0:
@@ -616,6 +649,9 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
             agree = codec.bit_matches(bits, M, msg).cpu().numpy()
             for b, c in pairs_:
                 c.agree = int(agree[row[b]])
+    if tamper_tile is not None:
+        best = [registry.record_at(r.candidates[0].index) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
+        _attach_tamper_maps(out, z, signs, best, M, l, tamper_tile, fpr)
     return out
 
 
@@ -630,6 +666,8 @@ def format_line(name: str, result, message_length: int) -> str:
     text = f"{name}, user: {result.attributed if result.attributed is not None else 'none'}, agreement, {c.agree / message_length}, log10 p, {c.log10_p_any:.3f}"
     for o in result.candidates[1:]:
         text += f", next: {o.user_id} ({o.agree / message_length}, {o.log10_p_any:.3f})"
+    if result.tamper is not None:
+        text += f", intact tiles {result.tamper.n_intact}/{result.tamper.n_tiles}"
     return text
 
 
@@ -676,6 +714,10 @@ def build_parser():
     p.add_argument("--l", type=int, default=1, choices=codec.WINDOWS, help="cipher bits per lattice element the images were embedded with")
     p.add_argument("--allow_synthetic_weights", action="store_true", help="run without a checkpoint (pipeline tests / benchmarks only)")
     p.add_argument("--batch_size", type=int, default=16, help="images per device batch")
+    p.add_argument("--tamper_map", default=None, metavar="DIR",
+                   help="for every attributed image write DIR/<image>.tamper.npy (agreeing bits per tile with the attributed record's codeword) and "
+                        "DIR/<image>.tamper.png (255 where the watermark's presence in the tile is proven at --fpr over the map), and report the intact tiles")
+    p.add_argument("--tile", type=int, default=8, choices=codec.TILES, help="tile edge of --tamper_map, in lattice elements (one element = 8 x 8 pixels)")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
     return p
@@ -695,10 +737,11 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
 
     def run(arrs):
         latents = X.invert_decoded_images(arrs, args)
+        tile = args.tile if getattr(args, "tamper_map", None) else None
         if args.per_record_keys:
-            return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr, l=args.l)
+            return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr, l=args.l, tamper_tile=tile)
         return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard,
-                             l=args.l)
+                             l=args.l, tamper_tile=tile)
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         decoded = list(pool.map(decode, files))
@@ -717,6 +760,11 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
                     results.append(e)
         for i, r in zip(idx, results):
             out[i] = r
+    if getattr(args, "tamper_map", None):
+        from . import tamper as TM
+        for f, r in zip(files, out):
+            if isinstance(r, TraceResult) and r.tamper is not None:
+                TM.save_map(r.tamper, TM.map_stem(args.tamper_map, f), (args.width, args.height))
     return out
 
 

@@ -581,6 +581,31 @@ int gsw_extract_l(const void* z_dev, int z_dtype, const uint8_t key[32], const u
                   uint32_t* counts_dev, uint32_t* flags_dev, int B, int64_t n_elems, int l, void* stream);
 int gsw_quant_pack(const void* z_dev, int z_dtype, uint8_t* packed_dev, uint32_t* flags_dev, int B, int64_t n_elems, int l, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Localising edits: where an image still agrees with a codeword, and a vote weighted by tile.
+ * Additive: gsw_version() stays 500.
+ *
+ *   packed_dev : [B, Nb / 8], the rows gsw_sign_pack / gsw_quant_pack write for the [C, h, w] lattice, Nb = C h w l; element i = (c, y, x)
+ *                in C order owns bits [i l, i l + l), MSB first; 4-byte aligned
+ *   keys_dev   : [B, 48], key[32] | nonce16[16] PER IMAGE (4-byte aligned); the keystream is gsw_keystream's (initial counter, carry), generated
+ *                in registers: no keystream and no codeword is stored
+ *   tile       : T in {8, 16, 32}; tile (ty, tx) holds the elements of ALL C channels with y / T == ty and x / T == tx: n_t = C T T l bits
+ *   gsw_tile_agree : agree[b, ty, tx] = number of bits j of the tile with q_j == cw_j, cw_j = ks_j ^ msg[b][j mod msg_bits] (the cipher bits
+ *                gsw_embed[_l] plants for that message); msg_dev [B, msg_bits / 8], MSB first.  For a tile whose content is independent of the key
+ *                and a message fixed independently of the image, agree ~ Bin(n_t, 1/2) exactly.
+ *   gsw_vote_tiled : with p_j = q_j ^ ks_j and uint16 weights [B, h / T, w / T],
+ *                score[b, t] = sum over j = t (mod msg_bits) of wgt[tile(j / l)] (2 p_j - 1),  wsum[b, t] = the same sum of wgt alone,
+ *                bits MSB first with bit t = (score > 0): a tie or no weight at all gives 0, gsw_extract's tie rule.  With every weight 1,
+ *                score = 2 counts - copies of gsw_extract[_l] and the bits are its bits.
+ * Every output element is written; the results are exact integers and do not depend on the launch geometry.
+ * GSW_ERR_BAD_ARG: null pointer, misaligned packed_dev / keys_dev / weights_dev, B < 1, non-positive C, h, w or msg_bits, l outside {1, 2, 4}.
+ * GSW_ERR_UNSUPPORTED: tile outside {8, 16, 32}, h or w not a multiple of tile, msg_bits % 8 != 0, Nb > 1 048 576 (one image's row is staged in
+ * 128 KiB of LDS); gsw_vote_tiled also when (Nb / msg_bits) * 65535 does not fit int32.  GSW_ERR_RAGGED: Nb % msg_bits != 0. */
+int gsw_tile_agree(const uint8_t* packed_dev, int B, int C, int h, int w, int l, int tile, const uint8_t* keys_dev, const uint8_t* msg_dev,
+                   int msg_bits, int32_t* agree_dev, void* stream);
+int gsw_vote_tiled(const uint8_t* packed_dev, int B, int C, int h, int w, int l, int tile, const uint8_t* keys_dev, const uint16_t* weights_dev,
+                   int msg_bits, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
