@@ -141,6 +141,10 @@ _PROTOTYPES = {
     "gsw_tile_agree": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gsw_vote_tiled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
+    "gsw_embed_keyed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+                                  C.c_uint32, C.c_int, C.c_void_p]),
+    "gsw_extract_keyed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_int, C.c_int64, C.c_int, C.c_void_p]),
 }
 
 _lib = None

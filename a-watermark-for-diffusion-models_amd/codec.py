@@ -362,8 +362,94 @@ def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, ms
     return idx, score
 
 
+# ------------------------------------------------------------------------------------------------ issuing (one record per image)
+def _records_operand(records: torch.Tensor, msg_bytes: int) -> Tuple[int, int, int]:
+    """The checks `embed_records` and `extract_records` share -> (B, stride, msg_bytes)"""
+    _need_gpu(records, "records")
+    if records.dtype != torch.uint8 or records.dim() != 2:
+        raise ValueError("records must be uint8 [B, stride] (`trace.KeyedRegistry.packed` rows)")
+    B, stride = records.shape[0], records.shape[1]
+    if B < 1:
+        raise ValueError("records holds no row")
+    if isinstance(msg_bytes, bool) or not isinstance(msg_bytes, (int, np.integer)) or not 1 <= int(msg_bytes) <= N.GSW_MSG_INLINE_MAX:
+        raise ValueError(f"msg_bytes {msg_bytes!r} is outside 1..{N.GSW_MSG_INLINE_MAX}")
+    msg_bytes = int(msg_bytes)
+    if stride < KEYED_RECORD_HEAD + msg_bytes or stride % 16:
+        raise ValueError(f"record rows of {stride} bytes cannot hold key | nonce | {msg_bytes}-byte message at a multiple of 16")
+    return B, stride, msg_bytes
+
+
+def embed_records(records: torch.Tensor, msg_bytes: int, shape: Sequence[int], *, u: Optional[torch.Tensor] = None, seed: int = 0,
+                  image_index0: int = 0, dtype: torch.dtype = torch.float32, fast: bool = False, out: Optional[torch.Tensor] = None,
+                  l: int = 1) -> torch.Tensor:
+    """Watermarked initial latents [B, *shape], image b under its OWN record, in one launch.
+
+    records: uint8 [B, stride] on the device, a row is key[32] | nonce16[16] | message[msg_bytes] (`trace.KeyedRegistry.packed` rows as
+    they are; stride >= 48 + msg_bytes, a multiple of 16).  Row b of the result is bit for bit
+    `embed_batch(key_b, nonce_b, msg_b, 1, shape, u=u[b:b+1], seed=seed, image_index0=image_index0 + b, dtype=dtype, fast=fast, l=l)`;
+    u, seed, fast, out and l as there."""
+    B, stride, msg_bytes = _records_operand(records, msg_bytes)
+    l = check_window(l)
+    n = 1
+    for s in shape:
+        n *= int(s)
+    if n < 4 or n % 4:
+        raise ValueError(f"the lattice must hold a positive multiple of 4 elements per image (got {n})")
+    if out is None:
+        out = torch.empty((B, *shape), dtype=dtype, device=records.device)
+    elif out.numel() != B * n:
+        raise ValueError("out has the wrong size")
+    _need_gpu(out, "out")
+    if out.device != records.device:
+        raise RuntimeError(f"out lives on {out.device}, expected {records.device}")
+    u_ptr = None
+    if u is not None:
+        _need_gpu(u, "u")
+        if u.device != records.device:
+            raise RuntimeError(f"u lives on {u.device}, expected {records.device}")
+        if u.dtype != torch.float64 or u.numel() != B * n:
+            raise ValueError("u must be float64 with batch*n_elems entries")
+        u_ptr = u.data_ptr()
+    mode = N.GSW_EMBED_FAST_F32 if fast else N.GSW_EMBED_EXACT_F64
+    with torch.cuda.device(out.device):
+        N.check(N.lib().gsw_embed_keyed(records.data_ptr(), stride, msg_bytes, u_ptr, seed & (2**64 - 1), image_index0, out.data_ptr(),
+                                        _dt(out.dtype), B, n, mode, l, _stream_ptr()))
+    return out
+
+
+def extract_records(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, l: int = 1, return_counts: bool = False):
+    """Recover and verify the message of every image under its OWN record, in one launch.
+
+    z: latents [B, ...] (fp16 / bf16 / fp32 / fp64), records: as `embed_records`, one row per image.  Returns (bits uint8 [B, msg_bytes]
+    MSB first, flags int32 [B], matches int32 [B]) (+ counts int32 [B, 8 msg_bytes]): bits, flags and counts of row b are those of
+    `extract_batch(z[b:b+1], key_b, nonce_b, 8 * msg_bytes, l=l)`, matches[b] is how many of the recovered bits equal record b's
+    message.  The n * l bits of an image must fill whole bytes and number at most 1 048 576 (ValueError otherwise); raises IndexError
+    where `extract_batch` does (n * l is not a multiple of 8 msg_bytes)."""
+    B, stride, msg_bytes = _records_operand(records, msg_bytes)
+    l = check_window(l)
+    _need_gpu(z, "z")
+    if z.device != records.device:
+        raise RuntimeError(f"records lives on {records.device}, expected {z.device}")
+    if z.dim() < 2 or z.shape[0] != B:
+        raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 1 or (n * l) % 8 or n * l > 1048576:
+        raise ValueError(f"a lattice of {n} elements at l = {l} must fill whole bytes and hold at most 1048576 bits")
+    M = 8 * msg_bytes
+    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    matches = torch.empty((B,), dtype=torch.int32, device=z.device)
+    counts = torch.empty((B, M), dtype=torch.int32, device=z.device) if return_counts else None
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_extract_keyed(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, bits.data_ptr(),
+                                          counts.data_ptr() if return_counts else None, flags.data_ptr(), matches.data_ptr(), B, n, l,
+                                          _stream_ptr()))
+    return (bits, flags, matches, counts) if return_counts else (bits, flags, matches)
+
+
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)
-TILES = (8, 16, 32)             # supported tile edges, in lattice elements
+TILES =(8, 16, 32)             # supported tile edges, in lattice elements
 
 
 def _tiled_operands(packed: torch.Tensor, keys: torch.Tensor, msg_bits: int, shape: Sequence[int], l: int, tile: int):

@@ -136,10 +136,65 @@ __device__ __forceinline__ void store_binsafe(OutT* dst, const ZT (&z)[4], const
     }
 }
 
+// The four elements e .. e+3 of image `img`, one thread: uniforms (usrc, or the Philox group of e) -> z -> bin-safe 16-byte store at dst.
+// Element e + k owns bits [l (3 - k), l (4 - k)) of yw.  The body of gsw_embed_l_kernel's image loop, shared with the per-record kernel
+// (gswm_codec_keyed.inc).
 template <typename OutT, int L, bool HAS_U, bool FAST>
-__global__ __launch_bounds__(GSW_WG) void gsw_embed_l_kernel(EmbedArgs p) {
+__device__ __forceinline__ void embed_quad_l(OutT* dst, const double* usrc, uint32_t e, uint64_t img, uint32_t k0, uint32_t k1, uint32_t yw,
+                                             const typename BinOf<OutT>::V* bins /* LDS */) {
     constexpr uint32_t FULL = 1u << L, HALF = FULL / 2u, MASK = FULL - 1u;
     constexpr double INV = 1.0 / (double)FULL, INVH = 1.0 / (double)HALF;
+    double u[4];
+    if (HAS_U) {
+        const double2 ua = reinterpret_cast<const double2*>(usrc)[0];
+        const double2 ub = reinterpret_cast<const double2*>(usrc)[1];
+        u[0] = ua.x; u[1] = ua.y; u[2] = ub.x; u[3] = ub.y;
+    } else {
+        uint32_t w[4];
+        philox4x32<GSW_PHILOX_ROUNDS>(e >> 2, 0u, (uint32_t)img, (uint32_t)(img >> 32), k0, k1, w);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) u[k] = u_from_word(w[k]);
+    }
+    uint32_t y[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = (yw >> (L * (3 - k))) & MASK;
+    if (FAST) {
+        // the tail-side mass, exact in fp64 up to one rounding: p = (u + y) / 2^l below the median, 1 - p = ((2^l - 1 - y) + (1 - u)) / 2^l
+        // above it; v = 2 min(p, 1 - p), x = 1 - v as the l = 1 fast path takes them
+        float v[4], x[4], a[4], zf[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double m = y[k] < HALF ? u[k] + (double)y[k] : (double)(MASK - y[k]) + (1.0 - u[k]);
+            const double vd = m * INVH;
+            v[k] = (float)vd;
+            x[k] = (float)(1.0 - vd);
+        }
+        ndtri_fast_abs4(v, x, a);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) zf[k] = y[k] < HALF ? -a[k] : a[k];
+        // The fp32 tail polynomial was fitted for l = 1, whose argument stops at v = 2^-53; here it reaches 2^-53 / 2^(l-1).
+        // Below 2^-50 (one element in 10^15) the element takes the exact core instead.  Only a supplied u gets there: a Philox
+        // uniform is (w + .5) 2^-32, so v >= 2^-33 / 2^(l-1), and that instantiation carries no fp64 core (and not its registers).
+        if constexpr (HAS_U) {
+            const float vmin = fminf(fminf(v[0], v[1]), fminf(v[2], v[3]));
+            if (!(vmin >= 0x1p-50f)) {
+#pragma unroll 1
+                for (int k = 0; k < 4; ++k)
+                    if (!(v[k] >= 0x1p-50f)) zf[k] = (float)ndtri_cephes((u[k] + (double)y[k]) * INV);
+            }
+        }
+        store_binsafe<OutT, float>(dst, zf, y, bins);
+    } else {
+        double z[4];
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) z[k] = ndtri_cephes((u[k] + (double)y[k]) * INV);
+        store_binsafe<OutT, double>(dst, z, y, bins);
+    }
+}
+
+template <typename OutT, int L, bool HAS_U, bool FAST>
+__global__ __launch_bounds__(GSW_WG) void gsw_embed_l_kernel(EmbedArgs p) {
+    constexpr uint32_t FULL = 1u << L;
     __shared__ uint32_t ks_words[64 * L];  // 4 l blocks x 16 words
     __shared__ typename BinOf<OutT>::V bins[FULL];
     const uint32_t tid = threadIdx.x;
@@ -184,52 +239,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_embed_l_kernel(EmbedArgs p) {
             if (e >= N) continue;
             const size_t off = (size_t)b * N + e;
             OutT* dst = reinterpret_cast<OutT*>(p.out) + off;
-            double u[4];
-            if (HAS_U) {
-                const double2 ua = reinterpret_cast<const double2*>(p.u + off)[0];
-                const double2 ub = reinterpret_cast<const double2*>(p.u + off)[1];
-                u[0] = ua.x; u[1] = ua.y; u[2] = ub.x; u[3] = ub.y;
-            } else {
-                uint32_t w[4];
-                philox4x32<GSW_PHILOX_ROUNDS>(e >> 2, 0u, (uint32_t)img, (uint32_t)(img >> 32), k0, k1, w);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) u[k] = u_from_word(w[k]);
-            }
-            uint32_t y[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = (yw[r] >> (L * (3 - k))) & MASK;
-            if (FAST) {
-                // the tail-side mass, exact in fp64 up to one rounding: p = (u + y) / 2^l below the median, 1 - p = ((2^l - 1 - y) + (1 - u)) / 2^l
-                // above it; v = 2 min(p, 1 - p), x = 1 - v as the l = 1 fast path takes them
-                float v[4], x[4], a[4], zf[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const double m = y[k] < HALF ? u[k] + (double)y[k] : (double)(MASK - y[k]) + (1.0 - u[k]);
-                    const double vd = m * INVH;
-                    v[k] = (float)vd;
-                    x[k] = (float)(1.0 - vd);
-                }
-                ndtri_fast_abs4(v, x, a);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) zf[k] = y[k] < HALF ? -a[k] : a[k];
-                // The fp32 tail polynomial was fitted for l = 1, whose argument stops at v = 2^-53; here it reaches 2^-53 / 2^(l-1).
-                // Below 2^-50 (one element in 10^15) the element takes the exact core instead.  Only a supplied u gets there: a Philox
-                // uniform is (w + .5) 2^-32, so v >= 2^-33 / 2^(l-1), and that instantiation carries no fp64 core (and not its registers).
-                if constexpr (HAS_U) {
-                    const float vmin = fminf(fminf(v[0], v[1]), fminf(v[2], v[3]));
-                    if (!(vmin >= 0x1p-50f)) {
-#pragma unroll 1
-                        for (int k = 0; k < 4; ++k)
-                            if (!(v[k] >= 0x1p-50f)) zf[k] = (float)ndtri_cephes((u[k] + (double)y[k]) * INV);
-                    }
-                }
-                store_binsafe<OutT, float>(dst, zf, y, bins);
-            } else {
-                double z[4];
-#pragma unroll 1
-                for (int k = 0; k < 4; ++k) z[k] = ndtri_cephes((u[k] + (double)y[k]) * INV);
-                store_binsafe<OutT, double>(dst, z, y, bins);
-            }
+            embed_quad_l<OutT, L, HAS_U, FAST>(dst, p.u + off, e, img, k0, k1, yw[r], bins);
         }
     }
 }

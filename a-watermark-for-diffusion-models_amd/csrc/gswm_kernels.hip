@@ -296,6 +296,58 @@ __device__ __forceinline__ uint32_t inline_msg_byte(uint32_t i) {
     return ka[offsetof(EmbedArgs, msg) + i];
 }
 
+// The four elements e .. e+3 of image `img`, one thread: uniforms (usrc, or the Philox group of e) -> z -> one 16-byte store at dst.
+// Bit (3-k) of ynib is the cipher bit of element e + k.  The body of gsw_embed_kernel's image loop, shared with the per-record kernel
+// (gswm_codec_keyed.inc).
+template <typename OutT, bool HAS_U, bool FAST>
+__device__ __forceinline__ void embed_quad(OutT* dst, const double* usrc, uint32_t e, uint64_t img, uint32_t k0, uint32_t k1, uint32_t ynib,
+                                           const float4* icdf /* LDS, FAST && !HAS_U only */) {
+    uint32_t w[4];
+    double u[4];
+    if (HAS_U) {
+        const double2 ua = reinterpret_cast<const double2*>(usrc)[0];
+        const double2 ub = reinterpret_cast<const double2*>(usrc)[1];
+        u[0] = ua.x; u[1] = ua.y; u[2] = ub.x; u[3] = ub.y;
+    } else {
+        philox4x32<GSW_PHILOX_ROUNDS>(e >> 2, 0u, (uint32_t)img, (uint32_t)(img >> 32), k0, k1, w);
+    }
+    if (FAST) {
+        float a[4];
+        if (HAS_U) {
+            float v[4], x[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool one = (ynib >> (3 - k)) & 1u;
+                v[k] = (float)(one ? 1.0 - u[k] : u[k]);   // exact in fp64 for a 53-bit u, then one rounding
+                x[k] = (float)(one ? u[k] : 1.0 - u[k]);
+            }
+            ndtri_fast_abs4(v, x, a);
+        } else {
+            // u = (w + .5) 2^-32  =>  1 - u = (~w + .5) 2^-32: the tail-side uniform is an integer select of the
+            // Philox word, and |z| comes from the table without ever forming u
+            const uint32_t ones = (ynib & 8u ? 1u : 0u) | (ynib & 4u ? 2u : 0u) | (ynib & 2u ? 4u : 0u) | (ynib & 1u ? 8u : 0u);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = icdf_table_abs(((ones >> k) & 1u) ? ~w[k] : w[k], icdf);
+        }
+        float zf[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t neg = ((~ynib >> (3 - k)) & 1u) << 31;   // cipher bit 0 -> negative half
+            zf[k] = __uint_as_float(__float_as_uint(a[k]) | neg);
+        }
+        Vec4Store<OutT>::stf(dst, zf);
+    } else {
+        double z[4];
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+            const double uk = HAS_U ? u[k] : u_from_word(w[k]);
+            const double y = (double)((ynib >> (3 - k)) & 1u);
+            z[k] = ndtri_cephes((uk + y) * 0.5);       // gs_insert.py:64, same operation order
+        }
+        Vec4Store<OutT>::st(dst, z);
+    }
+}
+
 // BITMSG: message length is not a multiple of 8 bits -> plaintext bit looked up per element (generic geometry)
 template <typename OutT, bool HAS_U, bool FAST, bool BITMSG>
 __global__ __launch_bounds__(GSW_WG) void gsw_embed_kernel(EmbedArgs p) {
@@ -357,50 +409,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_embed_kernel(EmbedArgs p) {
             if (e >= N) continue;
             const size_t off = (size_t)b * N + e;
             OutT* dst = reinterpret_cast<OutT*>(p.out) + off;
-            uint32_t w[4];
-            double u[4];
-            if (HAS_U) {
-                const double2 ua = reinterpret_cast<const double2*>(p.u + off)[0];
-                const double2 ub = reinterpret_cast<const double2*>(p.u + off)[1];
-                u[0] = ua.x; u[1] = ua.y; u[2] = ub.x; u[3] = ub.y;
-            } else {
-                philox4x32<GSW_PHILOX_ROUNDS>(e >> 2, 0u, (uint32_t)img, (uint32_t)(img >> 32), k0, k1, w);
-            }
-            if (FAST) {
-                float a[4];
-                if (HAS_U) {
-                    float v[4], x[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const bool one = (ynib[r] >> (3 - k)) & 1u;
-                        v[k] = (float)(one ? 1.0 - u[k] : u[k]);   // exact in fp64 for a 53-bit u, then one rounding
-                        x[k] = (float)(one ? u[k] : 1.0 - u[k]);
-                    }
-                    ndtri_fast_abs4(v, x, a);
-                } else {
-                    // u = (w + .5) 2^-32  =>  1 - u = (~w + .5) 2^-32: the tail-side uniform is an integer select of the
-                    // Philox word, and |z| comes from the table without ever forming u
-                    const uint32_t ones = (ynib[r] & 8u ? 1u : 0u) | (ynib[r] & 4u ? 2u : 0u) | (ynib[r] & 2u ? 4u : 0u) | (ynib[r] & 1u ? 8u : 0u);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) a[k] = icdf_table_abs(((ones >> k) & 1u) ? ~w[k] : w[k], icdf);
-                }
-                float zf[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint32_t neg = ((~ynib[r] >> (3 - k)) & 1u) << 31;   // cipher bit 0 -> negative half
-                    zf[k] = __uint_as_float(__float_as_uint(a[k]) | neg);
-                }
-                Vec4Store<OutT>::stf(dst, zf);
-            } else {
-                double z[4];
-#pragma unroll 1
-                for (int k = 0; k < 4; ++k) {
-                    const double uk = HAS_U ? u[k] : u_from_word(w[k]);
-                    const double y = (double)((ynib[r] >> (3 - k)) & 1u);
-                    z[k] = ndtri_cephes((uk + y) * 0.5);       // gs_insert.py:64, same operation order
-                }
-                Vec4Store<OutT>::st(dst, z);
-            }
+            embed_quad<OutT, HAS_U, FAST>(dst, p.u + off, e, img, k0, k1, ynib[r], icdf);
         }
     }
 }
@@ -1419,6 +1428,18 @@ static int launch_extract_wave(const ExtractArgs& a, const Src& src, size_t lds,
     return GSW_OK;
 }
 
+// gsw_extract votes wave-per-image (gsw_extract_wave_kernel) for these geometries and through the generic kernel otherwise.  The two agree on
+// every element but a NaN, which the wave vote counts by its sign bit (fp64: as 1) and the generic vote as 0; gsw_extract_keyed asks here
+// to count a flagged image's NaNs as gsw_extract does.
+static bool extract_votes_by_wave(uint32_t N, uint32_t M) {
+    const uint32_t nbytes = (N + 7u) / 8u;
+    const uint32_t nblk = (nbytes + 63u) / 64u;
+    const uint32_t Mb = M / 8u;
+    const size_t lds_wave = (size_t)nblk * 64u + (size_t)nbytes * 8u;
+    return (N % 8u == 0) && (M % 8u == 0) && Mb >= 1 && Mb <= 256u && (256u % Mb == 0) && (N % M == 0) &&
+           (N / M <= 65535u) && lds_wave <= GSW_MAX_DYN_LDS;
+}
+
 template <typename Src>
 static int launch_extract(const ExtractArgs& a, const Src& src, hipStream_t st) {
     const uint32_t N = a.n_elems, M = a.msg_bits;
@@ -1426,8 +1447,7 @@ static int launch_extract(const ExtractArgs& a, const Src& src, hipStream_t st) 
     const uint32_t nblk = (nbytes + 63u) / 64u;
     const uint32_t Mb = M / 8u;
     const size_t lds_wave = (size_t)nblk * 64u + (size_t)nbytes * 8u;
-    const bool fast = (N % 8u == 0) && (M % 8u == 0) && Mb >= 1 && Mb <= 256u && (256u % Mb == 0) && (N % M == 0) &&
-                      (N / M <= 65535u) && lds_wave <= GSW_MAX_DYN_LDS;
+    const bool fast = extract_votes_by_wave(N, M);
     if (fast) {
         if (Mb <= 64u) return launch_extract_wave<Src, 1>(a, src, lds_wave, st);
         if (Mb == 128u) return launch_extract_wave<Src, 2>(a, src, lds_wave, st);
@@ -1647,3 +1667,8 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
 // Multi-bit windows (l = 2, 4): gsw_embed_l / gsw_extract_l / gsw_quant_pack, kernels and entry points
 // ------------------------------------------------------------------------------------------------
 #include "gswm_codec_l.inc"
+
+// ------------------------------------------------------------------------------------------------
+// One record per image (every image under its own key, nonce and message): gsw_embed_keyed / gsw_extract_keyed, kernels and entry points
+// ------------------------------------------------------------------------------------------------
+#include "gswm_codec_keyed.inc"

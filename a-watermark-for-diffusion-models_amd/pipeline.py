@@ -50,6 +50,19 @@ class GaussianShadingPipeline:
         return codec.embed_batch(self.key, self.nonce, self.message, batch, self.shape, u=u, seed=seed, image_index0=image_index0,
                                  dtype=self.dtype, fast=fast, device=self.device, l=self.l)
 
+    # E1-E6, one record per image (issue.py): the pipeline's shape, dtype and l, the records' own keys and messages
+    def embed_records(self, records: torch.Tensor, msg_bytes: int, *, seed: int = 0, image_index0: int = 0, fast: bool = True,
+                      u: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return codec.embed_records(records, msg_bytes, self.shape, u=u, seed=seed, image_index0=image_index0, dtype=self.dtype, fast=fast,
+                                   l=self.l)
+
+    # X2 + X3-X5 + X6 against each image's own record
+    def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False):
+        """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`"""
+        z = ddim_invert(self.eps_model, x0, self._uncond(x0.shape[0]), self.schedule)
+        res = codec.extract_records(z, records, msg_bytes, l=self.l)
+        return (*res, z) if return_latents else res
+
     # G1
     def _uncond(self, batch: int) -> torch.Tensor:
         """the empty prompt's context for `batch` images: ONE view object per batch size (the eps model's per-context caches live on the tensor object)"""

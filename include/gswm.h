@@ -606,6 +606,31 @@ int gsw_tile_agree(const uint8_t* packed_dev, int B, int C, int h, int w, int l,
 int gsw_vote_tiled(const uint8_t* packed_dev, int B, int C, int h, int w, int l, int tile, const uint8_t* keys_dev, const uint16_t* weights_dev,
                    int msg_bits, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Per-image records: embed and verify a batch in which every image has its own key, nonce and message.
+ * Additive: gsw_version() stays 500.
+ *
+ *   records_dev : uint8 [B, record_stride], 16-byte aligned, gsw_trace_keyed_topk's rows: key[32] | nonce16[16] | msg[msg_bytes], with
+ *                 record_stride >= 48 + msg_bytes and record_stride % 16 == 0; row b belongs to image b.  msg_bytes is 1..256.
+ *   gsw_embed_keyed   : row b of out_dev is bit for bit what gsw_embed (l == 1) or gsw_embed_l (l == 2, 4) writes when called with record
+ *                 b's key, nonce16 and message, B = 1, image_index0 + b, row b of u_dev (or NULL: Philox, addressed by that global image
+ *                 index) and the same seed, flags (GSW_EMBED_*) and out_dtype.  n_elems % 4 == 0; for l > 1 the rule of gsw_embed_l.
+ *   gsw_extract_keyed : bits_dev [B, msg_bytes], counts_dev [B, 8 msg_bytes] (NULL ok) and flags_dev [B] of row b are exactly those of
+ *                 gsw_extract / gsw_extract_l for that image under record b's key and nonce16 with msg_bits = 8 msg_bytes;
+ *                 matches_dev [B] (NULL ok) = how many of those recovered bits equal record b's message.
+ *                 (That includes the votes of a NaN element in an image flagged GSW_FLAG_NAN: as gsw_extract[_l] counts them for the same geometry.)
+ * One launch each; the keystreams are generated inside it and never stored.  Every output element is written, no atomics, no workspace;
+ * the results do not depend on the launch geometry.
+ * GSW_ERR_BAD_ARG: null pointer (u_dev, counts_dev, matches_dev excepted), B < 1, msg_bytes outside 1..256, a bad stride or alignment of
+ * records_dev, out_dev / u_dev / z_dev not 16-byte aligned, unknown dtype, n_elems < 1 (embed: n_elems % 4 != 0).
+ * GSW_ERR_UNSUPPORTED: l outside {1, 2, 4}; embed: as gsw_embed_l; extract: Nb = n_elems * l not a multiple of 8 or above 1 048 576 (one
+ * image's row is staged in 128 KiB of LDS).  GSW_ERR_RAGGED (extract): Nb % (8 msg_bytes) != 0. */
+int gsw_embed_keyed(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const double* u_dev, uint64_t seed,
+                    uint64_t image_index0, void* out_dev, int out_dtype, int B, int64_t n_elems, uint32_t flags, int l, void* stream);
+int gsw_extract_keyed(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
+                      uint8_t* bits_dev, uint32_t* counts_dev /* NULL ok */, uint32_t* flags_dev, uint32_t* matches_dev /* NULL ok */,
+                      int B, int64_t n_elems, int l, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
