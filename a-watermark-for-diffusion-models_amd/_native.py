@@ -145,6 +145,8 @@ _PROTOTYPES = {
                                   C.c_uint32, C.c_int, C.c_void_p]),
     "gsw_extract_keyed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    "gsw_extract_soft": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
 }
 
 _lib = None

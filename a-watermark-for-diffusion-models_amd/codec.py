@@ -9,7 +9,7 @@ X2/G1 elementwise step -> `ddim_step*`.
 from __future__ import annotations
 
 import os
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -446,6 +446,60 @@ def extract_records(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, l
                                           counts.data_ptr() if return_counts else None, flags.data_ptr(), matches.data_ptr(), B, n, l,
                                           _stream_ptr()))
     return (bits, flags, matches, counts) if return_counts else (bits, flags, matches)
+
+
+# ------------------------------------------------------------------------------------------------ soft-decision vote (reliability levels)
+SOFT_MAX_LEVELS = 15
+
+
+class SoftVote(NamedTuple):
+    """What `extract_soft` returns, all on z's device"""
+    bits: torch.Tensor      # uint8 [B, msg_bytes], MSB first, bit t = (score > 0)
+    flags: torch.Tensor     # int32 [B], GSW_FLAG_*
+    matches: torch.Tensor   # int32 [B], recovered bits equal to the record's message
+    score: torch.Tensor     # int32 [B, 8 msg_bytes], sum of level (2 p - 1) over the copies of a message bit
+    wsum: torch.Tensor      # int32 [B, 8 msg_bytes], the same sum of level alone
+    wsq: torch.Tensor       # int32 [B], sum of level^2 over the image
+
+
+def extract_soft(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresholds: torch.Tensor) -> SoftVote:
+    """The soft-decision vote of every image under its OWN record, in one launch (gsw_extract_soft, l = 1): element j votes for its
+    decrypted bit with the integer weight level_j = #{ i : |z_j| >= thresholds[b][i] }.
+
+    z: latents [B, ...] (fp16 / bf16 / fp32 / fp64), records: as `extract_records`, thresholds: float32 [levels] (one table for all images)
+    or [B, levels] on z's device, levels in 1..15 (`soft.uniform_thresholds`, `soft.llr_thresholds`).  The comparison is exact in every
+    dtype (fp32 after an exact widening; fp64 against the thresholds widened to fp64); a NaN has level 0.  With thresholds = [0] on
+    NaN-free images the bits are `extract_records`' bits and score = 2 counts - copies.  Lattice limits and IndexError as `extract_records`."""
+    B, stride, msg_bytes = _records_operand(records, msg_bytes)
+    _need_gpu(z, "z")
+    if z.device != records.device:
+        raise RuntimeError(f"records lives on {records.device}, expected {z.device}")
+    if z.dim() < 2 or z.shape[0] != B:
+        raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
+    _need_gpu(thresholds, "thresholds")
+    if thresholds.device != z.device:
+        raise RuntimeError(f"thresholds lives on {thresholds.device}, expected {z.device}")
+    if thresholds.dtype != torch.float32 or thresholds.dim() not in (1, 2) or (thresholds.dim() == 2 and thresholds.shape[0] != B):
+        raise ValueError(f"thresholds must be float32 [levels] or [{B}, levels]")
+    levels = thresholds.shape[-1]
+    if not 1 <= levels <= SOFT_MAX_LEVELS:
+        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 1 or n % 8 or n > 1048576:
+        raise ValueError(f"a lattice of {n} elements must fill whole bytes and hold at most 1048576 bits")
+    M = 8 * msg_bytes
+    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    matches = torch.empty((B,), dtype=torch.int32, device=z.device)
+    score = torch.empty((B, M), dtype=torch.int32, device=z.device)
+    wsum = torch.empty((B, M), dtype=torch.int32, device=z.device)
+    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_extract_soft(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, thresholds.data_ptr(),
+                                         levels if thresholds.dim() == 2 else 0, levels, bits.data_ptr(), score.data_ptr(), wsum.data_ptr(),
+                                         wsq.data_ptr(), flags.data_ptr(), matches.data_ptr(), B, n, _stream_ptr()))
+    return SoftVote(bits, flags, matches, score, wsum, wsq)
 
 
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)

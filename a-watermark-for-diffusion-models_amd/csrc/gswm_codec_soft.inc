@@ -1,0 +1,232 @@
+// gswm_codec_soft.inc -- the soft-decision vote: every lattice element votes with an integer reliability level taken from its magnitude,
+// B images under their own records in one launch (gfx950).  Included at the end of gswm_kernels.hip, after gswm_codec_keyed.inc: records,
+// keystream and its LDS staging are gsw_extract_keyed's own (codec_keyed::record_block, records_check), the hard bit q_j is gsw_extract's
+// quantiser (quantise8 / quantise8d), l = 1 only.
+//
+// Definition, image b with thresholds thr[b][0 .. levels) (fp32; row b * thr_stride of thr_dev, thr_stride == 0: one row for all), M = 8 msg_bytes:
+//   p_j     = q_j ^ ks_j                                  the decrypted bit of element j
+//   level_j = #{ i < levels : |z_j| >= thr[b][i] }        0 .. levels, levels in 1 .. 15
+//             fp16 / bf16 / fp32: z widened exactly to fp32 and compared there; fp64: compared in fp64 against the thresholds widened to
+//             fp64 -- an exact function of the stored bits in every dtype.  NaN: level 0; +-inf: `levels` (finite thresholds); -0.0 is 0.0.
+//   score[b, t] = sum over j = t (mod M) of level_j (2 p_j - 1)        wsum[b, t] = the same sum of level_j alone
+//   wsq[b]      = sum over j of level_j^2
+//   bits: MSB first, bit t = (score > 0); a tie or no weight at all gives 0, gsw_extract's tie rule
+//   matches[b]  = how many recovered bits equal record b's message;  flags[b] = gsw_extract's GSW_FLAG_*.  A flagged element still votes
+//                 with its level (a saturated one with the top level its magnitude reaches, a NaN with level 0).
+// With levels = 1, thr = {0} every non-NaN element has level 1: on NaN-free images score = 2 counts - copies of gsw_extract_keyed and the
+// bits are its bits.
+//
+// Kernel.  gsw_extract_soft_kernel<T, STEPS> : [B] workgroups of 256, ceil(N / 512) x 64 bytes of dynamic LDS (the keystream) + 17.1 KiB static;
+// STEPS = bit length of `levels` (1 .. 4).
+// The quads write the image's keystream to LDS as in gsw_extract_keyed_kernel.  N % 8 == 0 and M % 8 == 0, so the group of eight elements
+// g always meets the message bits 8 (g % msg_bytes) .. + 7.  With R = 256 / msg_bytes (rounded down) the first R msg_bytes threads walk the
+// groups tid, tid + R msg_bytes, ...: adjacent lanes load adjacent 16 bytes (fp32: 32, fp64: 64), a thread keeps its octet for the whole
+// image and accumulates eight score and eight wsum sums in registers.  The threads of an octet then meet through LDS, one writer per slot:
+// 16 x 256 int32.
+// The level is a count, so the order of the thresholds does not matter: the first `levels` threads rank the row (ascending, -0.0 == 0.0, ties
+// by index, NaNs last -- no magnitude reaches a NaN) into 16 LDS slots padded with NaN, and "thr[i] <= |z|" is then true exactly for the
+// first level_j slots.  An element finds that count by bisection, STEPS LDS reads and compares instead of `levels` compares
+// (DESIGN.md section 4.16).  Bits come from
+// the wave's ballot (eight adjacent lanes hold a byte).  Integer sums throughout: no atomics, no workspace, nothing to zero first, every
+// output element written, and the results do not depend on the launch geometry.
+
+namespace codec_soft {
+
+constexpr int SOFT_MAX_LEVELS = 15;
+
+struct ExtractSoftArgs {
+    const void* z;          // [B][N]
+    const uint8_t* records; // [B][stride]
+    const float* thr;       // [B][thr_stride] or one row
+    uint8_t* bits;          // [B][msg_bytes]
+    int32_t* score;         // [B][msg_bits] or nullptr
+    int32_t* wsum;          // [B][msg_bits] or nullptr
+    int32_t* wsq;           // [B] or nullptr
+    uint32_t* flags;        // [B]
+    uint32_t* matches;      // [B] or nullptr
+    int64_t thr_stride;     // floats
+    uint32_t stride;
+    uint32_t n_elems;       // N
+    uint32_t msg_bytes;
+    uint32_t nblk;          // ChaCha blocks that cover the staged row
+    uint32_t levels;
+    uint32_t reps;          // R: threads per octet
+    Thr q;                  // gsw_extract's quantiser
+};
+
+// eight elements as the type they are compared in (fp32, fp64 for fp64 inputs), their cipher byte and flags by gsw_extract's quantiser
+template <typename T> struct Group8 {
+    typedef float cmp_t;
+    static __device__ __forceinline__ uint32_t ld(const T* p, const Thr& q, float (&v)[8], uint32_t& flags) {
+        Load8<T>::ld(p, v);
+        return quantise8(v, q, flags);
+    }
+};
+template <> struct Group8<double> {
+    typedef double cmp_t;
+    static __device__ __forceinline__ uint32_t ld(const double* p, const Thr&, double (&v)[8], uint32_t& flags) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const double2 d = reinterpret_cast<const double2*>(p)[i]; v[2 * i] = d.x; v[2 * i + 1] = d.y; }
+        return quantise8d(v, flags);
+    }
+};
+
+template <typename T, int STEPS>
+__global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArgs p) {
+    typedef typename Group8<T>::cmp_t cmp_t;
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // the keystream of the image, p.nblk * 16 words
+    __shared__ int32_t s_part[16][GSW_WG];                           // [k] score, [8 + k] wsum of every thread's octet
+    __shared__ float s_thr[SOFT_MAX_LEVELS + 1];                     // the row in ascending order, NaNs and the padding last
+    __shared__ uint32_t s_flags[GSW_WG / 64], s_wsq[GSW_WG / 64];
+    __shared__ uint32_t s_match[GSW_MSG_INLINE_MAX];                 // matching bits per message byte
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = tid & 3u;
+    const uint32_t b = blockIdx.x;
+    const uint32_t N = p.n_elems, P = p.msg_bytes, M = P * 8u;
+    const uint8_t* rec = p.records + (int64_t)b * p.stride;
+    const uint8_t* row = reinterpret_cast<const uint8_t*>(lds);
+
+    if (tid <= (uint32_t)SOFT_MAX_LEVELS) {
+        uint32_t rank = tid;                                         // the padding stays where it is
+        float t = __uint_as_float(0x7FC00000u);
+        if (tid < p.levels) {
+            const float* thr = p.thr + (int64_t)b * p.thr_stride;
+            t = thr[tid];
+            rank = 0;
+            for (uint32_t j = 0; j < p.levels; ++j) {
+                const float u = thr[j];
+                const bool before = t != t ? (u == u || j < tid) : (u < t || (u == t && j < tid));
+                rank += before ? 1u : 0u;
+            }
+        }
+        s_thr[rank] = t;
+    }
+    for (uint32_t blk = tid >> 2; blk < p.nblk; blk += GSW_WG >> 2) {
+        uint32_t ks[4];
+        codec_keyed::record_block(reinterpret_cast<const uint32_t*>(rec), (uint64_t)blk, col, ks);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) lds[16u * blk + 4u * r + col] = ks[r];
+    }
+    __syncthreads();
+
+    const T* z = reinterpret_cast<const T*>(p.z) + (size_t)b * N;
+    const uint32_t step = p.reps * P;                                // <= 256, a multiple of msg_bytes: a thread keeps its octet
+    int32_t sc[8], ws[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sc[k] = 0; ws[k] = 0; }
+    uint32_t flags = 0, wsq = 0;
+    if (tid < step) {
+        for (uint32_t g = tid; g < (N >> 3); g += step) {            // N % 8 == 0: whole, 16-byte aligned groups
+            cmp_t v[8];
+            const uint32_t c = Group8<T>::ld(z + ((size_t)g << 3), p.q, v, flags) ^ (uint32_t)row[g];
+            uint32_t lv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { v[k] = fabs(v[k]); lv[k] = 0; }   // NaN stays NaN: no threshold counts it
+#pragma unroll
+            for (int h = 1 << (STEPS - 1); h > 0; h >>= 1) {         // slots lv .. lv + h - 1 hold thresholds <= |z| iff the last of them does
+#pragma unroll
+                for (int k = 0; k < 8; ++k) lv[k] += v[k] >= (cmp_t)s_thr[lv[k] + (uint32_t)h - 1u] ? (uint32_t)h : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int32_t w = (int32_t)lv[k];
+                sc[k] += (c >> (7 - k)) & 1u ? w : -w;
+                ws[k] += w;
+                wsq += lv[k] * lv[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { s_part[k][tid] = sc[k]; s_part[8 + k][tid] = ws[k]; }
+    for (int s = 32; s > 0; s >>= 1) { flags |= __shfl_xor(flags, s, 64); wsq += __shfl_xor(wsq, s, 64); }
+    if (lane == 0) { s_flags[tid >> 6] = flags; s_wsq[tid >> 6] = wsq; }
+    __syncthreads();
+
+    for (uint32_t t0 = 0; t0 < M; t0 += GSW_WG) {                    // the same trip count for every lane: the ballot runs with all lanes on
+        const uint32_t t = t0 + tid;
+        int32_t s = 0, w = 0;
+        if (t < M) {
+            for (uint32_t r = 0, th = t >> 3; r < p.reps; ++r, th += P) { s += s_part[t & 7u][th]; w += s_part[8u + (t & 7u)][th]; }
+            if (p.score) p.score[(size_t)b * M + t] = s;
+            if (p.wsum) p.wsum[(size_t)b * M + t] = w;
+        }
+        const uint64_t ball = __ballot(t < M && s > 0);              // ties and no weight -> 0
+        if (t < M && (t & 7u) == 0) {                                // M % 8 == 0: the seven bits after t are this wave's as well
+            uint32_t v = 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v |= (uint32_t)((ball >> (lane + (uint32_t)i)) & 1ull) << (7 - i);
+            p.bits[(size_t)b * P + (t >> 3)] = (uint8_t)v;
+            s_match[t >> 3] = 8u - __popc(v ^ (uint32_t)rec[codec_keyed::KR_HEAD + (t >> 3)]);
+        }
+    }
+    __syncthreads();
+    if (tid < 64u) {
+        uint32_t m = 0;
+        for (uint32_t i = tid; i < P; i += 64u) m += s_match[i];
+        for (int sh = 32; sh > 0; sh >>= 1) m += __shfl_xor(m, sh, 64);
+        if (tid == 0) {
+            if (p.matches) p.matches[b] = m;
+            if (p.wsq) p.wsq[b] = (int32_t)(s_wsq[0] + s_wsq[1] + s_wsq[2] + s_wsq[3]);
+            p.flags[b] = s_flags[0] | s_flags[1] | s_flags[2] | s_flags[3];
+        }
+    }
+}
+
+template <typename T, int STEPS>
+static int launch_soft_steps(const ExtractSoftArgs& a, int B, hipStream_t st) {
+    const uint32_t lds = a.nblk * 64u;
+    if (lds > 32u * 1024u) GSW_HIP(hipFuncSetAttribute((const void*)gsw_extract_soft_kernel<T, STEPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((gsw_extract_soft_kernel<T, STEPS>), dim3((uint32_t)B), dim3(GSW_WG), lds, st, a);
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
+template <typename T>
+static int launch_soft(const ExtractSoftArgs& a, int B, hipStream_t st) {
+    if (a.levels < 2u) return launch_soft_steps<T, 1>(a, B, st);    // the bit length of `levels`: 2^STEPS - 1 >= levels
+    if (a.levels < 4u) return launch_soft_steps<T, 2>(a, B, st);
+    if (a.levels < 8u) return launch_soft_steps<T, 3>(a, B, st);
+    return launch_soft_steps<T, 4>(a, B, st);
+}
+
+}  // namespace codec_soft
+
+int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
+                     int64_t thr_stride, int levels, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,
+                     uint32_t* flags_dev, uint32_t* matches_dev, int B, int64_t n_elems, void* stream) {
+    const int rc = codec_keyed::records_check(records_dev, record_stride, msg_bytes, B);
+    if (rc != GSW_OK) return rc;
+    if (!z_dev || !thr_dev || !bits_dev || !flags_dev || n_elems <= 0) return GSW_ERR_BAD_ARG;
+    if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
+    if ((uintptr_t)z_dev & 15u) return GSW_ERR_BAD_ARG;                                      // 16-byte loads
+    if ((uintptr_t)thr_dev & 3u) return GSW_ERR_BAD_ARG;
+    if (levels < 1 || levels > codec_soft::SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
+    if (thr_stride != 0 && thr_stride < levels) return GSW_ERR_BAD_ARG;
+    if (n_elems % 8 || n_elems > codec_keyed::KR_MAX_BITS) return GSW_ERR_UNSUPPORTED;
+    if (n_elems % ((int64_t)msg_bytes * 8)) return GSW_ERR_RAGGED;
+    codec_soft::ExtractSoftArgs a;
+    memset(&a, 0, sizeof(a));
+    a.z = z_dev;
+    a.records = records_dev;
+    a.thr = thr_dev;
+    a.bits = bits_dev;
+    a.score = score_dev;
+    a.wsum = wsum_dev;
+    a.wsq = wsq_dev;
+    a.flags = flags_dev;
+    a.matches = matches_dev;
+    a.thr_stride = thr_stride;
+    a.stride = (uint32_t)record_stride;
+    a.n_elems = (uint32_t)n_elems;
+    a.msg_bytes = (uint32_t)msg_bytes;
+    a.nblk = (uint32_t)((n_elems / 8 + 63) / 64);
+    a.levels = (uint32_t)levels;
+    a.reps = (uint32_t)GSW_WG / (uint32_t)msg_bytes;               // msg_bytes <= 256 = GSW_WG: at least 1
+    a.q = make_thr(z_dtype);
+    hipStream_t st = (hipStream_t)stream;
+    switch (z_dtype) {
+        case GSW_F32: return codec_soft::launch_soft<float>(a, B, st);
+        case GSW_F16: return codec_soft::launch_soft<__half>(a, B, st);
+        case GSW_BF16: return codec_soft::launch_soft<__hip_bfloat16>(a, B, st);
+        default: return codec_soft::launch_soft<double>(a, B, st);
+    }
+}

@@ -1672,3 +1672,8 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
 // One record per image (every image under its own key, nonce and message): gsw_embed_keyed / gsw_extract_keyed, kernels and entry points
 // ------------------------------------------------------------------------------------------------
 #include "gswm_codec_keyed.inc"
+
+// ------------------------------------------------------------------------------------------------
+// Soft-decision vote (every element weighted by an integer reliability level): gsw_extract_soft, kernel and entry point
+// ------------------------------------------------------------------------------------------------
+#include "gswm_codec_soft.inc"

@@ -40,8 +40,24 @@ def _window(args) -> int:
     return codec.check_window(l)
 
 
+def _soft_wanted(args, l: int) -> bool:
+    """--soft as a bool; the combinations the soft vote does not exist for are refused by name"""
+    if not int(getattr(args, "soft", 0) or 0):
+        return False
+    if int(getattr(args, "robust", 0) or 0):
+        raise ValueError("--soft 1 cannot be combined with --robust 1: level weights and tile weights are separate votes")
+    if l != 1:
+        raise ValueError(f"--soft 1 cannot be combined with --l {l}: reliability levels are defined for one cipher bit per element (--l 1)")
+    return True
+
+
 def _vote(z, args, m: int, l: int):
-    """(bits, flags) of the reference's vote, or with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations)"""
+    """(bits, flags) of the reference's vote, with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations), with
+    --soft 1 of the level-weighted vote (soft.extract_soft, thresholds scaled to each image's RMS)"""
+    if _soft_wanted(args, l):
+        from . import soft
+        res = soft.extract_soft(z, args.key, args.nonce, m, levels=int(getattr(args, "soft_levels", 15)), clip=float(getattr(args, "soft_clip", 2.5)))
+        return res.bits, res.flags
     if int(getattr(args, "robust", 0) or 0):
         from . import tamper
         return tamper.extract_robust(z, args.key, args.nonce, m, l=l, tile=int(getattr(args, "tile", 8)))[:2]
@@ -582,7 +598,17 @@ def process_single_directory(dir_path, args, *, batch_size=None):
 def build_parser():
     """extract.py:180-195: same flags and defaults."""
     import argparse
-    parser = argparse.ArgumentParser(description="Extract watermark from a image")
+
+    class Parser(argparse.ArgumentParser):
+        def parse_args(self, args=None, namespace=None):
+            a = super().parse_args(args, namespace)
+            if a.soft and a.robust:
+                self.error("--soft 1 cannot be combined with --robust 1: level weights and tile weights are separate votes")
+            if a.soft and a.l != 1:
+                self.error(f"--soft 1 cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
+            return a
+
+    parser = Parser(description="Extract watermark from a image")
     parser.add_argument("--model_id", default="stabilityai/stable-diffusion-2-1-base")
     parser.add_argument("--images_directory_path", default="", help="The path of directory containing images to process")
     parser.add_argument("--single_image_path", default="")
@@ -609,6 +635,12 @@ def build_parser():
     parser.add_argument("--tamper_map", default=None, metavar="DIR",
                         help="(not a reference flag) write DIR/<image>.tamper.npy / .tamper.png: per tile, the bits that agree with --original_message_hex")
     parser.add_argument("--tile", type=int, default=8, choices=codec.TILES, help="(not a reference flag) tile edge of --robust / --tamper_map, in lattice elements")
+    parser.add_argument("--soft", type=int, choices=[0, 1], default=0,
+                        help="(not a reference flag) 1: decode with the soft-decision vote (soft.extract_soft): every lattice element votes with a "
+                             "reliability level taken from its magnitude; 0: the reference's vote.  Not with --robust 1, --l 1 only")
+    parser.add_argument("--soft_levels", type=int, default=15, choices=range(1, 16), metavar="LEVELS", help="(not a reference flag) reliability levels of --soft 1 (1..15)")
+    parser.add_argument("--soft_clip", type=float, default=2.5,
+                        help="(not a reference flag) --soft 1: the top level starts at this many times the image's RMS")
     parser.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                         help="(not a reference flag) 1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning "
                              "(default: 1; 0 opts into the library kernels, counted and warned about once per reason)")

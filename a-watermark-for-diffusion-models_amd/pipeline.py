@@ -57,10 +57,19 @@ class GaussianShadingPipeline:
                                    l=self.l)
 
     # X2 + X3-X5 + X6 against each image's own record
-    def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False):
-        """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`"""
+    def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False, soft: bool = False,
+                       levels: int = 15, clip: float = 2.5):
+        """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`.
+        soft=True: the `codec.SoftVote` (bits, flags, matches, score, wsum, wsq) of `codec.extract_soft` instead, every element weighted by
+        one of `levels` reliability levels with thresholds scaled to its image's RMS (`soft.uniform_thresholds(z, levels, clip)`); l = 1 only."""
+        if soft and self.l != 1:
+            raise ValueError(f"soft=True cannot be combined with l = {self.l}: reliability levels are defined for one cipher bit per element")
         z = ddim_invert(self.eps_model, x0, self._uncond(x0.shape[0]), self.schedule)
-        res = codec.extract_records(z, records, msg_bytes, l=self.l)
+        if soft:
+            from . import soft as S
+            res = codec.extract_soft(z, records, msg_bytes, S.uniform_thresholds(z, levels, clip))
+        else:
+            res = codec.extract_records(z, records, msg_bytes, l=self.l)
         return (*res, z) if return_latents else res
 
     # G1

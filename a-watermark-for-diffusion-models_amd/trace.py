@@ -21,6 +21,11 @@ the Bonferroni bound min(0, log10 p + log10 U); an image is attributed iff that 
 
 Single key (`Registry`, `trace_latents`): every candidate shares one ChaCha20 key / nonce.
 
+Reliability levels (`trace_latents(..., reliability=T)`, `--reliability T`; single key, l = 1): the vote is the soft-decision vote of `soft.py`, every
+lattice bit weighted by an integer level 0..T taken from its element's magnitude, s = sum_t (2 r[t] - 1) score[t].  The same search launch ranks
+it (`reliability_counts`).  Given the levels the null model still makes every decrypted bit a fair coin, but the weighted sum has no closed-form
+tail: the reported value is the Hoeffding bound `soft.log10_p(s, sum level^2)`, valid but looser than an exact tail.
+
 Per-record keys (`KeyedRegistry`, `trace_latents_keyed`, `--per_record_keys`): what gs_insert logs when key and nonce are left blank --
 a fresh random key and nonce per run, so the log is a list of (key, nonce, message) triples.  Decrypting the image under a record's
 key and comparing with its message is the same as comparing the image's quantised sign bits h with the record's codeword
@@ -541,27 +546,61 @@ def _attach_tamper_maps(out, z, packed, records, M: int, l: int, tile: int, fpr:
         out[b].tamper = TM.make_map(agree[b], n_t, tile, fpr, "registry")
 
 
+def reliability_counts(score, levels: int, copies: int):
+    """The (counts', copies') that make `codec.trace_topk`'s soft weight 2 c' - copies' equal to 2 score[b, t], the level-weighted vote of
+    `codec.extract_soft`: c' = score + levels copies (0 <= c' <= copies'), copies' = 2 levels copies.  Works on tensors and arrays; raises
+    where gsw_trace_topk's limits on copies' would not hold."""
+    T, V = int(levels), int(copies)
+    M = int(score.shape[-1])
+    if 2 * T * V > 2000000 or M * 2 * T * V >= 2 ** 31:
+        raise ValueError(f"reliability={T} with {V} copies of {M} message bits is beyond the registry search's limits "
+                         "(2 levels copies <= 2 000 000 and msg_bits 2 levels copies < 2^31)")
+    return score + T * V, 2 * T * V
+
+
 def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, message_length: Optional[int] = None, k: int = 1,
-                  fpr: float = 1e-6, soft: bool = True, l: int = 1, tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+                  fpr: float = 1e-6, soft: bool = True, l: int = 1, tamper_tile: Optional[int] = None,
+                  reliability: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
     """latents [B, ...] on the device -> one TraceResult per image (best candidate first), or the ValueError the reference raises for
     that image (a saturated / NaN latent, extract.py:84-86), like `extract.recover_exactracted_message_batch`.
 
     One vote kernel, one search launch over the packed registry; the host receives the B k pairs (plus the vote's flags and bits).
     l: cipher bits per lattice element the images were embedded with (a property of the deployment, like the key).
     tamper_tile: 8, 16 or 32 -> every attributed image also gets `TraceResult.tamper`, the per-tile agreement with its best candidate's
-    codeword (one quantise-and-pack and one `codec.tile_agreement` launch more per batch); None: nothing more runs."""
+    codeword (one quantise-and-pack and one `codec.tile_agreement` launch more per batch); None: nothing more runs.
+    reliability: None, or the number of reliability levels (1..15) of the level-weighted statistic: the vote is `soft.extract_soft` with
+    thresholds scaled to each image's RMS, a candidate's score is sum_t (2 r[t] - 1) score[t] (the same search launch, fed through
+    `reliability_counts`), `Candidate.agree` counts the soft vote's bits and the p-value is the Hoeffding bound `soft.log10_p` with the
+    image's wsq -- a bound, not the exact binomial tail of the margin statistic.  Not with soft=False, l = 1 only."""
     import torch
     from . import _native as N
     if not 0.0 < float(fpr) <= 1.0:
         raise ValueError("fpr must be in (0, 1]")
+    l = codec.check_window(l)
+    if reliability is not None:
+        if not soft:
+            raise ValueError("reliability cannot be combined with --hard (soft=False): the level-weighted statistic ranks by weighted margins")
+        if l != 1:
+            raise ValueError(f"reliability cannot be combined with l = {l}: reliability levels are defined for one cipher bit per element")
+        from . import soft as S
+        reliability = S._check_table(reliability, 2.5)[0]
     M = registry.message_bits if message_length is None else int(message_length)
     z = latents.contiguous()
     B = z.shape[0]
     rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
     V = codec.vote_copies(z.numel() // max(B, 1), M, l)
     reg_dev = registry.to_device(z.device, M)
-    bits, flags, counts = codec.extract_batch(z, key, nonce, M, return_counts=True, l=l)
-    idx, score = codec.trace_topk(counts, V, reg_dev, k=k, soft=soft)
+    wsq_h = None
+    if reliability is None:
+        bits, flags, counts = codec.extract_batch(z, key, nonce, M, return_counts=True, l=l)
+        idx, score = codec.trace_topk(counts, V, reg_dev, k=k, soft=soft)
+    else:
+        vote = S.extract_soft(z, key, nonce, M, levels=reliability)
+        bits, flags = vote.bits, vote.flags
+        counts, copies = reliability_counts(vote.score, reliability, V)
+        idx, score = codec.trace_topk(counts, copies, reg_dev, k=k, soft=True)
+        score = torch.where(idx >= 0, score // 2, score)                 # the search weighs 2 score[b, t]: every score is even
+        wsq_h = vote.wsq.cpu().numpy()
     pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy; flags and voted bits are the vote's own outputs
     idx_h, score_h = pairs[0], pairs[1]
     flags_h, bits_h = flags.cpu().numpy(), bits.cpu().numpy()
@@ -580,7 +619,10 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
             if i < 0:
                 break
             agree = M - int(np.unpackbits(bits_h[b] ^ rows[i]).sum())
-            lp = log10_p_soft(s, M * V) if soft else log10_p_hard(agree, M, V)
+            if wsq_h is not None:
+                lp = S.log10_p(s, int(wsq_h[b]))
+            else:
+                lp = log10_p_soft(s, M * V) if soft else log10_p_hard(agree, M, V)
             res.candidates.append(Candidate(registry.user_at(i), i, s, agree, log10_p_any(lp, U)))
         if res.candidates and res.candidates[0].log10_p_any <= limit:
             res.attributed = res.candidates[0].user_id
@@ -593,7 +635,7 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
 
 
 def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: float = 1e-6, l: int = 1,
-                        tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+                        tamper_tile: Optional[int] = None, reliability: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
     """`trace_latents` against a registry whose records carry their own keys: latents [B, ...] on the device -> one TraceResult per
     image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
 
@@ -602,9 +644,13 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     the soft score (`log10_p_soft(score, n)`), Bonferroni over the records.  `Candidate.agree` is the reference's voted-bit agreement
     under that candidate's own key: `codec.extract_batch` + `codec.bit_matches` for the reported candidates only, grouped by key.
     l: cipher bits per lattice element; the codewords then span n l bits.
-    tamper_tile: as in `trace_latents`; the map of an image is taken under its best candidate's OWN key (one launch more per batch)."""
+    tamper_tile: as in `trace_latents`; the map of an image is taken under its best candidate's OWN key (one launch more per batch).
+    reliability: must be None -- a level-weighted search across keys would be a search kernel of its own."""
     import torch
     from . import _native as N
+    if reliability is not None:
+        raise ValueError("reliability cannot be combined with trace_latents_keyed (--per_record_keys): the level-weighted search exists "
+                         "for the shared-key registry only")
     if not 0.0 < float(fpr) <= 1.0:
         raise ValueError("fpr must be in (0, 1]")
     z = latents.contiguous()
@@ -677,6 +723,13 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.reliability is not None:
+                if a.hard:
+                    self.error("--reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
+                if a.per_record_keys:
+                    self.error("--reliability cannot be combined with --per_record_keys: the level-weighted search exists for the shared-key registry only")
+                if a.l != 1:
+                    self.error(f"--reliability cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
             if a.per_record_keys:
                 if a.hard:
                     self.error("--hard cannot be combined with --per_record_keys: only the soft statistic exists across keys")
@@ -704,6 +757,9 @@ def build_parser():
     p.add_argument("--fpr", type=float, default=1e-6, help="false-positive rate per image, over the whole registry (Bonferroni)")
     p.add_argument("--top", type=int, default=1, choices=range(1, 9), metavar="K", help="candidates reported per image (1..8)")
     p.add_argument("--hard", action="store_true", help="rank by the majority-voted bits instead of the vote margins")
+    p.add_argument("--reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
+                   help="rank by level-weighted margins: every lattice element votes with one of LEVELS (1..15) reliability levels taken from its "
+                        "magnitude, the p-value is a Hoeffding bound (shared key, --l 1, not with --hard)")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -741,7 +797,7 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
         if args.per_record_keys:
             return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr, l=args.l, tamper_tile=tile)
         return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard,
-                             l=args.l, tamper_tile=tile)
+                             l=args.l, tamper_tile=tile, reliability=args.reliability)
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         decoded = list(pool.map(decode, files))
@@ -777,7 +833,7 @@ def _report(job, outcomes, args, registry, synthetic: bool) -> None:
         keyed = [("keys", registry.n_keys)] if args.per_record_keys else []
         fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("key_hex", "per record" if keyed else args.key_hex),
                   ("nonce_hex", "per record" if keyed else args.nonce_hex), ("registry", args.registry),
-                  ("users", len(registry)), *keyed, ("message_length", M), ("statistic", "hard" if args.hard else "soft"), ("fpr", args.fpr),
+                  ("users", len(registry)), *keyed, ("message_length", M), ("statistic", "hard" if args.hard else "soft" if args.reliability is None else f"soft, {args.reliability} reliability levels"), ("fpr", args.fpr),
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:

@@ -631,6 +631,39 @@ int gsw_extract_keyed(const void* z_dev, int z_dtype, const uint8_t* records_dev
                       uint8_t* bits_dev, uint32_t* counts_dev /* NULL ok */, uint32_t* flags_dev, uint32_t* matches_dev /* NULL ok */,
                       int B, int64_t n_elems, int l, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Soft-decision vote: every lattice element votes with an integer reliability level taken from its magnitude.
+ * Additive: gsw_version() stays 500.
+ *
+ *   records_dev : gsw_extract_keyed's rows, uint8 [B, record_stride], 16-byte aligned: key[32] | nonce16[16] | msg[msg_bytes]; the keystream of
+ *                 image b is record b's (gsw_keystream's counter and carry), generated inside the launch and never stored.  M = 8 msg_bytes,
+ *                 one cipher bit per element (l = 1).
+ *   thr_dev     : float [B, thr_stride] (thr_stride >= levels, in floats) or, with thr_stride == 0, one row of `levels` floats for all images;
+ *                 levels is 1..15.
+ *   p_j         = q_j ^ ks_j, q_j the quantiser of gsw_extract.
+ *   level_j     = #{ i < levels : |z_j| >= thr[b][i] }.  fp16, bf16 and fp32 inputs are widened exactly to fp32 and compared there, fp64
+ *                 inputs are compared in fp64 against the thresholds widened to fp64: an exact function of the stored bits in every dtype.
+ *                 NaN gives level 0, +-inf gives `levels` (finite thresholds), -0.0 counts as 0.0.
+ *   score_dev   : int32 [B, M] (NULL ok), score[b, t] = sum over j = t (mod M) of level_j (2 p_j - 1)
+ *   wsum_dev    : int32 [B, M] (NULL ok), the same sum of level_j alone
+ *   wsq_dev     : int32 [B] (NULL ok), sum over the image of level_j^2
+ *   bits_dev    : uint8 [B, msg_bytes], MSB first, bit t = (score > 0): a tie or no weight at all gives 0, gsw_extract's tie rule
+ *   matches_dev : uint32 [B] (NULL ok), how many recovered bits equal record b's message, as gsw_extract_keyed
+ *   flags_dev   : uint32 [B], gsw_extract's GSW_FLAG_*; a flagged element still votes with its level, a NaN with level 0
+ * With levels = 1 and thr = {0} every non-NaN element has level 1: on NaN-free images score = 2 counts - copies of gsw_extract_keyed and
+ * the bits are its bits.
+ * One launch.  Every output element is written, no atomics, no workspace, nothing to zero first; the results are exact integers and do
+ * not depend on the launch geometry.
+ * GSW_ERR_BAD_ARG: null pointer (score_dev, wsum_dev, wsq_dev, matches_dev excepted), B < 1, msg_bytes outside 1..256, a bad stride or
+ * alignment of records_dev, z_dev not 16-byte aligned, thr_dev not 4-byte aligned, thr_stride neither 0 nor >= levels, levels outside
+ * 1..15, unknown dtype, n_elems < 1.
+ * GSW_ERR_UNSUPPORTED: n_elems % 8 != 0 or n_elems > 1 048 576 (one image's keystream is staged in 128 KiB of LDS).
+ * GSW_ERR_RAGGED: n_elems % (8 msg_bytes) != 0. */
+int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
+                     const float* thr_dev, int64_t thr_stride /* floats; 0: one table for all images */, int levels,
+                     uint8_t* bits_dev, int32_t* score_dev /* NULL ok */, int32_t* wsum_dev /* NULL ok */, int32_t* wsq_dev /* NULL ok */,
+                     uint32_t* flags_dev, uint32_t* matches_dev /* NULL ok */, int B, int64_t n_elems, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
