@@ -33,12 +33,16 @@ def _need_gpu(t: torch.Tensor, name: str):
         raise ValueError(f"{name} must be 16-byte aligned (got a view at an odd storage offset; .clone() it)")
 
 
+def _same_device(t: torch.Tensor, ref: torch.Tensor, name: str):
+    if t.device != ref.device:
+        raise RuntimeError(f"{name} lives on {t.device}, expected {ref.device}")
+
+
 def _like(t: torch.Tensor, ref: torch.Tensor, name: str, numel: Optional[int] = None):
     """A companion operand whose raw pointer crosses the C ABI next to `ref`: same device and dtype, contiguous, aligned, expected size.
     (A dtype mismatch would be read as the wrong bytes, a short tensor is an out-of-bounds device read: both are silent otherwise.)"""
     _need_gpu(t, name)
-    if t.device != ref.device:
-        raise RuntimeError(f"{name} lives on {t.device}, expected {ref.device}")
+    _same_device(t, ref, name)
     if t.dtype != ref.dtype:
         raise ValueError(f"{name} is {t.dtype}, expected {ref.dtype}")
     if numel is not None and t.numel() != numel:
@@ -113,6 +117,26 @@ def keystream(key: bytes, nonce: bytes, nbytes: int, device="cuda") -> torch.Ten
 
 
 # ------------------------------------------------------------------------------------------------ E3-E6
+def _embed_operands(out: Optional[torch.Tensor], u: Optional[torch.Tensor], batch: int, shape: Sequence[int], n: int, dtype: torch.dtype, device,
+                    ref: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[int]]:
+    """The `out` / `u` operands of an embed -> (out, allocated when None, and u's pointer or None); ref: a tensor both must share the device of"""
+    if out is None:
+        out = torch.empty((batch, *shape), dtype=dtype, device=device)
+    elif out.numel() != batch * n:
+        raise ValueError("out has the wrong size")
+    _need_gpu(out, "out")
+    if ref is not None:
+        _same_device(out, ref, "out")
+    if u is None:
+        return out, None
+    _need_gpu(u, "u")
+    if ref is not None:
+        _same_device(u, ref, "u")
+    if u.dtype != torch.float64 or u.numel() != batch * n:
+        raise ValueError("u must be float64 with batch*n_elems entries")
+    return out, u.data_ptr()
+
+
 def embed_batch(key: bytes, nonce: bytes, k: bytes, batch: int, shape: Sequence[int], *, u: Optional[torch.Tensor] = None,
                 seed: int = 0, image_index0: int = 0, dtype: torch.dtype = torch.float32, fast: bool = False,
                 device="cuda", out: Optional[torch.Tensor] = None, l: int = 1) -> torch.Tensor:
@@ -129,18 +153,7 @@ def embed_batch(key: bytes, nonce: bytes, k: bytes, batch: int, shape: Sequence[
     n = 1
     for s in shape:
         n *= int(s)
-    if out is None:
-        out = torch.empty((batch, *shape), dtype=dtype, device=device)
-    else:
-        if out.numel() != batch * n:
-            raise ValueError("out has the wrong size")
-    _need_gpu(out, "out")
-    u_ptr = None
-    if u is not None:
-        _need_gpu(u, "u")
-        if u.dtype != torch.float64 or u.numel() != batch * n:
-            raise ValueError("u must be float64 with batch*n_elems entries")
-        u_ptr = u.data_ptr()
+    out, u_ptr = _embed_operands(out, u, batch, shape, n, dtype, device)
     mode = N.GSW_EMBED_FAST_F32 if fast else N.GSW_EMBED_EXACT_F64
     with torch.cuda.device(out.device):
         if l == 1:
@@ -188,6 +201,14 @@ def mt19937_uniform(n: int, rng=None, *, device="cuda") -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ X3-X5
+def _vote_outputs(B: int, M: int, device, return_counts: bool):
+    """What a vote writes -> (bits uint8 [B, ceil(M / 8)], flags int32 [B], counts int32 [B, M] or None)"""
+    bits = torch.empty((B, (M + 7) // 8), dtype=torch.uint8, device=device)
+    flags = torch.empty((B,), dtype=torch.int32, device=device)
+    counts = torch.empty((B, M), dtype=torch.int32, device=device) if return_counts else None
+    return bits, flags, counts
+
+
 def extract_batch(z: torch.Tensor, key: bytes, nonce: bytes, message_length: int, *, return_counts: bool = False, l: int = 1):
     """Recover the message from latents z [B, ...] (any of fp16/bf16/fp32/fp64); l: cipher bits per element (1, 2 or 4), the
     lattice then holds n * l bits and each message bit gets n * l / message_length votes.
@@ -202,9 +223,7 @@ def extract_batch(z: torch.Tensor, key: bytes, nonce: bytes, message_length: int
     B = z.shape[0]
     n = z.numel() // max(B, 1)
     M = int(message_length)
-    bits = torch.empty((B, (M + 7) // 8), dtype=torch.uint8, device=z.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
-    counts = torch.empty((B, M), dtype=torch.int32, device=z.device) if return_counts else None
+    bits, flags, counts = _vote_outputs(B, M, z.device, return_counts)
     with torch.cuda.device(z.device):
         if l == 1:
             N.check(N.lib().gsw_extract(z.data_ptr(), _dt(z.dtype), key, nonce, M, bits.data_ptr(),
@@ -261,8 +280,7 @@ def trace_topk(counts: torch.Tensor, copies: int, registry_bits: torch.Tensor, k
         raise ValueError("counts must be int32 [B, M]")
     if registry_bits.dtype != torch.uint8 or registry_bits.dim() != 2:
         raise ValueError("registry_bits must be uint8 [U, M/8]")
-    if registry_bits.device != counts.device:
-        raise RuntimeError(f"registry_bits lives on {registry_bits.device}, expected {counts.device}")
+    _same_device(registry_bits, counts, "registry_bits")
     B, M = counts.shape
     U = registry_bits.shape[0]
     if registry_bits.shape[1] * 8 != M:
@@ -283,11 +301,22 @@ def trace_topk(counts: torch.Tensor, copies: int, registry_bits: torch.Tensor, k
 
 # ------------------------------------------------------------------------------------------------ tracing (records with their own keys)
 KEYED_RECORD_HEAD = 48          # key[32] | nonce16[16], then the message
+ROW_MAX_BITS = 1048576          # lattice bits of one image in the kernels that stage an image's row in LDS (csrc/gswm_record.h)
 
 
 def keyed_record_stride(msg_bytes: int) -> int:
     """Bytes per row of a keyed registry: key | nonce | message, padded to a multiple of 16."""
     return (KEYED_RECORD_HEAD + int(msg_bytes) + 15) // 16 * 16
+
+
+def _record_layout(stride: int, msg_bytes) -> int:
+    """msg_bytes of a records operand with rows of `stride` bytes, as an int, or ValueError"""
+    if isinstance(msg_bytes, bool) or not isinstance(msg_bytes, (int, np.integer)) or not 1 <= int(msg_bytes) <= N.GSW_MSG_INLINE_MAX:
+        raise ValueError(f"msg_bytes {msg_bytes!r} is outside 1..{N.GSW_MSG_INLINE_MAX}")
+    msg_bytes = int(msg_bytes)
+    if stride < KEYED_RECORD_HEAD + msg_bytes or stride % 16:
+        raise ValueError(f"record rows of {stride} bytes cannot hold key | nonce | {msg_bytes}-byte message at a multiple of 16")
+    return msg_bytes
 
 
 def sign_pack(z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -339,16 +368,12 @@ def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, ms
         raise ValueError("signs must be uint8 [B, n_bits / 8]")
     if records.dtype != torch.uint8 or records.dim() != 2:
         raise ValueError("records must be uint8 [U, stride]")
-    if records.device != signs.device:
-        raise RuntimeError(f"records lives on {records.device}, expected {signs.device}")
+    _same_device(records, signs, "records")
     B, U, stride = signs.shape[0], records.shape[0], records.shape[1]
     n_bits, msg_bytes, k = int(n_bits), int(msg_bytes), int(k)
     if signs.shape[1] * 8 != n_bits:
         raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
-    if not 1 <= msg_bytes <= N.GSW_MSG_INLINE_MAX:
-        raise ValueError(f"msg_bytes {msg_bytes} is outside 1..{N.GSW_MSG_INLINE_MAX}")
-    if stride < KEYED_RECORD_HEAD + msg_bytes or stride % 16:
-        raise ValueError(f"record rows of {stride} bytes cannot hold key | nonce | {msg_bytes}-byte message at a multiple of 16")
+    _record_layout(stride, msg_bytes)
     lib = N.lib()
     ws_bytes = lib.gsw_trace_keyed_workspace_bytes(B, U, k)
     if ws_bytes == 0:
@@ -371,12 +396,7 @@ def _records_operand(records: torch.Tensor, msg_bytes: int) -> Tuple[int, int, i
     B, stride = records.shape[0], records.shape[1]
     if B < 1:
         raise ValueError("records holds no row")
-    if isinstance(msg_bytes, bool) or not isinstance(msg_bytes, (int, np.integer)) or not 1 <= int(msg_bytes) <= N.GSW_MSG_INLINE_MAX:
-        raise ValueError(f"msg_bytes {msg_bytes!r} is outside 1..{N.GSW_MSG_INLINE_MAX}")
-    msg_bytes = int(msg_bytes)
-    if stride < KEYED_RECORD_HEAD + msg_bytes or stride % 16:
-        raise ValueError(f"record rows of {stride} bytes cannot hold key | nonce | {msg_bytes}-byte message at a multiple of 16")
-    return B, stride, msg_bytes
+    return B, stride, _record_layout(stride, msg_bytes)
 
 
 def embed_records(records: torch.Tensor, msg_bytes: int, shape: Sequence[int], *, u: Optional[torch.Tensor] = None, seed: int = 0,
@@ -395,21 +415,7 @@ def embed_records(records: torch.Tensor, msg_bytes: int, shape: Sequence[int], *
         n *= int(s)
     if n < 4 or n % 4:
         raise ValueError(f"the lattice must hold a positive multiple of 4 elements per image (got {n})")
-    if out is None:
-        out = torch.empty((B, *shape), dtype=dtype, device=records.device)
-    elif out.numel() != B * n:
-        raise ValueError("out has the wrong size")
-    _need_gpu(out, "out")
-    if out.device != records.device:
-        raise RuntimeError(f"out lives on {out.device}, expected {records.device}")
-    u_ptr = None
-    if u is not None:
-        _need_gpu(u, "u")
-        if u.device != records.device:
-            raise RuntimeError(f"u lives on {u.device}, expected {records.device}")
-        if u.dtype != torch.float64 or u.numel() != B * n:
-            raise ValueError("u must be float64 with batch*n_elems entries")
-        u_ptr = u.data_ptr()
+    out, u_ptr = _embed_operands(out, u, B, shape, n, dtype, records.device, ref=records)
     mode = N.GSW_EMBED_FAST_F32 if fast else N.GSW_EMBED_EXACT_F64
     with torch.cuda.device(out.device):
         N.check(N.lib().gsw_embed_keyed(records.data_ptr(), stride, msg_bytes, u_ptr, seed & (2**64 - 1), image_index0, out.data_ptr(),
@@ -428,19 +434,15 @@ def extract_records(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, l
     B, stride, msg_bytes = _records_operand(records, msg_bytes)
     l = check_window(l)
     _need_gpu(z, "z")
-    if z.device != records.device:
-        raise RuntimeError(f"records lives on {records.device}, expected {z.device}")
+    _same_device(records, z, "records")
     if z.dim() < 2 or z.shape[0] != B:
         raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
     dt = _dt(z.dtype)
     n = z.numel() // B
-    if n < 1 or (n * l) % 8 or n * l > 1048576:
-        raise ValueError(f"a lattice of {n} elements at l = {l} must fill whole bytes and hold at most 1048576 bits")
-    M = 8 * msg_bytes
-    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    if n < 1 or (n * l) % 8 or n * l > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n} elements at l = {l} must fill whole bytes and hold at most {ROW_MAX_BITS} bits")
+    bits, flags, counts = _vote_outputs(B, 8 * msg_bytes, z.device, return_counts)
     matches = torch.empty((B,), dtype=torch.int32, device=z.device)
-    counts = torch.empty((B, M), dtype=torch.int32, device=z.device) if return_counts else None
     with torch.cuda.device(z.device):
         N.check(N.lib().gsw_extract_keyed(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, bits.data_ptr(),
                                           counts.data_ptr() if return_counts else None, flags.data_ptr(), matches.data_ptr(), B, n, l,
@@ -472,13 +474,11 @@ def extract_soft(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresho
     NaN-free images the bits are `extract_records`' bits and score = 2 counts - copies.  Lattice limits and IndexError as `extract_records`."""
     B, stride, msg_bytes = _records_operand(records, msg_bytes)
     _need_gpu(z, "z")
-    if z.device != records.device:
-        raise RuntimeError(f"records lives on {records.device}, expected {z.device}")
+    _same_device(records, z, "records")
     if z.dim() < 2 or z.shape[0] != B:
         raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
     _need_gpu(thresholds, "thresholds")
-    if thresholds.device != z.device:
-        raise RuntimeError(f"thresholds lives on {thresholds.device}, expected {z.device}")
+    _same_device(thresholds, z, "thresholds")
     if thresholds.dtype != torch.float32 or thresholds.dim() not in (1, 2) or (thresholds.dim() == 2 and thresholds.shape[0] != B):
         raise ValueError(f"thresholds must be float32 [levels] or [{B}, levels]")
     levels = thresholds.shape[-1]
@@ -486,8 +486,8 @@ def extract_soft(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresho
         raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
     dt = _dt(z.dtype)
     n = z.numel() // B
-    if n < 1 or n % 8 or n > 1048576:
-        raise ValueError(f"a lattice of {n} elements must fill whole bytes and hold at most 1048576 bits")
+    if n < 1 or n % 8 or n > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n} elements must fill whole bytes and hold at most {ROW_MAX_BITS} bits")
     M = 8 * msg_bytes
     bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
     flags = torch.empty((B,), dtype=torch.int32, device=z.device)
@@ -530,8 +530,7 @@ def _tiled_operands(packed: torch.Tensor, keys: torch.Tensor, msg_bits: int, sha
         raise ValueError(f"packed rows hold {packed.shape[1] * 8} bits, a {C} x {h} x {w} lattice at l = {l} has {C * h * w * l}")
     if keys.dtype != torch.uint8 or tuple(keys.shape) != (B, KEYED_RECORD_HEAD):
         raise ValueError(f"keys must be uint8 [{B}, {KEYED_RECORD_HEAD}]: key[32] | nonce16[16] per image")
-    if keys.device != packed.device:
-        raise RuntimeError(f"keys lives on {keys.device}, expected {packed.device}")
+    _same_device(keys, packed, "keys")
     return B, C, h, w, l, tile, M, h // tile, w // tile
 
 
@@ -548,8 +547,7 @@ def tile_agreement(packed: torch.Tensor, keys: torch.Tensor, messages: torch.Ten
     _need_gpu(messages, "messages")
     if messages.dtype != torch.uint8 or tuple(messages.shape) != (B, M // 8):
         raise ValueError(f"messages must be uint8 [{B}, {M // 8}]")
-    if messages.device != packed.device:
-        raise RuntimeError(f"messages lives on {messages.device}, expected {packed.device}")
+    _same_device(messages, packed, "messages")
     agree = torch.empty((B, th, tw), dtype=torch.int32, device=packed.device)
     with torch.cuda.device(packed.device):
         N.check(N.lib().gsw_tile_agree(packed.data_ptr(), B, C, h, w, l, tile, keys.data_ptr(), messages.data_ptr(), M, agree.data_ptr(), _stream_ptr()))
@@ -568,8 +566,7 @@ def vote_tiled(packed: torch.Tensor, keys: torch.Tensor, weights: torch.Tensor, 
     _need_gpu(weights, "weights")
     if weights.dtype != torch.uint16 or tuple(weights.shape) != (B, th, tw):
         raise ValueError(f"weights must be uint16 [{B}, {th}, {tw}]")
-    if weights.device != packed.device:
-        raise RuntimeError(f"weights lives on {weights.device}, expected {packed.device}")
+    _same_device(weights, packed, "weights")
     bits = torch.empty((B, M // 8), dtype=torch.uint8, device=packed.device)
     score = torch.empty((B, M), dtype=torch.int32, device=packed.device)
     wsum = torch.empty((B, M), dtype=torch.int32, device=packed.device)
@@ -653,9 +650,7 @@ def ddim_step_extract(x: torch.Tensor, model_out: torch.Tensor, a: float, b: flo
     B = x.shape[0]
     n = x.numel() // max(B, 1)
     M = int(message_length)
-    bits = torch.empty((B, (M + 7) // 8), dtype=torch.uint8, device=x.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=x.device)
-    counts = torch.empty((B, M), dtype=torch.int32, device=x.device) if return_counts else None
+    bits, flags, counts = _vote_outputs(B, M, x.device, return_counts)
     with torch.cuda.device(x.device):
         N.check(N.lib().gsw_ddim_step_extract(x.data_ptr(), model_out.data_ptr(), z_out.data_ptr() if z_out is not None else None,
                                               a, b, _dt(x.dtype), key, nonce, M, bits.data_ptr(),

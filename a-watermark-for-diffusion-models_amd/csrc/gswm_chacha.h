@@ -1,5 +1,7 @@
-// gswm_chacha.h -- the ChaCha20 block function of the codec kernels, shared by gswm_kernels.hip (keystream, embed, extract) and
-// gswm_keyed.hip (per-record keystreams of the keyed registry search).  Device code only; include after <hip/hip_runtime.h>.
+// gswm_chacha.h -- the ChaCha20 block function of the codec family.  chacha20_block computes one block of a cipher whose words a lane
+// holds as a CipherLane (cipher_lane_of_record: the per-record codec, the keyed registry search, the tile kernels);
+// chacha20_blocks_to_lds is the shared-key kernels' loop (keystream, embed, extract), whose cipher words are kernel arguments and whose
+// instruction stream the benchmark times: it keeps its own copy of the rounds.  Device code only; include after <hip/hip_runtime.h>.
 #pragma once
 #include <stdint.h>
 
@@ -26,10 +28,45 @@ __device__ __forceinline__ uint32_t quad_perm(uint32_t v) {
     a += b; d = rotl32(d ^ a, 8);  \
     c += d; b = rotl32(b ^ c, 7);
 
+// A lane's share of a cipher: column `col` of the initial state below the sigma row (which is a function of col alone and so not kept
+// here: a loop that walks records would carry it along), the counter as the 64-bit number it is (state words 12 and 13: the 32-bit
+// counter carries into the next word, as OpenSSL's) and the lane's word of the nonce tail.
+struct CipherLane {
+    uint32_t b0, c0;   // key words col, 4 + col
+    uint32_t n0, n1;   // initial counter, low and high word
+    uint32_t n23;      // state word 12 + col of the lanes col = 2, 3 (nonce16 words 2, 3); the other two lanes do not use it
+};
+
+// A lane's share of the cipher of a record head key[32] | nonce16[16] in memory (4-byte aligned), as 32-bit loads by lane `col`.
+__device__ __forceinline__ CipherLane cipher_lane_of_record(const uint32_t* __restrict__ rec, uint32_t col) {
+    return CipherLane{rec[col], rec[4 + col], rec[8], rec[9], rec[8 + (col | 2u)]};
+}
+
+// ChaCha20 block `initial counter + block` of a cipher, four lanes per block: lane col of the quad returns words col, 4 + col, 8 + col,
+// 12 + col of the block, i.e. bytes 16 r + 4 col .. + 3 for r = 0 .. 3.  All four lanes of the quad call it together.
+// The counter rule and the rounds are written out in two more places, which change together with this one: chacha20_blocks_to_lds below
+// and the record loop of gsw_trace_keyed_scan_kernel (gswm_keyed.hip); each says why.
+__device__ __forceinline__ void chacha20_block(const CipherLane ck, uint64_t block, uint32_t col, uint32_t (&ks)[4]) {
+    const uint32_t a0 = col == 0 ? 0x61707865u : col == 1 ? 0x3320646eu : col == 2 ? 0x79622d32u : 0x6b206574u;
+    const uint64_t ctr = (((uint64_t)ck.n1 << 32) | ck.n0) + block;
+    const uint32_t d0 = col == 0 ? (uint32_t)ctr : col == 1 ? (uint32_t)(ctr >> 32) : ck.n23;
+    uint32_t a = a0, b = ck.b0, c = ck.c0, d = d0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        CHACHA_QR(a, b, c, d)
+        b = quad_perm<QP_ROT1>(b); c = quad_perm<QP_ROT2>(c); d = quad_perm<QP_ROT3>(d);
+        CHACHA_QR(a, b, c, d)
+        b = quad_perm<QP_ROT3>(b); c = quad_perm<QP_ROT2>(c); d = quad_perm<QP_ROT1>(d);
+    }
+    ks[0] = a + a0; ks[1] = b + ck.b0; ks[2] = c + ck.c0; ks[3] = d + d0;
+}
+
 // Computes ChaCha20 blocks [first_block, first_block + nblocks) into ks_words[nblocks*16] (LDS), using every lane
 // of the workgroup in quads.  All lanes of a participating quad are active together (4 | blockDim, tid-contiguous).
 // The cipher words are taken BY VALUE (SGPRs): handing the by-value kernel-argument struct around by reference
 // makes clang materialise it in scratch.
+// Written out, not as a loop over chacha20_block: these are the kernels the benchmark times, and gathering the lane's words in a
+// CipherLane first gives every one of them a different instruction stream (profiles/record_refactor_resources.txt).
 struct CipherRegs {
     uint32_t k0, k1, k2, k3, k4, k5, k6, k7, n0, n1, n2, n3;
 };

@@ -4,7 +4,8 @@
 // is bit for bit what gsw_embed[_l] / gsw_extract[_l] give for that one image under record b.
 //
 // Records (gsw_trace_keyed_topk's rows): uint8 [B, stride], 16-byte aligned, stride % 16 == 0, a row is key[32] | nonce16[16] |
-// msg[msg_bytes].  Key, nonce and message words are read from the row with ordinary vector loads by the lanes that need them.
+// msg[msg_bytes] (gswm_record.h: layout, operand check, the repeated message, the vote tail).  Key, nonce and message words are read
+// from the row with ordinary vector loads by the lanes that need them; the block function is gswm_chacha.h's chacha20_block.
 //
 // Cipher bits of image b: the keystream of record b (initial counter nonce16[0:8] as a 64-bit little-endian number, so the 32-bit
 // counter carries into the next word, as gsw_keystream) XOR the message repeated floor(Nb / (8 msg_bytes)) times, then zeros.  Cipher
@@ -30,28 +31,6 @@
 // as 0, except at l = 1 where gsw_extract takes its wave vote, which goes by the sign bit (nan_ones8).
 
 namespace codec_keyed {
-
-constexpr uint32_t KR_HEAD = 48;                  // key[32] | nonce16[16]
-constexpr int64_t KR_MAX_BITS = 1048576;          // extract: one image's row is staged in 128 KiB of LDS
-
-// The ChaCha20 block `ctr_base + block` of the record at `rec`, four lanes per block (gswm_chacha.h): lane col of the quad returns words
-// col, 4 + col, 8 + col, 12 + col of the block, i.e. bytes 16 r + 4 col .. + 3 for r = 0 .. 3.  All four lanes of the quad call it together.
-__device__ __forceinline__ void record_block(const uint32_t* __restrict__ rec, uint64_t block, uint32_t col, uint32_t (&ks)[4]) {
-    const uint32_t a0 = col == 0 ? 0x61707865u : col == 1 ? 0x3320646eu : col == 2 ? 0x79622d32u : 0x6b206574u;
-    const uint32_t b0 = rec[col], c0 = rec[4 + col];
-    const uint32_t n0 = rec[8], n1 = rec[9], n23 = rec[8 + (col | 2u)];
-    const uint64_t ctr = (((uint64_t)n1 << 32) | n0) + block;
-    const uint32_t d0 = col == 0 ? (uint32_t)ctr : col == 1 ? (uint32_t)(ctr >> 32) : n23;
-    uint32_t a = a0, b = b0, c = c0, d = d0;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        CHACHA_QR(a, b, c, d)
-        b = quad_perm<QP_ROT1>(b); c = quad_perm<QP_ROT2>(c); d = quad_perm<QP_ROT3>(d);
-        CHACHA_QR(a, b, c, d)
-        b = quad_perm<QP_ROT3>(b); c = quad_perm<QP_ROT2>(c); d = quad_perm<QP_ROT1>(d);
-    }
-    ks[0] = a + a0; ks[1] = b + b0; ks[2] = c + c0; ks[3] = d + d0;
-}
 
 struct EmbedKeyedArgs {
     const uint8_t* records; // [B][stride]
@@ -94,17 +73,14 @@ __global__ __launch_bounds__(GSW_WG) void gsw_embed_keyed_kernel(EmbedKeyedArgs 
         if (q_img < gcount && q_blk < nblk) {      // the same for the four lanes of a quad
             const uint8_t* rec = p.records + (int64_t)(b0 + (int)q_img) * p.stride;
             uint32_t ks[4];
-            record_block(reinterpret_cast<const uint32_t*>(rec), (uint64_t)chunk * BLKS + q_blk, col, ks);
-            const uint8_t* msg = rec + KR_HEAD;
+            chacha20_block(cipher_lane_of_record(reinterpret_cast<const uint32_t*>(rec), col), (uint64_t)chunk * BLKS + q_blk, col, ks);
+            const uint8_t* msg = rec + GSW_REC_HEAD;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const uint32_t g0 = chunk * (64u * BLKS) + 64u * q_blk + 16u * r + 4u * col;   // cipher byte of the image, < 2^28
-                uint32_t o = g0 % p.msg_bytes, m = 0u;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if ((g0 + i) * 8u < p.lim_bits) m |= (uint32_t)msg[o] << (8 * i);
-                    o = o + 1u == p.msg_bytes ? 0u : o + 1u;
-                }
+                // the message ends with its last whole copy: byte g takes it iff 8 g < lim_bits, and lim_bits (whole copies of whole
+                // bytes) is a multiple of 8, so the bytes g0 + i < lim_bits / 8 are the first lim_bits / 8 - g0 of the word
+                const uint32_t m = repeated_msg_word(msg, g0 % p.msg_bytes, p.msg_bytes, false, (int)(p.lim_bits >> 3) - (int)g0);
                 cw_words[q_img * CW + q_blk * 16u + 4u * r + col] = ks[r] ^ m;
             }
         }
@@ -176,18 +152,13 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_keyed_kernel(ExtractKeyedA
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // the row: keystream, then decrypted bits, p.nblk * 16 words
     __shared__ uint32_t s_flags[GSW_WG / 64];
     __shared__ uint32_t s_match[GSW_MSG_INLINE_MAX];                 // matching bits per message byte
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = tid & 3u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t b = blockIdx.x;
     const uint32_t N = p.n_elems, M = p.msg_bytes * 8u;
     const uint8_t* rec = p.records + (int64_t)b * p.stride;
     uint8_t* row = reinterpret_cast<uint8_t*>(lds);
 
-    for (uint32_t blk = tid >> 2; blk < p.nblk; blk += GSW_WG >> 2) {
-        uint32_t ks[4];
-        record_block(reinterpret_cast<const uint32_t*>(rec), (uint64_t)blk, col, ks);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[16u * blk + 4u * r + col] = ks[r];
-    }
+    record_keystream_to_lds<GSW_WG>(rec, p.nblk, lds);
     __syncthreads();
 
     const size_t base = (size_t)b * N;
@@ -232,24 +203,14 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_keyed_kernel(ExtractKeyedA
         if (t < M && s == 0) {
             if (p.counts) p.counts[(size_t)b * M + t] = c1;
             if ((t & 7u) == 0) {                                     // the seven bits after t are this wave's as well
-                uint32_t v = 0u;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v |= (uint32_t)((ball >> (lane + ((uint32_t)i << p.log2s))) & 1ull) << (7 - i);
+                const uint32_t v = ballot_byte(ball, lane, p.log2s);
                 p.bits[(size_t)b * p.msg_bytes + (t >> 3)] = (uint8_t)v;
-                s_match[t >> 3] = 8u - __popc(v ^ (uint32_t)rec[KR_HEAD + (t >> 3)]);
+                s_match[t >> 3] = 8u - __popc(v ^ (uint32_t)rec[GSW_REC_HEAD + (t >> 3)]);
             }
         }
     }
     __syncthreads();
-    if (tid < 64u) {
-        uint32_t m = 0;
-        for (uint32_t i = tid; i < p.msg_bytes; i += 64u) m += s_match[i];
-        for (int sh = 32; sh > 0; sh >>= 1) m += __shfl_xor(m, sh, 64);
-        if (tid == 0) {
-            if (p.matches) p.matches[b] = m;
-            p.flags[b] = s_flags[0] | s_flags[1] | s_flags[2] | s_flags[3];
-        }
-    }
+    store_matches_flags<GSW_WG / 64>(s_match, s_flags, p.msg_bytes, p.matches, p.flags, b);
 }
 
 template <typename OutT, int L>
@@ -276,7 +237,7 @@ static void launch_embed_dtype(const EmbedKeyedArgs& a, int out_dtype, bool has_
 template <typename T, int L>
 static int launch_extract(const ExtractKeyedArgs& a, int B, hipStream_t st) {
     const uint32_t lds = a.nblk * 64u;
-    if (lds > 48u * 1024u) GSW_HIP(hipFuncSetAttribute((const void*)gsw_extract_keyed_kernel<T, L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_keyed_kernel<T, L>, lds));
     hipLaunchKernelGGL((gsw_extract_keyed_kernel<T, L>), dim3((uint32_t)B), dim3(GSW_WG), lds, st, a);
     GSW_HIP(hipGetLastError());
     return GSW_OK;
@@ -292,20 +253,11 @@ static int launch_extract_dtype(const ExtractKeyedArgs& a, int dtype, int B, hip
     }
 }
 
-// what both entry points ask of the records and the batch
-static int records_check(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int B) {
-    if (!records_dev || B < 1) return GSW_ERR_BAD_ARG;
-    if (msg_bytes < 1 || msg_bytes > GSW_MSG_INLINE_MAX) return GSW_ERR_BAD_ARG;
-    if (record_stride < (int64_t)KR_HEAD + msg_bytes || record_stride % 16 || record_stride > (int64_t)0x7FFFFFF0) return GSW_ERR_BAD_ARG;
-    if ((uintptr_t)records_dev & 15u) return GSW_ERR_BAD_ARG;
-    return GSW_OK;
-}
-
 }  // namespace codec_keyed
 
 int gsw_embed_keyed(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const double* u_dev, uint64_t seed,
                     uint64_t image_index0, void* out_dev, int out_dtype, int B, int64_t n_elems, uint32_t flags, int l, void* stream) {
-    const int rc = codec_keyed::records_check(records_dev, record_stride, msg_bytes, B);
+    const int rc = records_check32(records_dev, record_stride, msg_bytes, B);
     if (rc != GSW_OK) return rc;
     if (!out_dev || n_elems <= 0 || (n_elems & 3)) return GSW_ERR_BAD_ARG;
     if (out_dtype < GSW_F32 || out_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
@@ -345,15 +297,15 @@ int gsw_embed_keyed(const uint8_t* records_dev, int64_t record_stride, int msg_b
 
 int gsw_extract_keyed(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, uint8_t* bits_dev,
                       uint32_t* counts_dev, uint32_t* flags_dev, uint32_t* matches_dev, int B, int64_t n_elems, int l, void* stream) {
-    const int rc = codec_keyed::records_check(records_dev, record_stride, msg_bytes, B);
+    const int rc = records_check32(records_dev, record_stride, msg_bytes, B);
     if (rc != GSW_OK) return rc;
     if (!z_dev || !bits_dev || !flags_dev || n_elems <= 0) return GSW_ERR_BAD_ARG;
     if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
     if ((uintptr_t)z_dev & 15u) return GSW_ERR_BAD_ARG;                                      // 16-byte loads
     if (l != 1 && l != 2 && l != 4) return GSW_ERR_UNSUPPORTED;
-    if (n_elems > codec_keyed::KR_MAX_BITS) return GSW_ERR_UNSUPPORTED;
+    if (n_elems > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;
     const int64_t nbits = n_elems * l, msg_bits = (int64_t)msg_bytes * 8;
-    if (nbits % 8 || nbits > codec_keyed::KR_MAX_BITS) return GSW_ERR_UNSUPPORTED;
+    if (nbits % 8 || nbits > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;
     if (nbits % msg_bits) return GSW_ERR_RAGGED;
     codec_keyed::ExtractKeyedArgs a;
     memset(&a, 0, sizeof(a));
@@ -368,8 +320,7 @@ int gsw_extract_keyed(const void* z_dev, int z_dtype, const uint8_t* records_dev
     a.msg_bytes = (uint32_t)msg_bytes;
     a.nblk = (uint32_t)((((n_elems + 7) / 8) * l + 63) / 64);      // whole groups of eight elements are staged
     a.copies = (uint32_t)(nbits / msg_bits);
-    // lanes per message bit: enough to fill the workgroup for short messages, at most 8 (a wave then still owns whole bytes) and at most the copies
-    while (a.log2s < 3 && ((uint32_t)msg_bits << a.log2s) < GSW_WG && (2u << a.log2s) <= a.copies) ++a.log2s;
+    a.log2s = (uint32_t)vote_log2s(msg_bits, a.copies, GSW_WG);
     a.thr = make_thr(z_dtype);
     a.nan_by_sign = l == 1 && extract_votes_by_wave((uint32_t)n_elems, (uint32_t)msg_bits);
     hipStream_t st = (hipStream_t)stream;

@@ -377,7 +377,7 @@ static int launch_extract_l(const ExtractLArgs& a, hipStream_t st) {
     const size_t lds = (size_t)((gbytes + 63u) / 64u) * 64u + (size_t)((gbytes + 3u) / 4u) * 4u + (size_t)((a.msg_bits + 31u) / 32u) * 4u;
     if (lds > GSW_MAX_DYN_LDS) return GSW_ERR_UNSUPPORTED;
     const uint32_t grid = (uint32_t)std::min<int64_t>(a.B, (int64_t)device_cus() * 8);
-    if (lds > 48u * 1024u) GSW_HIP(hipFuncSetAttribute((const void*)gsw_extract_l_kernel<T, L>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_l_kernel<T, L>, lds));
     hipLaunchKernelGGL((gsw_extract_l_kernel<T, L>), dim3(grid), dim3(GSW_WG), lds, st, a);
     GSW_HIP(hipGetLastError());
     return GSW_OK;

@@ -1,6 +1,6 @@
 // gswm_codec_soft.inc -- the soft-decision vote: every lattice element votes with an integer reliability level taken from its magnitude,
 // B images under their own records in one launch (gfx950).  Included at the end of gswm_kernels.hip, after gswm_codec_keyed.inc: records,
-// keystream and its LDS staging are gsw_extract_keyed's own (codec_keyed::record_block, records_check), the hard bit q_j is gsw_extract's
+// keystream, its LDS staging and the end of the vote are gsw_extract_keyed's own (gswm_record.h), the hard bit q_j is gsw_extract's
 // quantiser (quantise8 / quantise8d), l = 1 only.
 //
 // Definition, image b with thresholds thr[b][0 .. levels) (fp32; row b * thr_stride of thr_dev, thr_stride == 0: one row for all), M = 8 msg_bytes:
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
     __shared__ float s_thr[SOFT_MAX_LEVELS + 1];                     // the row in ascending order, NaNs and the padding last
     __shared__ uint32_t s_flags[GSW_WG / 64], s_wsq[GSW_WG / 64];
     __shared__ uint32_t s_match[GSW_MSG_INLINE_MAX];                 // matching bits per message byte
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, col = tid & 3u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t b = blockIdx.x;
     const uint32_t N = p.n_elems, P = p.msg_bytes, M = P * 8u;
     const uint8_t* rec = p.records + (int64_t)b * p.stride;
@@ -100,12 +100,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
         }
         s_thr[rank] = t;
     }
-    for (uint32_t blk = tid >> 2; blk < p.nblk; blk += GSW_WG >> 2) {
-        uint32_t ks[4];
-        codec_keyed::record_block(reinterpret_cast<const uint32_t*>(rec), (uint64_t)blk, col, ks);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) lds[16u * blk + 4u * r + col] = ks[r];
-    }
+    record_keystream_to_lds<GSW_WG>(rec, p.nblk, lds);
     __syncthreads();
 
     const T* z = reinterpret_cast<const T*>(p.z) + (size_t)b * N;
@@ -151,30 +146,20 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
         }
         const uint64_t ball = __ballot(t < M && s > 0);              // ties and no weight -> 0
         if (t < M && (t & 7u) == 0) {                                // M % 8 == 0: the seven bits after t are this wave's as well
-            uint32_t v = 0u;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) v |= (uint32_t)((ball >> (lane + (uint32_t)i)) & 1ull) << (7 - i);
+            const uint32_t v = ballot_byte(ball, lane, 0u);
             p.bits[(size_t)b * P + (t >> 3)] = (uint8_t)v;
-            s_match[t >> 3] = 8u - __popc(v ^ (uint32_t)rec[codec_keyed::KR_HEAD + (t >> 3)]);
+            s_match[t >> 3] = 8u - __popc(v ^ (uint32_t)rec[GSW_REC_HEAD + (t >> 3)]);
         }
     }
     __syncthreads();
-    if (tid < 64u) {
-        uint32_t m = 0;
-        for (uint32_t i = tid; i < P; i += 64u) m += s_match[i];
-        for (int sh = 32; sh > 0; sh >>= 1) m += __shfl_xor(m, sh, 64);
-        if (tid == 0) {
-            if (p.matches) p.matches[b] = m;
-            if (p.wsq) p.wsq[b] = (int32_t)(s_wsq[0] + s_wsq[1] + s_wsq[2] + s_wsq[3]);
-            p.flags[b] = s_flags[0] | s_flags[1] | s_flags[2] | s_flags[3];
-        }
-    }
+    store_matches_flags<GSW_WG / 64>(s_match, s_flags, P, p.matches, p.flags, b);
+    if (tid == 0 && p.wsq) p.wsq[b] = (int32_t)(s_wsq[0] + s_wsq[1] + s_wsq[2] + s_wsq[3]);
 }
 
 template <typename T, int STEPS>
 static int launch_soft_steps(const ExtractSoftArgs& a, int B, hipStream_t st) {
     const uint32_t lds = a.nblk * 64u;
-    if (lds > 32u * 1024u) GSW_HIP(hipFuncSetAttribute((const void*)gsw_extract_soft_kernel<T, STEPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_soft_kernel<T, STEPS>, lds, 32u * 1024u));   // next to 17.1 KiB of static LDS
     hipLaunchKernelGGL((gsw_extract_soft_kernel<T, STEPS>), dim3((uint32_t)B), dim3(GSW_WG), lds, st, a);
     GSW_HIP(hipGetLastError());
     return GSW_OK;
@@ -193,7 +178,7 @@ static int launch_soft(const ExtractSoftArgs& a, int B, hipStream_t st) {
 int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
                      int64_t thr_stride, int levels, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,
                      uint32_t* flags_dev, uint32_t* matches_dev, int B, int64_t n_elems, void* stream) {
-    const int rc = codec_keyed::records_check(records_dev, record_stride, msg_bytes, B);
+    const int rc = records_check32(records_dev, record_stride, msg_bytes, B);
     if (rc != GSW_OK) return rc;
     if (!z_dev || !thr_dev || !bits_dev || !flags_dev || n_elems <= 0) return GSW_ERR_BAD_ARG;
     if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
@@ -201,7 +186,7 @@ int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev,
     if ((uintptr_t)thr_dev & 3u) return GSW_ERR_BAD_ARG;
     if (levels < 1 || levels > codec_soft::SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
     if (thr_stride != 0 && thr_stride < levels) return GSW_ERR_BAD_ARG;
-    if (n_elems % 8 || n_elems > codec_keyed::KR_MAX_BITS) return GSW_ERR_UNSUPPORTED;
+    if (n_elems % 8 || n_elems > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;
     if (n_elems % ((int64_t)msg_bytes * 8)) return GSW_ERR_RAGGED;
     codec_soft::ExtractSoftArgs a;
     memset(&a, 0, sizeof(a));

@@ -44,7 +44,9 @@ struct GswMsgInline {
     uint8_t b[GSW_MSG_INLINE_MAX];
 };
 
-#include "gswm_chacha.h"   // ChaCha20, four lanes per 64-byte block: CipherRegs, chacha20_blocks_to_lds
+#include "gswm_chacha.h"   // ChaCha20, four lanes per 64-byte block: CipherRegs, chacha20_block, chacha20_blocks_to_lds
+#include "gswm_record.h"   // one record per image: layout, operand check, repeated message, vote tail
+#include "gswm_host.h"     // GSW_HIP, hip_fail, device_cus, allow_dynamic_lds
 
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-R (in-kernel uniform source; NOT reference behaviour -- the reference draws from numpy's
@@ -1232,13 +1234,7 @@ __global__ __launch_bounds__(256) void gsw_mt19937_kernel(Mt19937State st, int32
     }
 }
 
-__attribute__((visibility("hidden"))) thread_local int g_last_hip_error = 0;   // shared with gswm_conv.hip / gswm_image.hip
-
-static inline int hip_fail(hipError_t e) {
-    g_last_hip_error = (int)e;
-    return GSW_ERR_HIP;
-}
-#define GSW_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) return hip_fail(_e); } while (0)
+__attribute__((visibility("hidden"))) thread_local int g_last_hip_error = 0;   // declared in gswm_host.h; shared with gswm_conv.hip / gswm_image.hip
 
 static inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 
@@ -1275,16 +1271,6 @@ static Thr make_thr(int dtype) {
             t.nz_add = 0x7FFFFFFFu - t1_32; t.sat_bits = sat_32; break;
     }
     return t;
-}
-
-static int device_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-        else cus = 256;
-    }
-    return cus;
 }
 
 // The public functions below get C linkage from their declarations in include/gswm.h.
@@ -1422,7 +1408,7 @@ static int launch_extract_wave(const ExtractArgs& a, const Src& src, size_t lds,
     const uint32_t waves = block / 64u;
     const uint32_t max_grid = (uint32_t)device_cus() * (2048u / block);
     const uint32_t grid = std::max<uint32_t>(1u, std::min<uint32_t>(((uint32_t)a.B + waves - 1u) / waves, max_grid));
-    if (lds > 48u * 1024u) GSW_HIP(hipFuncSetAttribute((const void*)gsw_extract_wave_kernel<Src, NSETS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_wave_kernel<Src, NSETS>, lds));
     hipLaunchKernelGGL((gsw_extract_wave_kernel<Src, NSETS>), dim3(grid), dim3(block), lds, st, a, src);
     GSW_HIP(hipGetLastError());
     return GSW_OK;
@@ -1456,7 +1442,7 @@ static int launch_extract(const ExtractArgs& a, const Src& src, hipStream_t st) 
     const uint32_t grid = (uint32_t)std::min<int64_t>(a.B, (int64_t)device_cus() * 8);
     const size_t lds = (size_t)nblk * 64u + (size_t)((nbytes + 3u) / 4u) * 4u + (size_t)((M + 31u) / 32u) * 4u;
     if (lds > GSW_MAX_DYN_LDS) return GSW_ERR_UNSUPPORTED;
-    if (lds > 48u * 1024u) GSW_HIP(hipFuncSetAttribute((const void*)gsw_extract_generic_kernel<Src>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_generic_kernel<Src>, lds));
     hipLaunchKernelGGL((gsw_extract_generic_kernel<Src>), dim3(grid), dim3(GSW_WG), lds, st, a, src);
     GSW_HIP(hipGetLastError());
     return GSW_OK;

@@ -44,21 +44,16 @@
 #include <cstdint>
 
 #include "../../include/gswm.h"
-#include "gswm_chacha.h"
+#include "gswm_host.h"     // GSW_HIP, allow_dynamic_lds
+#include "gswm_record.h"   // the record: GSW_REC_HEAD, GSW_ROW_MAX_BITS, records_check (and gswm_chacha.h: CHACHA_QR, quad_perm)
 #include "gswm_topk.h"
-
-extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip; read by gsw_last_hip_error()
-
-#define GSW_KEYED_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_last_hip_error = (int)_e; return GSW_ERR_HIP; } } while (0)
 
 namespace {
 
 constexpr int KY_WAVES = 8;
 constexpr int KY_WG = 64 * KY_WAVES;
 constexpr int KY_MAX_GRID_X = 512;                   // record ranges (two rounds of one workgroup per CU at the largest tiles)
-constexpr uint32_t KY_TILE_LDS = 128u * 1024u;       // sign rows of one image tile
-constexpr int64_t KY_MAX_BITS = (int64_t)KY_TILE_LDS * 8;   // one image per workgroup: 1 048 576 lattice bits
-constexpr int KY_REC_HEAD = 48;                      // key[32] | nonce16[16]
+constexpr uint32_t KY_TILE_LDS = (uint32_t)(GSW_ROW_MAX_BITS / 8);   // sign rows of one image tile: one image of the largest lattice
 
 struct KeyedArgs {
     const uint8_t* signs;     // [B, rowbytes]
@@ -113,6 +108,11 @@ __device__ __forceinline__ int lane_image(int lane) {
     return img;
 }
 
+// The record loop keeps its own copy of the block function (gswm_chacha.h's chacha20_block, with the prefetched words in a CipherLane) and
+// of the repeated message word (gswm_record.h's repeated_msg_word): moved onto the shared helpers the T = 64 instantiation ran 3 to 15 %
+// slower on the MI355X (the table of the discarded helper version in profiles/record_refactor_ab.txt), for a reason the resource figures
+// do not show.  A change to the counter rule or the record head is made here, in chacha20_block and in chacha20_blocks_to_lds.  The tail
+// after the loop is gswm_topk.h's.
 template <int T, bool MSG4>
 __global__ __launch_bounds__(KY_WG) void gsw_trace_keyed_scan_kernel(KeyedArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(KY_WG) void gsw_trace_keyed_scan_kernel(KeyedArgs a
     for (int64_t u = u0 + wave; u < u1; u += KY_WAVES) {
         nb0 = b0; nc0 = c0; nnonce = nonce;
         if (u + KY_WAVES < u1) fetch(u + KY_WAVES, nb0, nc0, nnonce);     // the next record's cipher words, under this one's rounds
-        const uint8_t* msg = a.records + u * a.stride + KY_REC_HEAD;
+        const uint8_t* msg = a.records + u * a.stride + GSW_REC_HEAD;
         const uint64_t ctr_base = ((uint64_t)nonce.y << 32) | nonce.x;      // 32-bit initial counter, the carry goes into the next word
         int acc[T];
 #pragma unroll
@@ -237,39 +237,16 @@ __global__ __launch_bounds__(KY_WG) void gsw_trace_keyed_scan_kernel(KeyedArgs a
     // ---- one list per (wave, image) -> LDS -> one per (workgroup, image)
     __syncthreads();                                   // every wave is done with the sign rows: reuse the LDS
     int64_t* wlist = (int64_t*)lds_raw;                // [KY_WAVES][T][TR_LIST]
-    if (lane < T) {
-#pragma unroll
-        for (int j = 0; j < TR_LIST; ++j) wlist[(wave * T + img) * TR_LIST + j] = L[j];
-    }
+    if (lane < T) put_list(wlist, wave * T + img, L);
     __syncthreads();
-    if (tid < T) {
-        int64_t F[TR_LIST];
-#pragma unroll
-        for (int j = 0; j < TR_LIST; ++j) F[j] = wlist[tid * TR_LIST + j];
-        for (int w = 1; w < KY_WAVES; ++w)
-#pragma unroll
-            for (int j = 0; j < TR_LIST; ++j) list_insert(F, wlist[(w * T + tid) * TR_LIST + j]);
-        const int b = img0 + tid;
-        if (b < a.B) {
-            int64_t* dst = a.partial + ((int64_t)b * a.grid_x + blockIdx.x) * a.k;
-#pragma unroll
-            for (int j = 0; j < TR_LIST; ++j)
-                if (j < a.k) dst[j] = F[j];
-        }
-    }
+    workgroup_lists_to_partial<KY_WAVES, T>(wlist, img0, a.B, a.partial, a.grid_x, a.k);
 }
 
 // one wave per image: the k largest keys of the partial lists
 __global__ __launch_bounds__(64) void gsw_trace_keyed_finish_kernel(KeyedArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int64_t L[TR_LIST];
-#pragma unroll
-    for (int j = 0; j < TR_LIST; ++j) L[j] = TR_EMPTY;
-    const int64_t* src = a.partial + (int64_t)b * a.grid_x * a.k;
-    const int n = a.grid_x * a.k;
-    for (int i = lane; i < n; i += 64) list_insert(L, src[i]);
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) merge_from_lane_xor(L, step);
+    wave_merge_partial(L, a.partial + (int64_t)b * a.grid_x * a.k, a.grid_x * a.k, lane);
     if (lane == 0) {
 #pragma unroll
         for (int j = 0; j < TR_LIST; ++j) {
@@ -297,9 +274,9 @@ int tile_images(int B, int nblk) {
 template <int T, bool MSG4>
 int launch_scan(const KeyedArgs& a, hipStream_t st) {
     const uint32_t lds = std::max<uint32_t>((uint32_t)T * (uint32_t)a.nblk * 64u, (uint32_t)(KY_WAVES * T * TR_LIST * sizeof(int64_t)));
-    if (lds > 48u * 1024u) GSW_KEYED_HIP(hipFuncSetAttribute((const void*)gsw_trace_keyed_scan_kernel<T, MSG4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_trace_keyed_scan_kernel<T, MSG4>, lds));
     hipLaunchKernelGGL((gsw_trace_keyed_scan_kernel<T, MSG4>), dim3(a.grid_x, (a.B + T - 1) / T), dim3(KY_WG), lds, st, a);
-    GSW_KEYED_HIP(hipGetLastError());
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -324,12 +301,12 @@ size_t gsw_trace_keyed_workspace_bytes(int B, int64_t n_records, int k) {
 
 int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
                          int64_t n_records, int k, int32_t* idx_dev, int32_t* score_dev, void* workspace_dev, void* stream) {
-    if (!signs_dev || !records_dev || !idx_dev || !score_dev || !workspace_dev) return GSW_ERR_BAD_ARG;
-    if (B < 1 || k < 1 || k > TR_LIST || msg_bytes < 1 || msg_bytes > GSW_MSG_INLINE_MAX || n_bits < 1) return GSW_ERR_BAD_ARG;
-    if (n_records < 1 || n_records > (int64_t)INT32_MAX) return GSW_ERR_BAD_ARG;
-    if (record_stride < KY_REC_HEAD + msg_bytes || (record_stride & 15) || ((uintptr_t)records_dev & 15)) return GSW_ERR_BAD_ARG;
+    if (!signs_dev || !idx_dev || !score_dev || !workspace_dev) return GSW_ERR_BAD_ARG;
+    if (B < 1 || k < 1 || k > TR_LIST || n_bits < 1 || n_records > (int64_t)INT32_MAX) return GSW_ERR_BAD_ARG;
+    int rc = records_check(records_dev, record_stride, msg_bytes, n_records);
+    if (rc != GSW_OK) return rc;
     if (n_bits % (8 * (int64_t)msg_bytes)) return GSW_ERR_RAGGED;
-    if (n_bits > KY_MAX_BITS || B > 65535) return GSW_ERR_UNSUPPORTED;
+    if (n_bits > GSW_ROW_MAX_BITS || B > 65535) return GSW_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     KeyedArgs a;
     a.signs = signs_dev;
@@ -346,10 +323,10 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
     a.grid_x = grid_x_for(n_records);
     a.signs_aligned = (a.rowbytes % 4 == 0) && ((uintptr_t)signs_dev % 4 == 0);
     const int t = tile_images(B, a.nblk);
-    const int rc = (msg_bytes % 4 == 0) ? launch_scan_tile<true>(a, t, st) : launch_scan_tile<false>(a, t, st);
+    rc = (msg_bytes % 4 == 0) ? launch_scan_tile<true>(a, t, st) : launch_scan_tile<false>(a, t, st);
     if (rc != GSW_OK) return rc;
     hipLaunchKernelGGL(gsw_trace_keyed_finish_kernel, dim3(B), dim3(64), 0, st, a);
-    GSW_KEYED_HIP(hipGetLastError());
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 

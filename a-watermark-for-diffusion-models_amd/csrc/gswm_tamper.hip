@@ -10,7 +10,7 @@
 //   bit_t    = score > 0                                          (a tie or no weight at all -> 0, the reference's tie rule)
 //
 // One workgroup per image, every image under its own key.  Both kernels start the same way: the quads of the workgroup compute the
-// ChaCha20 blocks of the image's keystream with the four-lanes-per-block code of gswm_chacha.h and, still in registers, XOR them with
+// ChaCha20 blocks of the image's keystream with gswm_chacha.h's chacha20_block and, still in registers, XOR them with
 // the packed row (and, for the map, the message): what reaches LDS is the row of differences d = q ^ cw (map) or of decrypted bits p
 // (vote), in the row's own byte order.  No keystream and no codeword exists in memory.  h and w are multiples of T and T of 8, so a
 // row is a whole number of dwords and the T l bits a tile owns of one lattice row are T l / 8 whole bytes, aligned to their own size.
@@ -35,18 +35,13 @@
 #include <cstdint>
 
 #include "../../include/gswm.h"
-#include "gswm_chacha.h"
-
-extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip; read by gsw_last_hip_error()
-
-#define GSW_TAMPER_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_last_hip_error = (int)_e; return GSW_ERR_HIP; } } while (0)
+#include "gswm_host.h"     // GSW_HIP, allow_dynamic_lds
+#include "gswm_record.h"   // the record head (a row of `keys`), GSW_ROW_MAX_BITS, repeated_msg_word, the vote tail
 
 namespace {
 
 constexpr int TM_WG = 256;
 constexpr int TM_TILE_LANES = 8;                     // lanes per tile of the map
-constexpr int64_t TM_MAX_BITS = 1048576;             // one image's row is staged in 128 KiB of LDS
-constexpr int TM_KEY_BYTES = 48;                     // key[32] | nonce16[16]
 
 struct TamperArgs {
     const uint8_t* packed;    // [B, rowbytes]
@@ -73,46 +68,19 @@ struct TamperArgs {
 template <bool WITH_MSG>
 __device__ __forceinline__ void stage_row(const TamperArgs& a, int b, uint32_t* row_lds) {
     const int tid = threadIdx.x, col = tid & 3;
-    const uint32_t* rec = (const uint32_t*)(a.keys + (int64_t)b * TM_KEY_BYTES);
-    const uint32_t a0 = col == 0 ? 0x61707865u : col == 1 ? 0x3320646eu : col == 2 ? 0x79622d32u : 0x6b206574u;
-    const uint32_t b0 = rec[col], c0 = rec[4 + col];
-    const uint32_t n0 = rec[8], n1 = rec[9], n23 = rec[8 + (col | 2)];
-    const uint64_t ctr_base = ((uint64_t)n1 << 32) | n0;      // 32-bit initial counter, the carry goes into the next word
+    const CipherLane ck = cipher_lane_of_record((const uint32_t*)(a.keys + (int64_t)b * GSW_REC_HEAD), (uint32_t)col);
     const uint8_t* q = a.packed + (int64_t)b * a.rowbytes;
     const uint8_t* msg = WITH_MSG ? a.msg + (int64_t)b * a.msg_bytes : nullptr;
     for (int blk = tid >> 2; blk < a.nblk; blk += TM_WG >> 2) {
-        const uint64_t ctr = ctr_base + (uint64_t)blk;
-        const uint32_t d0 = col == 0 ? (uint32_t)ctr : col == 1 ? (uint32_t)(ctr >> 32) : n23;
-        uint32_t x = a0, y = b0, z = c0, d = d0;
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            CHACHA_QR(x, y, z, d)
-            y = quad_perm<QP_ROT1>(y); z = quad_perm<QP_ROT2>(z); d = quad_perm<QP_ROT3>(d);
-            CHACHA_QR(x, y, z, d)
-            y = quad_perm<QP_ROT3>(y); z = quad_perm<QP_ROT2>(z); d = quad_perm<QP_ROT1>(d);
-        }
-        const uint32_t ks[4] = {x + a0, y + b0, z + c0, d + d0};
+        uint32_t ks[4];
+        chacha20_block(ck, (uint64_t)blk, (uint32_t)col, ks);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int byte0 = 64 * blk + 16 * r + 4 * col;
             uint32_t v = 0u;
             if (byte0 < a.rowbytes) {
                 v = ks[r] ^ *(const uint32_t*)(q + byte0);
-                if constexpr (WITH_MSG) {
-                    int o = byte0 % a.msg_bytes;
-                    uint32_t m;
-                    if (a.msg_aligned) {
-                        m = *(const uint32_t*)(msg + o);
-                    } else {
-                        m = 0u;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            m |= (uint32_t)msg[o] << (8 * i);
-                            o = o + 1 == a.msg_bytes ? 0 : o + 1;
-                        }
-                    }
-                    v ^= m;
-                }
+                if constexpr (WITH_MSG) v ^= repeated_msg_word(msg, (uint32_t)(byte0 % a.msg_bytes), (uint32_t)a.msg_bytes, a.msg_aligned != 0);
             }
             row_lds[16 * blk + 4 * r + col] = v;
         }
@@ -191,10 +159,7 @@ __global__ __launch_bounds__(TM_WG) void gsw_vote_tiled_kernel(TamperArgs a) {
             score[t] = sc;
             wsum[t] = ws;
             if ((t & 7) == 0) {                        // msg_bits % 8 == 0: the seven bits after t are this wave's as well
-                uint32_t v = 0u;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) v |= (uint32_t)((ball >> (lane + (i << a.log2s))) & 1ull) << (7 - i);
-                bits[t >> 3] = (uint8_t)v;
+                bits[t >> 3] = (uint8_t)ballot_byte(ball, (uint32_t)lane, (uint32_t)a.log2s);
             }
         }
     }
@@ -215,7 +180,7 @@ int prepare(TamperArgs& a, const uint8_t* packed_dev, int B, int C, int h, int w
     if (tile != 8 && tile != 16 && tile != 32) return GSW_ERR_UNSUPPORTED;
     if (h % tile || w % tile || msg_bits % 8) return GSW_ERR_UNSUPPORTED;
     const int64_t nb = (int64_t)C * h * w * l;
-    if (nb > TM_MAX_BITS) return GSW_ERR_UNSUPPORTED;
+    if (nb > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;
     if (nb % msg_bits) return GSW_ERR_RAGGED;
     a = TamperArgs{};
     a.packed = packed_dev;
@@ -236,9 +201,9 @@ int prepare(TamperArgs& a, const uint8_t* packed_dev, int B, int C, int h, int w
 template <typename K>
 int launch(K kernel, const TamperArgs& a, int B, hipStream_t st) {
     const uint32_t lds = (uint32_t)a.nblk * 64u;
-    if (lds > 48u * 1024u) GSW_TAMPER_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)kernel, lds));
     hipLaunchKernelGGL(kernel, dim3(B), dim3(TM_WG), lds, st, a);
-    GSW_TAMPER_HIP(hipGetLastError());
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -270,9 +235,7 @@ int gsw_vote_tiled(const uint8_t* packed_dev, int B, int C, int h, int w, int l,
     a.bits = bits_dev;
     a.score = score_dev;
     a.wsum = wsum_dev;
-    // lanes per message bit: enough to fill the workgroup for short messages, at most 8 (a wave then still owns whole bytes) and at most the copies
-    a.log2s = 0;
-    while (a.log2s < 3 && (msg_bits << a.log2s) < TM_WG && (2 << a.log2s) <= a.copies) ++a.log2s;
+    a.log2s = vote_log2s(msg_bits, a.copies, TM_WG);
     return launch(gsw_vote_tiled_kernel, a, B, (hipStream_t)stream);
 }
 

@@ -41,11 +41,8 @@
 #include <cstdint>
 
 #include "../../include/gswm.h"
-#include "gswm_topk.h"   // TR_LIST, TR_EMPTY, make_key, list_insert, merge_from_lane_xor
-
-extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip; read by gsw_last_hip_error()
-
-#define GSW_TRACE_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_last_hip_error = (int)_e; return GSW_ERR_HIP; } } while (0)
+#include "gswm_host.h"   // GSW_HIP, allow_dynamic_lds
+#include "gswm_topk.h"   // TR_LIST, TR_EMPTY, make_key, list_insert, merge_from_lane_xor, workgroup_lists_to_partial, wave_merge_partial
 
 namespace {
 
@@ -244,39 +241,17 @@ __global__ __launch_bounds__(TR_WG) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     int64_t* wlist = (int64_t*)lds_raw;                // [4 waves][NT * 16 images][TR_LIST]
     if (lane < 16) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int j = 0; j < TR_LIST; ++j) wlist[((wave * NT + nt) * 16 + lane) * TR_LIST + j] = L[nt][j];
+        for (int nt = 0; nt < NT; ++nt) put_list(wlist, (wave * NT + nt) * 16 + lane, L[nt]);
     }
     __syncthreads();
-    if (tid < NT * 16) {
-        int64_t F[TR_LIST];
-#pragma unroll
-        for (int j = 0; j < TR_LIST; ++j) F[j] = wlist[tid * TR_LIST + j];
-        for (int w = 1; w < 4; ++w)
-#pragma unroll
-            for (int j = 0; j < TR_LIST; ++j) list_insert(F, wlist[(w * NT * 16 + tid) * TR_LIST + j]);
-        const int b = img0 + tid;
-        if (b < a.B) {
-            int64_t* dst = a.partial + ((int64_t)b * a.grid_x + blockIdx.x) * a.k;
-#pragma unroll
-            for (int j = 0; j < TR_LIST; ++j)
-                if (j < a.k) dst[j] = F[j];
-        }
-    }
+    workgroup_lists_to_partial<TR_WG / 64, NT * 16>(wlist, img0, a.B, a.partial, a.grid_x, a.k);
 }
 
 // one wave per image: the k largest keys of the partial lists, W = sum_t w, s = 2 R1 - W
 __global__ __launch_bounds__(64) void gsw_trace_finish_kernel(TraceArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     int64_t L[TR_LIST];
-#pragma unroll
-    for (int j = 0; j < TR_LIST; ++j) L[j] = TR_EMPTY;
-    const int64_t* src = a.partial + (int64_t)b * a.grid_x * a.k;
-    const int n = a.grid_x * a.k;
-    for (int i = lane; i < n; i += 64) list_insert(L, src[i]);
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) merge_from_lane_xor(L, step);
+    wave_merge_partial(L, a.partial + (int64_t)b * a.grid_x * a.k, a.grid_x * a.k, lane);
     int W = 0;
     for (int t = lane; t < a.M; t += 64) W += weight_of(a.counts[(int64_t)b * a.M + t], a.V, a.hard);
 #pragma unroll
@@ -301,16 +276,6 @@ __global__ __launch_bounds__(64) void gsw_trace_finish_kernel(TraceArgs a) {
     }
 }
 
-int device_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) cus = n;
-        else return 256;
-    }
-    return cus;
-}
-
 // Registries of TR_SAMPLE_FROM users and more are searched twice: first a sample (the first 1/64 of the rows, at least 65536), whose
 // k-th best R1 per image is a floor no member of the final k best can be below; with it the running lists of the full search change
 // a few hundred times per image instead of at every pass, and the search runs at the speed of its matrix and expansion work.
@@ -329,10 +294,10 @@ template <int NT, int P>
 int launch_scan(const TraceArgs& a, hipStream_t st) {
     const uint32_t lds = (uint32_t)a.nblk * 4u * NT * P * 1024u;          // >= the NT * 4 KiB the final merge needs
     if (lds > TR_MAX_LDS) return GSW_ERR_UNSUPPORTED;
-    if (lds > 48u * 1024u) GSW_TRACE_HIP(hipFuncSetAttribute((const void*)gsw_trace_scan_kernel<NT, P>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_trace_scan_kernel<NT, P>, lds));
     const int tiles_y = (a.B + NT * 16 - 1) / (NT * 16);
     hipLaunchKernelGGL((gsw_trace_scan_kernel<NT, P>), dim3(a.grid_x, tiles_y), dim3(TR_WG), lds, st, a);
-    GSW_TRACE_HIP(hipGetLastError());
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -397,13 +362,13 @@ int gsw_trace_topk(const uint32_t* counts_dev, int B, int msg_bits, int copies, 
         if (rc != GSW_OK) return rc;
         s.floor_out = floors;
         hipLaunchKernelGGL(gsw_trace_finish_kernel, dim3(B), dim3(64), 0, st, s);
-        GSW_TRACE_HIP(hipGetLastError());
+        GSW_HIP(hipGetLastError());
         a.floor = floors;
     }
     int rc = scan(a);
     if (rc != GSW_OK) return rc;
     hipLaunchKernelGGL(gsw_trace_finish_kernel, dim3(B), dim3(64), 0, st, a);
-    GSW_TRACE_HIP(hipGetLastError());
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 

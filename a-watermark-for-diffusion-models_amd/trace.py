@@ -496,7 +496,8 @@ class KeyedRegistry:
         if t is None:
             t = np.zeros((len(self._ids), self.record_stride), dtype=np.uint8)
             flat = np.frombuffer(b"".join(k + n + m for k, n, m in self._records), dtype=np.uint8)
-            t[:, :48 + self.message_bytes] = flat.reshape(len(self._ids), 48 + self.message_bytes)
+            used = codec.KEYED_RECORD_HEAD + self.message_bytes
+            t[:, :used] = flat.reshape(len(self._ids), used)
             self._device_cache["host"] = t
         return t
 

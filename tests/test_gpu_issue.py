@@ -17,6 +17,7 @@ for p_ in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
         sys.path.insert(0, p_)
 
 import gs_oracle as O  # noqa: E402
+from record_rows import counter_carry_rows, make_records  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -40,15 +41,6 @@ def _bits(t):
 
 def _n(shape):
     return int(np.prod(shape))
-
-
-def make_records(B, mb, seed, stride=None):
-    """(host rows uint8 [B, stride], [(key, nonce, msg)])"""
-    rs = np.random.RandomState(seed)
-    stride = (48 + mb + 15) // 16 * 16 if stride is None else stride
-    rows = np.zeros((B, stride), dtype=np.uint8)
-    rows[:, :48 + mb] = rs.randint(0, 256, (B, 48 + mb), dtype=np.uint8)
-    return rows, [(bytes(r[:32]), bytes(r[32:48]), bytes(r[48:48 + mb])) for r in rows]
 
 
 def make_u(B, n, seed):
@@ -147,12 +139,15 @@ def test_split_invariance(P, l, fast):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------ 4
+CARRY_SHAPE = (4, 16, 32)       # 2048 elements, 4 l ChaCha blocks: the shape whose records count across a carry (record_rows.counter_carry_rows)
+
+
 def _extract_combos(l):
     out = []
     for shape in ((4, 8, 8), (4, 17, 25), (4, 64, 64), (4, 96, 96)):
         nb = _n(shape) * l
         out += [(shape, mb) for mb in (1, 32, 256) if nb % 8 == 0 and nb % (8 * mb) == 0]
-    return out
+    return out + [(CARRY_SHAPE, 2)]
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
@@ -160,10 +155,12 @@ def _extract_combos(l):
 def test_extract_identity(P, l, dtype):
     B = 5
     combos = _extract_combos(l)
-    assert {s for s, _ in combos} >= {(4, 8, 8), (4, 64, 64), (4, 96, 96)} and {m for _, m in combos} == {1, 32, 256}
+    assert {s for s, _ in combos} >= {(4, 8, 8), (4, 64, 64), (4, 96, 96), CARRY_SHAPE} and {m for _, m in combos} == {1, 2, 32, 256}
     for j, (shape, mb) in enumerate(combos):
         n, M = _n(shape), 8 * mb
         rows, recs = make_records(B, mb, 200 + j)
+        if shape == CARRY_SHAPE:
+            recs = counter_carry_rows(rows, mb)
         dev = torch.from_numpy(rows).cuda()
         clean = P.codec.embed_records(dev, mb, shape, seed=j, dtype=dtype, l=l)
         g = torch.Generator(device="cuda").manual_seed(j)

@@ -18,6 +18,7 @@ for p_ in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
 import gs_oracle as O  # noqa: E402
 import soft_reference as R  # noqa: E402
 from poison import FINITE, NAN, Ledger, poisoned  # noqa: E402
+from record_rows import counter_carry_rows, make_records  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -28,8 +29,10 @@ SAT = 8.3125            # >= 8.2924 (the quantiser saturates from 8.292361075813
 OUTPUTS = ("bits", "flags", "matches", "score", "wsum", "wsq")
 
 # (elements per image, msg_bytes, B): 256 elements with an 8-bit message; 4 x 24 x 40 with a 15-byte message (M = 120, 32 copies: neither a power of two
-# nor word-sized, 255 of the 256 threads walk the image); 4 x 64 x 64 with 256 bits; one image at the cap of 1 048 576 elements with M = 2048
-GEOMETRIES = [(256, 1, 3), (256, 1, 70), (3840, 15, 1), (3840, 15, 70), (16384, 32, 3), (16384, 32, 70), (1048576, 256, 1)]
+# nor word-sized, 255 of the 256 threads walk the image); 4 x 64 x 64 with 256 bits; one image at the cap of 1 048 576 elements with M = 2048;
+# 2048 elements (four ChaCha blocks) under records whose block counter carries inside the row (CARRY)
+CARRY = (2048, 2, 3)
+GEOMETRIES = [(256, 1, 3), (256, 1, 70), (3840, 15, 1), (3840, 15, 70), (16384, 32, 3), (16384, 32, 70), (1048576, 256, 1), CARRY]
 GEOMETRY_IDS = [f"n{n}-mb{mb}-B{B}" for n, mb, B in GEOMETRIES]
 
 
@@ -38,15 +41,6 @@ def P():
     import gswm_amd  # noqa: F401
     from gswm_amd import _native, codec, soft, trace
     return types.SimpleNamespace(codec=codec, soft=soft, trace=trace, N=_native, lib=_native.lib())
-
-
-def make_records(B, mb, seed):
-    """(host rows uint8 [B, stride], [(key, nonce, msg)])"""
-    rs = np.random.RandomState(seed)
-    stride = (48 + mb + 15) // 16 * 16
-    rows = np.zeros((B, stride), dtype=np.uint8)
-    rows[:, :48 + mb] = rs.randint(0, 256, (B, 48 + mb), dtype=np.uint8)
-    return rows, [(bytes(r[:32]), bytes(r[32:48]), bytes(r[48:48 + mb])) for r in rows]
 
 
 _CASES = {}
@@ -58,6 +52,8 @@ def case(n, mb, B):
     if c is None:
         rs = np.random.RandomState(n + 131 * mb + B)
         rows, recs = make_records(B, mb, 7 * n + B)
+        if (n, mb, B) == CARRY:                 # the 32-bit counter of image 0 carries at block 1, the 64-bit counter of image 1 wraps at block 2
+            recs = counter_carry_rows(rows, mb)
         z = rs.standard_normal((B, n)) * rs.uniform(0.5, 3.0, (B, 1))
         tables = {}
         for levels in (1, 2, 15):
