@@ -24,6 +24,7 @@
 
 #include "../../include/gswm.h"
 #include "gswm_mm.h"
+#include "gswm_host.h"
 
 typedef _Float16 gsw_h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 gsw_b8 __attribute__((ext_vector_type(8)));
@@ -522,9 +523,6 @@ __global__ __launch_bounds__(256) void gsw_add_layernorm_kernel(const uint16_t* 
 }
 
 // host ---------------------------------------------------------------------------------------------
-extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip; read by gsw_last_hip_error()
-#define g_conv_hip_error g_last_hip_error
-#define GSW_CONV_HIP(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_conv_hip_error = (int)_e; return GSW_ERR_HIP; } } while (0)
 static int launch_engine(const ConvArgs& a, int64_t M, int N, int dtype, void* stream, GswMmExtras* ex);
 static bool use_engine(const ConvArgs& a, int N);
 
@@ -555,14 +553,12 @@ static void zero_border(void* y, int B, int Hp, int Wp, int N, hipStream_t st) {
 }
 
 static int launch_engine(const ConvArgs& a, int64_t M, int N, int dtype, void* stream, GswMmExtras* ex) {
-    MMArgs m;
+    MMArgs m = mm_args_rows(a.x, a.ldx, a.C, a.w, a.ntaps * a.C + a.C1 + a.C2, a.y, 0, N);
     const int tw = a.ntaps == 9 ? 3 : a.ntaps == 4 ? 2 : 1;
     m.seg[0] = MMSeg{a.x, a.ldx, a.C / 64, a.ntaps, tw, a.in_Wp, a.tap_off[0], 0};
     m.seg[1] = MMSeg{a.x1 ? a.x1 : a.x, a.C1 ? a.C1 : a.ldx, a.C1 / 64, 1, 1, 0, 0, a.ntaps * a.C};
     m.seg[2] = MMSeg{a.x2 ? a.x2 : a.x, a.C2 ? a.C2 : a.ldx, a.C2 / 64, 1, 1, 0, 0, a.ntaps * a.C + a.C1};
-    m.nseg = 1 + (a.C1 > 0) + (a.C2 > 0);
-    m.P = a.ntaps * (a.C / 64) + a.C1 / 64 + a.C2 / 64;
-    m.w = a.w; m.ldw = a.ntaps * a.C + a.C1 + a.C2;
+    m.nseg = 1 + (a.C1 > 0) + (a.C2 > 0); m.P = a.ntaps * (a.C / 64) + a.C1 / 64 + a.C2 / 64;
     // the M dimension enumerates interior pixels only (the padded border is 6 % of the rows at 64x64 and 56 % at 8x8); the border rows of
     // the output are zeroed by a separate small kernel (the up2x caller does that once for its four parity launches).
     // Small tensors (one or two images: the launch is latency-bound, not throughput-bound) enumerate ALL padded rows instead and let the epilogue
@@ -576,12 +572,11 @@ static int launch_engine(const ConvArgs& a, int64_t M, int N, int dtype, void* s
     bool whole = !a.up && a.stride == 1 && M <= 8192;
     if (whole && M > 1024 && !(ex && ex->max_splits > 1))
         whole = gsw_mm_predict_us(M, N, m.P, ex) <= gsw_mm_predict_us(M_int, N, m.P, ex) + 5.0;
-    m.M = whole ? (int32_t)M : (int32_t)M_int; m.N = N;
+    m.M = whole ? (int32_t)M : (int32_t)M_int;
     m.flags = whole ? MM_FLAG_NONE : MM_FLAG_COMPACT;
-    m.bias = a.bias; m.rowbias = a.rowbias; m.resid = a.resid; m.y = a.y; m.colstats = nullptr; m.y2 = nullptr; m.n_rows = 0; m.ln_stat = nullptr; m.ln_u = nullptr; m.ln_v = nullptr;
-    m.ldy = N; m.ldr = N; m.ldrb = a.ldrb;
+    m.bias = a.bias; m.rowbias = a.rowbias; m.resid = a.resid; m.ldrb = a.ldrb;
     m.mode = a.up ? MM_MODE_UP2X : MM_MODE_PF;
-    m.Hp = a.Hp; m.Wp = a.Wp; m.in_Hp = a.in_Hp; m.in_Wp = a.in_Wp; m.stride = a.stride; m.S = 1; m.Wimg = 1; m.up = a.up;
+    m.Hp = a.Hp; m.Wp = a.Wp; m.in_Hp = a.in_Hp; m.in_Wp = a.in_Wp; m.stride = a.stride; m.up = a.up;
     const int rc = gsw_mm_launch(m, dtype, stream, ex);
     // the border of the output: zeroed by a small kernel of its own (it touches rows the engine launch does not) -- unless the caller declared the output
     // GroupNorm-only (GSW_MM_GN_ONLY) AND this launch wrote the column records that GroupNorm will take its statistics from: nothing reads the border then
@@ -643,8 +638,7 @@ static int launch_conv_gemm(ConvArgs& a, int64_t M, int N, int dtype, void* stre
     const uint32_t grid = (uint32_t)(((M + CV_BM - 1) / CV_BM) * (N / CV_BN));
     if (dtype == GSW_F16) hipLaunchKernelGGL((gsw_conv_gemm_kernel<_Float16>), dim3(grid), dim3(CV_THREADS), 0, st, a);
     else hipLaunchKernelGGL((gsw_conv_gemm_kernel<__bf16>), dim3(grid), dim3(CV_THREADS), 0, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_conv_hip_error = (int)e; return GSW_ERR_HIP; }
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -721,8 +715,7 @@ int gsw_groupnorm_pf_cs(const void* x_dev, const void* x2_dev, int Ca, const flo
     hipLaunchKernelGGL(gsw_gn_colstats_finish_kernel, dim3(B, (C / 2 + 63) / 64), dim3(512), 0, st, s1, s2, reinterpret_cast<float2*>(workspace_dev), C);
     hipLaunchKernelGGL(gsw_gn_pf_apply_kernel, dim3(nslab, B), dim3(threads), 0, st, (const uint16_t*)x_dev, (const uint16_t*)x2_dev, Ca, (const float*)workspace_dev, (const uint16_t*)gamma_dev,
                        (const uint16_t*)beta_dev, (uint16_t*)out_dev, C, groups, H + 2, W + 2, 0, slab_len, P, eps, act, out_tokens, bf);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_conv_hip_error = (int)e; return GSW_ERR_HIP; }
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -735,8 +728,7 @@ int gsw_gn_colstats_pairs(const float* cs_dev, int cs_rows, int cs_npar, int cs_
     if (pix <= 0 || pix % cs_rows || (int64_t)B * (pix / cs_rows) > cs_blocks) return GSW_ERR_UNSUPPORTED;
     const GnColSrc s1 = GnColSrc{cs_dev, C, cs_npar, (int32_t)(pix / cs_rows), cs_blocks}, s2 = GnColSrc{nullptr, 0, 0, 0, 0};
     hipLaunchKernelGGL(gsw_gn_colstats_finish_kernel, dim3(B, (C / 2 + 63) / 64), dim3(512), 0, (hipStream_t)stream, s1, s2, reinterpret_cast<float2*>(pairsum_dev), C);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_conv_hip_error = (int)e; return GSW_ERR_HIP; }
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -763,8 +755,7 @@ int gsw_groupnorm_pf2(const void* x_dev, const void* x2_dev, int Ca, const void*
     hipLaunchKernelGGL(gsw_gn_pf_stats_kernel, dim3(nslab, B), dim3(threads), 0, st, (const uint16_t*)x_dev, (const uint16_t*)x2_dev, Ca, workspace_dev, C, groups, HpWp, slab_len, P, bf);
     hipLaunchKernelGGL(gsw_gn_pf_apply_kernel, dim3(nslab_a, B), dim3(threads), 0, st, (const uint16_t*)x_dev, (const uint16_t*)x2_dev, Ca, (const float*)workspace_dev, (const uint16_t*)gamma_dev,
                        (const uint16_t*)beta_dev, (uint16_t*)out_dev, C, groups, H + 2, W + 2, nslab, slab_len_a, P, eps, act, out_tokens, bf);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_conv_hip_error = (int)e; return GSW_ERR_HIP; }
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -788,8 +779,7 @@ int gsw_add_layernorm(const void* x_dev, const void* delta_dev, const void* gamm
                        (const uint16_t*)gamma_dev, (const uint16_t*)beta_dev, (uint16_t*)xnew_dev, (uint16_t*)y_dev, rows, C, eps, dtype == GSW_BF16)
     if (L == 8) GSW_LN_LAUNCH(8); else if (L == 16) GSW_LN_LAUNCH(16); else if (L == 32) GSW_LN_LAUNCH(32); else GSW_LN_LAUNCH(64);
 #undef GSW_LN_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_conv_hip_error = (int)e; return GSW_ERR_HIP; }
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 

@@ -1,6 +1,6 @@
-// gswm_host.h -- the host prelude of the codec family (gswm_kernels.hip with its .inc files, gswm_trace.hip, gswm_keyed.hip,
-// gswm_tamper.hip): the HIP error path, the CU count and the dynamic-LDS opt-in.  Host code only; include after <hip/hip_runtime.h>
-// and include/gswm.h.
+// gswm_host.h -- the host prelude of the codec family (gswm_kernels.hip with its .inc files, gswm_trace.hip, gswm_keyed.hip, gswm_tamper.hip), the matmul
+// engine (gswm_mm.hip) and the convolution front end (gswm_conv.hip): the HIP error path, the CU count and the dynamic-LDS opt-in.  Host code only; include after
+// <hip/hip_runtime.h> and include/gswm.h.
 #pragma once
 
 extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip; read by gsw_last_hip_error()

@@ -53,6 +53,20 @@ struct MMArgs {
     float* ws;            // filled by gsw_mm_launch: split-K workspace, [splits][ntiles][8 waves][5 * MT accumulators][64 lanes] float4
 };
 
+// An MMArgs with every field at its dense-row default: Y [M][N] (rows N apart, like the residual's and the row bias's) = X W^T with ONE K segment of K columns of
+// x (row stride ld; the unused segment slots repeat it), all geometry fields 1, every optional pointer null, the fields gsw_mm_launch fills zero.  A caller sets the
+// fields in which it differs.
+inline MMArgs mm_args_rows(const void* x, int32_t ld, int32_t K, const void* w, int32_t ldw, void* y, int32_t M, int32_t N) {
+    MMArgs a{};
+    for (MMSeg& s : a.seg) s = MMSeg{x, ld, K / 64, 1, 1, 0, 0, 0};
+    a.nseg = 1; a.P = K / 64;
+    a.w = w; a.ldw = ldw; a.y = y; a.M = M; a.N = N;
+    a.ldy = a.ldr = a.ldrb = N;
+    a.mode = MM_MODE_DENSE;
+    a.Hp = a.Wp = a.in_Hp = a.in_Wp = a.stride = a.S = a.Wimg = 1;
+    return a;
+}
+
 // ex: the launch's extras (records requested, split-K scratch; results written back).  nullptr = none (gsw_mm_no_extras).
 struct GswMmExtras;
 int gsw_mm_launch(MMArgs& a, int dtype, void* stream, GswMmExtras* ex);

@@ -38,6 +38,8 @@
 
 #include "../../include/gswm.h"
 #include "gswm_mm.h"
+#include "gswm_mm_plan.h"
+#include "gswm_host.h"
 #include "gswm_mmtypes.h"
 #include "gswm_ablate.inc"
 
@@ -1571,51 +1573,45 @@ int mm_launch_k(const MMArgs& a, uint32_t grid, hipStream_t st) {
     hipLaunchKernelGGL((gsw_mm_kernel<T, EPI, SPLIT, MT, LNF>), dim3(grid), dim3(SPLIT ? 768 : 512), ldsb, st, a);
     return (int)hipGetLastError();
 }
+// The kernel instantiation of a decided launch: reads the plan (gswm_mm_plan.h) only.  Not every (epilogue, form, MT) exists: the plan never asks for the others.
 template <typename T, int EPI>
-int mm_launch_t(const MMArgs& a, uint32_t grid, int mt, hipStream_t st) {
+int mm_select_t(const MMLaunch& d, const MMArgs& a, hipStream_t st) {
+    const uint32_t grid = d.grid; const int mt = d.mt;
     if constexpr (EPI == 5) return mt == 4 ? mm_launch_k<T, 5, false, 4>(a, grid, st) : mm_launch_k<T, 5, false, 2>(a, grid, st);      // dense epilogues: 8-wave form
     else {
-    if (a.ln_stat) {                      // LayerNorm folded into the epilogue: dense rows / GEGLU / transposed, 8-wave form
+    if (d.lnf) {                          // LayerNorm folded into the epilogue: dense rows / GEGLU / transposed, 8-wave form
         if constexpr (EPI == 0 || EPI == 2) { if (mt == 8) return mm_launch_k<T, EPI, false, 8, true>(a, grid, st); }
         if constexpr (EPI == 0 || EPI == 2 || EPI == 3)
             return mt == 4 ? mm_launch_k<T, EPI, false, 4, true>(a, grid, st) : mm_launch_k<T, EPI, false, 2, true>(a, grid, st);
         else return (int)hipErrorInvalidValue;
     }
     if constexpr (EPI == 0 || EPI == 1 || EPI == 2) { if (mt == 8) return mm_launch_k<T, EPI, false, 8>(a, grid, st); }
-    // bit e of the split mask set = epilogue kind e runs the 12-wave variant whose waves 8-11 own the LDS-DMA (gsw_mm_config / GSW_MM_SPLIT: A/B switch)
-    const bool split = (g_mm_split_mask.load(std::memory_order_relaxed) >> EPI) & 1;
-    // (dense rows, 256-row tile: the 12-wave form does not fit its 168 registers -- 32-40 bytes of scratch per lane -- so that combination is not
-    // instantiated and always runs the 8-wave form; the mask bit still selects the 12-wave 128-row variant)
+    // (dense rows, 256-row tile: the 12-wave form is not instantiated -- mm_decide never asks for it)
     if constexpr (EPI == 0) { if (mt == 4) return mm_launch_k<T, EPI, false, 4>(a, grid, st); }
-    else { if (mt == 4) return split ? mm_launch_k<T, EPI, true, 4>(a, grid, st) : mm_launch_k<T, EPI, false, 4>(a, grid, st); }
-    return split ? mm_launch_k<T, EPI, true, 2>(a, grid, st) : mm_launch_k<T, EPI, false, 2>(a, grid, st);
+    else { if (mt == 4) return d.wave12 ? mm_launch_k<T, EPI, true, 4>(a, grid, st) : mm_launch_k<T, EPI, false, 4>(a, grid, st); }
+    return d.wave12 ? mm_launch_k<T, EPI, true, 2>(a, grid, st) : mm_launch_k<T, EPI, false, 2>(a, grid, st);
     }
 }
 template <typename T>
-int mm_launch_splitk(const MMArgs& a, uint32_t grid, int mt, hipStream_t st) {
-    // 128- or 256-row tiles (mm_plan decides); both variants fit the 168 registers of the 12-wave form (152 / 100) without scratch
-    if (mt != 2 && mt != 4) return (int)hipErrorInvalidValue;
-    const int e = mt == 4 ? mm_launch_k<T, 4, true, 4>(a, grid, st) : mm_launch_k<T, 4, true, 2>(a, grid, st);
-    if (e != 0) return e;
-    const int64_t units = (int64_t)a.ntiles * 8 * 5 * mt * 64;
-    hipLaunchKernelGGL((gsw_mm_reduce_kernel<T>), dim3((uint32_t)std::min<int64_t>((units + 255) / 256, 2048)), dim3(256), 0, st, a, mt);
-    return (int)hipGetLastError();
-}
-template <typename T>
-int mm_launch_e(const MMArgs& a, int epi, uint32_t grid, int mt, hipStream_t st) {
-    switch (epi) {
-        case 0: return mm_launch_t<T, 0>(a, grid, mt, st);
-        case 1: return mm_launch_t<T, 1>(a, grid, mt, st);
-        case 2: return mm_launch_t<T, 2>(a, grid, mt, st);
-        case 5: return mm_launch_t<T, 5>(a, grid, mt, st);
-        default: return mm_launch_t<T, 3>(a, grid, mt, st);
+int mm_select(const MMLaunch& d, const MMArgs& a, hipStream_t st) {
+    if (d.epi == 4) {        // split-K: the 12-wave form (MT 2 / 4), then the reduce kernel that adds the partials and runs the epilogue
+        if (d.mt != 2 && d.mt != 4) return (int)hipErrorInvalidValue;
+        const int e = d.mt == 4 ? mm_launch_k<T, 4, true, 4>(a, d.grid, st) : mm_launch_k<T, 4, true, 2>(a, d.grid, st);
+        if (e != 0) return e;
+        const int64_t units = (int64_t)a.ntiles * 8 * 5 * d.mt * 64;
+        hipLaunchKernelGGL((gsw_mm_reduce_kernel<T>), dim3((uint32_t)std::min<int64_t>((units + 255) / 256, 2048)), dim3(256), 0, st, a, d.mt);
+        return (int)hipGetLastError();
+    }
+    switch (d.epi) {
+        case 0: return mm_select_t<T, 0>(d, a, st);
+        case 1: return mm_select_t<T, 1>(d, a, st);
+        case 2: return mm_select_t<T, 2>(d, a, st);
+        case 5: return mm_select_t<T, 5>(d, a, st);
+        default: return mm_select_t<T, 3>(d, a, st);
     }
 }
 
 }  // namespace
-
-extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip
-
 
 // An engine launch without extras (a nullptr `ex` of an entry point): no records requested, no split-K scratch.  ABI < 0.5.0 kept thread-local one-shot
 // requests and a thread-local workspace behind this case; since 0.5.0 everything a launch needs travels in the caller's GswMmExtras.
@@ -1642,17 +1638,6 @@ int gsw_mm_get_config(int* tile_rows, int* split_mask) {
     return GSW_OK;
 }
 
-// Tiling and split-K plan of a launch, with the time the cost model predicts for it (microseconds).  The model is fitted to tools/splitk_tile_sweep.py
-// (profiles/r04i_splitk_tile_sweep.txt: 35 shapes x tile rows x split counts, HBM-cold weights, graph-captured; rms error 6 %, mean regret of its choices 1 %):
-//   a stage of a 128-row tile costs 0.56 us while at most half the CUs work and 0.67 with all of them; a stage of a 256-row tile 0.79-0.81 and 1.13 (the chip is
-//   power- and L2-bound when every CU multiplies: section 4.8 of DESIGN.md); an unsplit launch pays 2.5 us on top, a split one 12.5 (its reduce kernel) and 0.014 per
-//   80 KiB of slab.
-// Unsplit tile: for long K (>= 40 stages) and at most one round of 256-row tiles the model decides -- 128-row tiles when 256-row ones would leave half the chip idle
-// (4096 x 1280 outputs: 127 vs 162 us at K = 11520; 52 vs 69 at K = 5120; the round-3 rule kept 256 rows there from a sweep whose weights were L2-hot).  Short K keeps
-// the measured rule of round 3 (128-row tiles whenever 256-row ones do not fill the chip: a short-K weight matrix stays in L2 and all CUs win), more than one round
-// keeps 256-row tiles (a half tile re-fetches the weight tile twice as often).
-// Split: at most 128 tiles, at least 8 stages, up to 32 ways (one image at 8 x 8: 8 tiles x 32 = the whole chip, 19.9 vs 21.1 us at 16 ways) and 256 workgroups, 128- or 256-row tiles, taken for a predicted gain of 5 % or more.  Forced splits
-// (max_splits > 1: tests) use 128 rows unless gsw_mm_config forces the 256-row tile.
 // Compute units the persistent grid, the plan's "rounds" and its half-chip threshold are counted in: 256, the MI355X the stage costs, the wide-tile thresholds and the 8-XCD
 // tile interleave were fitted and tested on.  A partition with fewer CUs still runs correctly with 256 workgroups (they queue); GSW_MM_CUS=<n> (a multiple of 8) or
 // GSW_MM_CUS=device opts into another count for experiments -- read once per process.
@@ -1670,197 +1655,39 @@ static int mm_cus() {
     }();
     return cus;
 }
-struct MMPlan { int bm; int splits; double t_us; };
-// (the stage costs were fitted on ONE box of the pool in round 4 -- profiles/r04i_splitk_tile_sweep.txt: MI355X, 256 CUs, 1400 W board limit, HBM-cold weights,
-// the deep levels at 4-64 images, board at 1.1-1.3 kW; boxes of the pool differ by +-4 %.  W = busy workgroups; the costs are functions of the busy FRACTION
-// of the chip, so a different CU count rescales W, not the constants.)
-static inline double mm_stage_us(int bm, double W, int64_t CU) {
-    const double half = 0.5 * (double)CU;
-    const double over = W > half ? (W - half) / half : 0.0;
-    return bm == 128 ? 0.56 + 0.11 * over : 0.79 + 0.02 * std::min(1.0, W / half) + 0.32 * over;
-}
-static MMPlan mm_plan(int64_t M, int64_t tiles_n, int32_t P, bool can_split, int max_splits) {
-    const int bm_env = g_mm_tile_rows.load(std::memory_order_relaxed);          // GSW_MM_BM / gsw_mm_config: 128 / 256 forces a tiling (A/B runs, tests)
-    const int64_t CU = mm_cus();
-    const int64_t nt256 = ((M + 255) / 256) * tiles_n, nt128 = ((M + 127) / 128) * tiles_n;
-    auto t_unsplit = [&](int bm) {
-        const int64_t nt = bm == 256 ? nt256 : nt128, rounds = (nt + CU - 1) / CU;
-        return 2.5 + mm_stage_us(bm, rounds == 1 ? (double)nt : (double)CU, CU) * (double)P * (double)rounds;
-    };
-    int BM;
-    if (bm_env == 128 || bm_env == 256) BM = bm_env;
-    else if (M <= 128) BM = 256;
-    else if (P >= 40 && nt256 <= CU) BM = t_unsplit(128) < t_unsplit(256) ? 128 : 256;
-    else BM = nt256 < (P >= 64 ? CU / 2 : CU) ? 128 : 256;
-    MMPlan pl{BM, 1, t_unsplit(BM)};
-    if (!can_split) return pl;
-    if (max_splits > 1) {
-        const int bm_s = bm_env == 256 && M > 128 ? 256 : 128;
-        const int64_t nt_f = ((M + bm_s - 1) / bm_s) * tiles_n;
-        const int sp = (int)std::min<int64_t>(std::min<int64_t>(max_splits, P), CU / std::max<int64_t>(nt_f, 1));
-        if (sp >= 2) { pl.bm = bm_s; pl.splits = sp; }
-        return pl;
-    }
-    if (P < 8) return pl;
-    double best = pl.t_us / 1.05;
-    for (int bm_c = 128; bm_c <= 256; bm_c += 128) {
-        if (bm_c == 256 && (M <= 128 || bm_env == 128)) continue;
-        if (bm_c == 128 && bm_env == 256) continue;
-        const int64_t nt_c = bm_c == 256 ? nt256 : nt128;
-        if (nt_c > CU / 2) continue;
-        for (int s_ = 2; s_ <= 32 && s_ * nt_c <= CU && 2 * s_ <= P; ++s_) {
-            const double t = 12.5 + mm_stage_us(bm_c, (double)(s_ * nt_c), CU) * (double)((P + s_ - 1) / s_) + 0.014 * (double)(s_ * nt_c * (bm_c / 128));
-            if (t < best) { best = t; pl.bm = bm_c; pl.splits = s_; pl.t_us = t; }
-        }
-    }
-    return pl;
+// The knobs of the policy (gswm_mm_plan.h): the A/B values of the environment are read once per process, the two atomics per call.
+static MMKnobs mm_knobs() {
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    static const MMKnobs env{0, 0, mm_cus(), num("GSW_MM_PANEL", 0), num("GSW_MM_WIDE", 7), num("GSW_MM_WIDE_PMIN", 5), num("GSW_MM_WIDE_PMIN_PF", 64), num("GSW_MM_WIDE_PMIN_RES", 8)};
+    MMKnobs k = env;
+    k.tile_rows = g_mm_tile_rows.load(std::memory_order_relaxed);
+    k.split_mask = g_mm_split_mask.load(std::memory_order_relaxed);
+    return k;
 }
 
-// What the plan of a launch of M x N outputs over P stages predicts (microseconds): the convolution front end chooses between its two row enumerations with it.
 // ex: the launch's extras, or nullptr (no split-K scratch).
 double gsw_mm_predict_us(int64_t M, int N, int P, const GswMmExtras* ex) {
-    const bool have_ws = ex && ex->workspace_bytes > 0 && ex->workspace_dev;
-    const int max_splits = ex ? ex->max_splits : 0;
-    const MMPlan pl = mm_plan(M, ((int64_t)N + 159) / 160, P, have_ws && max_splits != 1, max_splits);
-    const int64_t need = (int64_t)pl.splits * (((M + pl.bm - 1) / pl.bm) * (((int64_t)N + 159) / 160)) * 8 * 5 * (pl.bm / 64) * 64 * 16;
-    if (pl.splits >= 2 && need > (ex ? ex->workspace_bytes : 0)) return mm_plan(M, ((int64_t)N + 159) / 160, P, false, 1).t_us;
-    return pl.t_us;
+    GswMmExtras none;
+    if (!ex) { gsw_mm_no_extras(&none); ex = &none; }
+    return mm_predict_us(M, N, P, *ex, mm_knobs());
 }
 
-// Launch the engine for a prepared MMArgs (segments, weights, epilogue); fills the tiling fields.
+// Launch the engine for a prepared MMArgs (segments, weights, epilogue): decide (mm_decide: the whole policy), copy the decision into the fields of `a` and `ex`
+// that are filled here, pick the kernel.
 int gsw_mm_launch(MMArgs& a, int dtype, void* stream, GswMmExtras* ex) {
     GswMmExtras none;
     if (!ex) { gsw_mm_no_extras(&none); ex = &none; }
     else { ex->colstats_rows_per_block = 0; ex->colstats_blocks = 0; ex->rowstats_slots = 0; ex->splits = 1; }
-    if (dtype != GSW_F16 && dtype != GSW_BF16) return GSW_ERR_BAD_ARG;
-    if (ex->colstats_capacity < 0 || ex->rowstats_capacity < 0 || ex->workspace_bytes < 0 || ex->max_splits < 0 || ex->max_splits > 64
-        || ((uintptr_t)ex->colstats_dev & 15) || ((uintptr_t)ex->rowstats_dev & 7) || ((uintptr_t)ex->workspace_dev & 15)
-        || (ex->flags & ~GSW_MM_GN_ONLY)) return GSW_ERR_BAD_ARG;      // (unknown flag bits: a caller that filled the struct field by field without zeroing it)
-    void* const ws_dev = ex->workspace_bytes > 0 ? ex->workspace_dev : nullptr;
-    const int64_t ws_bytes = ws_dev ? ex->workspace_bytes : 0;
-    const int max_splits = ex->max_splits;
-    // N: any multiple of 8 (the last 160-column tile may be partial: weight rows are clamped, stores masked); GEGLU pairs columns inside a tile
-    if (a.N % 8 || (a.mode == MM_MODE_GEGLU && a.N % 160) || a.M <= 0 || a.P <= 0) return GSW_ERR_UNSUPPORTED;
-    if (a.mode == MM_MODE_QKV && (a.n_rows <= 0 || a.n_rows % 160 || a.n_rows >= a.N || !a.y2)) return GSW_ERR_UNSUPPORTED;
-    constexpr int BN = 160;
-    const int64_t tiles_n = (a.N + BN - 1) / BN;
-    // panel of the tile order: 8 column tiles, or all of them when their weight tiles (tiles_n x 160 rows x K) stay under ~2 MiB of an XCD's 4 MiB L2
-    {
-        static const int panel_env = getenv("GSW_MM_PANEL") ? atoi(getenv("GSW_MM_PANEL")) : 0;       // A/B switch: 8 = the fixed panel of ABI < 0.4.0
-        a.panel = 8;
-        if (tiles_n > 8 && tiles_n <= 32 && tiles_n * BN * (int64_t)a.P * 64 * 2 <= (2 << 20)) a.panel = (int32_t)tiles_n;
-        if (panel_env > 0) a.panel = panel_env;
-    }
-    const MMPlan plan = mm_plan(a.M, tiles_n, a.P, ws_dev && max_splits != 1 && !a.ln_stat, max_splits);       // tiling and split-K policy: see mm_plan
-    const int BM = plan.splits >= 2 ? mm_plan(a.M, tiles_n, a.P, false, 1).bm : plan.bm;      // the tile of the UNSPLIT launch (also taken when a split plan does not fit the workspace)
-    hipStream_t st = (hipStream_t)stream;
-    a.splits = 1; a.ws = nullptr;
-    // the dense-row / GEGLU epilogues fetch the bias by 16-byte LDS-DMA pieces (STG in the kernel)
-    if ((a.mode == MM_MODE_DENSE || a.mode == MM_MODE_GEGLU) && ((uintptr_t)a.bias & 15u)) return GSW_ERR_BAD_ARG;
-    float* const cs_req = ex->colstats_capacity > 0 ? ex->colstats_dev : nullptr;
-    const int64_t cs_cap = cs_req ? ex->colstats_capacity : 0;
-    float* const rs_req = ex->rowstats_capacity > 0 ? ex->rowstats_dev : nullptr;
-    const int64_t rs_cap = rs_req ? ex->rowstats_capacity : 0;
-    a.colstats = nullptr;
-    a.rowstats = nullptr;
-    if (a.ln_stat && (a.mode != MM_MODE_DENSE && a.mode != MM_MODE_GEGLU && a.mode != MM_MODE_TRANS)) return GSW_ERR_UNSUPPORTED;
-    if (a.ln_stat && a.rowbias) return GSW_ERR_UNSUPPORTED;
-    // Split-K for launches that cannot fill the chip with output tiles (the deep levels at small batch: 8 x 8 pixels of one image are ONE row tile
-    // against 180-360 K stages): `splits` workgroups share a tile's stages, fp32 partials go through the caller's workspace, a second small kernel
-    // adds them in a fixed order and runs the epilogue.  Needs a workspace (gsw_mm_set_workspace); without one the launch runs unsplit.
-    if (plan.splits >= 2) {
-        const int bm_s = plan.bm, splits = plan.splits;
-        const int64_t nt = (((int64_t)a.M + bm_s - 1) / bm_s) * tiles_n;
-        const int64_t need = (int64_t)splits * nt * 8 * 5 * (bm_s / 64) * 64 * 16;
-        if (need <= ws_bytes) {
-            a.tiles_n = (int32_t)tiles_n;
-            a.ntiles = (int32_t)nt;
-            a.splits = splits; a.ws = (float*)ws_dev;
-            ex->splits = splits;
-            const uint32_t grid = (uint32_t)((nt * splits + 7) / 8 * 8);
-            const int e = dtype == GSW_F16 ? mm_launch_splitk<_Float16>(a, grid, bm_s / 64, st) : mm_launch_splitk<__bf16>(a, grid, bm_s / 64, st);
-            if (e != 0) { g_last_hip_error = e; return GSW_ERR_HIP; }
-            return GSW_OK;
-        }
-    }
-    // The wide tile (256 x 320, MT = 8): launches with enough of those tiles to keep every CU busy for several rounds and a K loop long enough to amortise
-    // the longer fill (two 72 KiB stages).  Fewer operand bytes per MFMA is what pays under the board's power limit.
-    // GSW_MM_WIDE=0 / gsw_mm_config(tile_rows = 256 or 128) keep the narrower tiles (A/B, tests); tile_rows = 512 forces the wide tile wherever it is legal.
-    bool wide = false;
-    {
-        static const int wide_mask = getenv("GSW_MM_WIDE") ? atoi(getenv("GSW_MM_WIDE")) : 7;       // bit e: epilogue kind e (0 dense rows, 1 PF rows, 2 GEGLU) may take the wide tile; 0 = never (A/B)
-        const int epi_k = a.mode == MM_MODE_GEGLU ? 2 : (a.mode == MM_MODE_DENSE && !a.rowbias) ? 0 : 1;
-        const int wide_env = (wide_mask >> epi_k) & 1;
-        const int bm_cfg = g_mm_tile_rows.load(std::memory_order_relaxed);
-        const bool mode_ok = a.mode == MM_MODE_DENSE || a.mode == MM_MODE_PF || a.mode == MM_MODE_TOK2PF || a.mode == MM_MODE_UP2X || a.mode == MM_MODE_GEGLU;
-        const int64_t tn_w = (a.N + 319) / 320, tm_w = ((int64_t)a.M + 255) / 256;
-        // buffer addressing of the wide producer: no weight-row clamp (N % 320 == 0), every activation segment below 4 GiB
-        int64_t rows_in = a.M;
-        if (a.mode == MM_MODE_PF || a.mode == MM_MODE_UP2X) {
-            const int64_t per_img = (a.flags & MM_FLAG_COMPACT) ? (int64_t)std::max(1, (a.Hp - 2) * (a.Wp - 2)) : (int64_t)a.Hp * a.Wp;
-            rows_in = ((int64_t)a.M / per_img + 1) * (int64_t)a.in_Hp * a.in_Wp + 2 * (int64_t)a.in_Wp + 4;
-        }
-        int64_t ld_max = 0;
-        for (int i = 0; i < a.nseg; ++i) ld_max = std::max<int64_t>(ld_max, a.seg[i].ld);
-        // rows of the output / residual row space (the residual touches address it through a buffer descriptor too)
-        int64_t rows_out = a.M;
-        if (a.mode == MM_MODE_PF || a.mode == MM_MODE_TOK2PF) rows_out = ((int64_t)a.M / std::max<int64_t>(1, (a.mode == MM_MODE_TOK2PF ? a.S : ((a.flags & MM_FLAG_COMPACT) ? (int64_t)(a.Hp - 2) * (a.Wp - 2) : (int64_t)a.Hp * a.Wp))) + 1) * (int64_t)a.Hp * a.Wp;
-        if (a.mode == MM_MODE_UP2X) rows_out = rows_in * 4 + 8;
-        const bool res_ok = !a.resid || rows_out * (int64_t)a.ldr * 2 < ((int64_t)1 << 32) - (1 << 20);
-        // (the dense-row epilogue of the wide tile addresses its OUTPUT by a 32-bit byte offset too)
-        const bool y_ok = !(a.mode == MM_MODE_DENSE && !a.rowbias) || (int64_t)a.M * a.ldy * 2 < ((int64_t)1 << 32) - (1 << 20);
-        const bool legal = mode_ok && res_ok && y_ok && a.N >= 320 && a.N % 320 == 0 && (!(a.mode == MM_MODE_GEGLU || (a.mode == MM_MODE_DENSE && !a.rowbias)) || a.M % 256 == 0) && rows_in * ld_max * 2 < ((int64_t)1 << 32) - (1 << 20) && (int64_t)a.N * a.ldw * 2 < ((int64_t)1 << 32) - (1 << 20);
-        // a partial last column tile costs a whole one: at most 1/8 of the column tiles' work wasted
-        // measured per shape at 128 rows (profiles/r05g_unet_forward_b128_wide_thresholds.txt): the dense-row and GEGLU launches win at every K of the eps model,
-        // K = 320 included (-5 ... -24 %: a 320-column tile reads the activations once where two 160-column tiles read them twice) -- except the K = 320 launches
-        // WITH a residual operand (+6 %: five stages do not pay for the longer epilogue), which stay narrow; the PF-row epilogue (convolutions, token scatter:
-        // per-row residual / row-bias fetches, twice as long per wave on the wide tile) needs a longer K loop -- 3 x 3 convolutions win from K = 5760 on
-        // (-3 ... -7 %) and lose 2-6 % at K = 2880
-        static const int pmin_dense = getenv("GSW_MM_WIDE_PMIN") ? atoi(getenv("GSW_MM_WIDE_PMIN")) : 5;          // (A/B knobs: stages from which the dense-row / GEGLU
-        static const int pmin_pf = getenv("GSW_MM_WIDE_PMIN_PF") ? atoi(getenv("GSW_MM_WIDE_PMIN_PF")) : 64;      //  and the PF-row launches take the wide tile)
-        static const int pmin_res = getenv("GSW_MM_WIDE_PMIN_RES") ? atoi(getenv("GSW_MM_WIDE_PMIN_RES")) : 8;     //  (dense rows with a residual operand)
-        const int p_min = epi_k == 1 ? pmin_pf : (a.resid ? std::max(pmin_dense, pmin_res) : pmin_dense);
-        // rounds of 256 workgroups: a stage of a wide tile costs 1.77 x a stage of a 256 x 160 tile for 2 x its outputs (1.70 vs 0.96 us, the slopes of time against K on
-        // the 64 x 64 convolutions) -- wide wins when its rounds, at that price, are fewer than the narrow tiling's (a half-empty last round can eat the gain:
-        // 4.5 rounds of wide tiles against 9 of narrow ones still win, 2.25 against 4.5 do not)
-        const int64_t cus = mm_cus();
-        const int64_t t_w = tm_w * tn_w, t_n = (((int64_t)a.M + 255) / 256) * tiles_n;
-        const double cost_w = 1.77 * (double)((t_w + cus - 1) / cus), cost_n = (double)((t_n + cus - 1) / cus);
-        const bool fits = t_w >= cus && cost_w <= 0.995 * cost_n && a.P >= p_min && a.M >= 2048;
-        // the wide dense-row / GEGLU producer (AFF in the kernel) steps from one 64-row piece to the next by seg[0]'s row stride, pinned in a scalar register for
-        // the whole launch: an A operand in several K segments stays on the narrow tiles there, and a caller that FORCES the wide tile is told so
-        // (a launch the plan split along K has returned above: the split kernels are narrow and segment-aware)
-        const bool aff_multi = epi_k != 1 && a.nseg > 1;
-        if (aff_multi && legal && bm_cfg == 512) return GSW_ERR_UNSUPPORTED;
-        wide = legal && !aff_multi && (bm_cfg == 512 || (bm_cfg == 0 && wide_env != 0 && fits));
-    }
-    const int BMt = wide ? 256 : BM, BNt = wide ? 320 : BN;
-    const int64_t tiles_nt = (a.N + BNt - 1) / BNt;
-    const int64_t tiles_m = ((int64_t)a.M + BMt - 1) / BMt;
-    if (tiles_m * tiles_nt > 0x7FFFFFFF) return GSW_ERR_UNSUPPORTED;
-    a.tiles_n = (int32_t)tiles_nt;
-    a.ntiles = (int32_t)(tiles_m * tiles_nt);
-    if (wide) {          // panel of the tile order for 320-column tiles: 4 (the same 1280 columns), or all of them under the same L2 budget
-        a.panel = 4;
-        if (tiles_nt > 4 && tiles_nt <= 16 && tiles_nt * 320 * (int64_t)a.P * 64 * 2 <= (2 << 20)) a.panel = (int32_t)tiles_nt;
-    }
-    const uint32_t grid = (uint32_t)std::min<int64_t>(mm_cus(), (a.ntiles + 7) / 8 * 8);
-    const int ngrp = wide ? 4 : 2, wmv = wide ? 2 : 4;        // 80-column groups per tile, waves along M
-    // row statistics: plain dense-row launches (EPI 0), unsplit
-    if (rs_req && a.mode == MM_MODE_DENSE && !a.rowbias && !a.ln_stat && (int64_t)a.M * ngrp * tiles_nt * 2 <= rs_cap) {
-        a.rowstats = rs_req;
-        ex->rowstats_slots = (int)(ngrp * tiles_nt);
-    }
-    // column statistics: EPI 1 launches whose M dimension enumerates real pixels / tokens (interior enumeration or the token scatter), unsplit
-    if (cs_req && (a.mode == MM_MODE_TOK2PF || ((a.mode == MM_MODE_PF || a.mode == MM_MODE_UP2X) && (a.flags & MM_FLAG_COMPACT)))
-        && tiles_m * wmv * (int64_t)a.N <= cs_cap) {
-        a.colstats = cs_req;
-        ex->colstats_rows_per_block = BMt / wmv; ex->colstats_blocks = (int)(tiles_m * wmv);
-    }
-    const int epi = a.mode == MM_MODE_QKV ? 5 : a.mode == MM_MODE_TRANS ? 3 : a.mode == MM_MODE_GEGLU ? 2 : (a.mode == MM_MODE_DENSE && !a.rowbias) ? 0 : 1;
-    const int e = dtype == GSW_F16 ? mm_launch_e<_Float16>(a, epi, grid, wide ? 8 : BM / 64, st) : mm_launch_e<__bf16>(a, epi, grid, wide ? 8 : BM / 64, st);
-    if (e != 0) { g_last_hip_error = e; return GSW_ERR_HIP; }
-    return GSW_OK;
+    const MMLaunch d = mm_decide(a, dtype, *ex, mm_knobs());
+    if (d.status != GSW_OK) return d.status;
+    a.tiles_n = d.tiles_n; a.ntiles = d.ntiles; a.panel = d.panel;
+    a.splits = d.splits; a.ws = d.splits > 1 ? (float*)ex->workspace_dev : nullptr;
+    a.rowstats = d.rowstats_slots ? ex->rowstats_dev : nullptr;
+    a.colstats = d.colstats_blocks ? ex->colstats_dev : nullptr;
+    ex->splits = d.splits; ex->rowstats_slots = d.rowstats_slots;
+    ex->colstats_rows_per_block = d.colstats_rows_per_block; ex->colstats_blocks = d.colstats_blocks;
+    const int e = dtype == GSW_F16 ? mm_select<_Float16>(d, a, (hipStream_t)stream) : mm_select<__bf16>(d, a, (hipStream_t)stream);
+    return e != 0 ? hip_fail((hipError_t)e) : GSW_OK;
 }
 
 int gsw_gemm_strided(const void* x_dev, int64_t ldx, const void* w_dev, int64_t ldw, const void* bias_dev, const void* resid_dev, int64_t ldr,
@@ -1886,18 +1713,11 @@ static int mm_gemm_dense(const void* x0_dev, int64_t ld0, int K0, const void* x1
     if (mode == GSW_GEMM_TOK2PF && (S <= 0 || Wimg <= 0 || S % Wimg || M % S)) return GSW_ERR_BAD_ARG;
     const int64_t ncols = mode == GSW_GEMM_GEGLU ? N / 2 : N;
     if (mode != GSW_GEMM_TRANS && (ldy < ncols || (resid_dev && ldr < ncols))) return GSW_ERR_BAD_ARG;
-    MMArgs a;
-    for (int i = 0; i < 3; ++i) a.seg[i] = MMSeg{x0_dev, (int32_t)ld0, K0 / 64, 1, 1, 0, 0, 0};
-    a.nseg = 1;
-    if (two) { a.seg[1] = MMSeg{x1_dev, (int32_t)ld1, K1 / 64, 1, 1, 0, 0, K0}; a.nseg = 2; }
-    a.P = (int32_t)(K / 64);
-    a.w = w_dev; a.ldw = (int32_t)ldw;
-    a.M = (int32_t)M; a.N = N;
-    a.bias = bias_dev; a.rowbias = nullptr; a.resid = resid_dev; a.y = y_dev; a.colstats = nullptr; a.y2 = nullptr; a.n_rows = 0;
-    a.ln_stat = nullptr; a.ln_u = nullptr; a.ln_v = nullptr;
-    a.ldy = (int32_t)ldy; a.ldr = (int32_t)ldr; a.ldrb = N;
-    a.Hp = 1; a.Wp = 1; a.in_Hp = 1; a.in_Wp = 1; a.stride = 1; a.S = S > 0 ? S : 1; a.Wimg = Wimg > 0 ? Wimg : 1; a.up = 0; a.flags = MM_FLAG_NONE;
-    a.mode = MM_MODE_DENSE;
+    MMArgs a = mm_args_rows(x0_dev, (int32_t)ld0, K0, w_dev, (int32_t)ldw, y_dev, (int32_t)M, N);
+    if (two) { a.seg[1] = MMSeg{x1_dev, (int32_t)ld1, K1 / 64, 1, 1, 0, 0, K0}; a.nseg = 2; a.P = (int32_t)(K / 64); }
+    a.bias = bias_dev; a.resid = resid_dev; a.ldy = (int32_t)ldy; a.ldr = (int32_t)ldr;
+    if (S > 0) a.S = S;
+    if (Wimg > 0) a.Wimg = Wimg;
     if (mode == GSW_GEMM_GEGLU) a.mode = MM_MODE_GEGLU;
     else if (mode == GSW_GEMM_TRANS) a.mode = MM_MODE_TRANS;
     else if (mode == GSW_GEMM_TOK2PF) { a.mode = MM_MODE_TOK2PF; a.Wp = Wimg + 2; a.Hp = S / Wimg + 2; }
@@ -1921,15 +1741,9 @@ int gsw_gemm_qkv(const void* x_dev, const void* w_dev, const void* bias_dev, voi
     // [M / S][N - N_rows][S] (the value projection transposed, what gsw_attention consumes).  w [N][K]; N_rows % 160 == 0; S % 8 == 0; M % S == 0.
     if (!x_dev || !w_dev || !rows_dev || !trans_dev || M <= 0 || K <= 0 || N <= 0 || N_rows <= 0 || N_rows >= N || S <= 0) return GSW_ERR_BAD_ARG;
     if (K % 64 || N % 8 || N_rows % 160 || (S & 7) || M % S || M > 0x7FFFFF00 || M * (int64_t)K >= ((int64_t)1 << 40) || (int64_t)N * K >= ((int64_t)1 << 31)) return GSW_ERR_UNSUPPORTED;
-    MMArgs a;
-    for (int i = 0; i < 3; ++i) a.seg[i] = MMSeg{x_dev, K, K / 64, 1, 1, 0, 0, 0};
-    a.nseg = 1; a.P = K / 64;
-    a.w = w_dev; a.ldw = K;
-    a.M = (int32_t)M; a.N = N;
-    a.bias = bias_dev; a.rowbias = nullptr; a.resid = nullptr; a.y = rows_dev; a.colstats = nullptr; a.y2 = trans_dev; a.n_rows = N_rows;
-    a.ln_stat = nullptr; a.ln_u = nullptr; a.ln_v = nullptr;
-    a.ldy = N_rows; a.ldr = N_rows; a.ldrb = N;
-    a.Hp = 1; a.Wp = 1; a.in_Hp = 1; a.in_Wp = 1; a.stride = 1; a.S = S; a.Wimg = 1; a.up = 0; a.flags = MM_FLAG_NONE;
+    MMArgs a = mm_args_rows(x_dev, K, K, w_dev, K, rows_dev, (int32_t)M, N);
+    a.bias = bias_dev; a.y2 = trans_dev; a.n_rows = N_rows;
+    a.ldy = N_rows; a.ldr = N_rows; a.S = S;
     a.mode = MM_MODE_QKV;
     return gsw_mm_launch(a, dtype, stream, nullptr);
 }
@@ -1950,8 +1764,7 @@ int gsw_ln_rowstats_finish(const float* records_dev, int slots, int64_t M, int C
     if (!records_dev || !stat_dev || slots <= 0 || M <= 0 || C <= 0) return GSW_ERR_BAD_ARG;
     hipLaunchKernelGGL(gsw_ln_rowstats_finish_kernel, dim3((uint32_t)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(records_dev), slots, M,
                        1.0f / (float)C, eps, reinterpret_cast<float2*>(stat_dev));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = (int)e; return GSW_ERR_HIP; }
+    GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
@@ -1969,16 +1782,10 @@ int gsw_gemm_ln_ex(const void* x_dev, const float* ln_stat_dev, const void* w_de
     if (K % 64 || N % 8 || (mode == GSW_GEMM_GEGLU && N % 160) || (M & 7) || M > 0x7FFFFF00 || M * (int64_t)K >= ((int64_t)1 << 40) || (int64_t)N * K >= ((int64_t)1 << 31)) return GSW_ERR_UNSUPPORTED;
     if (mode == GSW_GEMM_TRANS && (S <= 0 || (S & 7) || M % S)) return GSW_ERR_UNSUPPORTED;
     if (((uintptr_t)u_dev | (uintptr_t)v_dev | (uintptr_t)ln_stat_dev) & 15) return GSW_ERR_BAD_ARG;
-    MMArgs a;
-    for (int i = 0; i < 3; ++i) a.seg[i] = MMSeg{x_dev, K, K / 64, 1, 1, 0, 0, 0};
-    a.nseg = 1; a.P = K / 64;
-    a.w = w_dev; a.ldw = K;
-    a.M = (int32_t)M; a.N = N;
-    a.bias = nullptr; a.rowbias = nullptr; a.resid = nullptr; a.y = y_dev; a.colstats = nullptr; a.y2 = nullptr; a.n_rows = 0;
+    MMArgs a = mm_args_rows(x_dev, K, K, w_dev, K, y_dev, (int32_t)M, N);
     a.ln_stat = ln_stat_dev; a.ln_u = u_dev; a.ln_v = v_dev;
-    const int ncols = mode == GSW_GEMM_GEGLU ? N / 2 : N;
-    a.ldy = ncols; a.ldr = ncols; a.ldrb = N;
-    a.Hp = 1; a.Wp = 1; a.in_Hp = 1; a.in_Wp = 1; a.stride = 1; a.S = S > 0 ? S : 1; a.Wimg = 1; a.up = 0; a.flags = MM_FLAG_NONE;
+    if (mode == GSW_GEMM_GEGLU) a.ldy = a.ldr = N / 2;
+    if (S > 0) a.S = S;
     a.mode = mode == GSW_GEMM_GEGLU ? MM_MODE_GEGLU : mode == GSW_GEMM_TRANS ? MM_MODE_TRANS : MM_MODE_DENSE;
     return gsw_mm_launch(a, dtype, stream, ex);
 }

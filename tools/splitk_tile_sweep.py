@@ -1,4 +1,4 @@
-"""Calibration of the split-K plan at 4-64 images (csrc/gswm_mm.hip: mm_plan): time of one launch (+ its reduce) by tile rows (gsw_mm_config) and forced split count,
+"""Calibration of the split-K plan at 4-64 images (csrc/gswm_mm_plan.h: mm_plan): time of one launch (+ its reduce) by tile rows (gsw_mm_config) and forced split count,
 HBM-cold weights (the launches cycle through weight copies), graph-captured back to back.  Dense proxies of the deep convolutions (same engine loop; M = interior
 pixels, K = 9 C_in) and the long-K linears.  Prints measured microseconds next to the plan's prediction (gsw_mm_predict_us is internal: the model is restated here)."""
 import ctypes as C
