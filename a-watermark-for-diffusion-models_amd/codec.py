@@ -502,6 +502,100 @@ def extract_soft(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresho
     return SoftVote(bits, flags, matches, score, wsum, wsq)
 
 
+# ------------------------------------------------------------------------------------------------ level-weighted keyed search
+class LevelRows(NamedTuple):
+    """What `level_pack` returns, all on z's device: the operands of `trace_keyed_soft_topk`"""
+    signs: torch.Tensor     # uint8 [B, n/8], `sign_pack`'s row
+    planes: torch.Tensor    # uint8 [B, P, n/8], plane k = bit k of the levels, packed MSB first; P = bit length of `levels`
+    wsum: torch.Tensor      # int32 [B], sum of level over the image
+    wsq: torch.Tensor       # int32 [B], sum of level^2 over the image
+    flags: torch.Tensor     # int32 [B], GSW_FLAG_*, as `sign_pack`
+
+
+def level_planes(levels: int) -> int:
+    """P: how many bit planes hold levels 0..`levels` (the bit length of `levels`, 1..4)"""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= int(levels) <= SOFT_MAX_LEVELS:
+        raise ValueError(f"levels must be an int in 1..{SOFT_MAX_LEVELS}, got {levels!r}")
+    return int(levels).bit_length()
+
+
+def level_pack(z: torch.Tensor, thresholds: torch.Tensor) -> LevelRows:
+    """Quantise and pack latents z [B, ...] (fp16/bf16/fp32/fp64) once for the level-weighted keyed search, in one launch (gsw_level_pack):
+    the sign row of `sign_pack` bit for bit, the reliability level of every element -- `extract_soft`'s level_j = #{ i : |z_j| >=
+    thresholds[b][i] }, same exact comparison, NaN -> 0 -- as P bit planes, and the image's sum of levels and of squared levels.
+    thresholds: float32 [levels] or [B, levels] on z's device, levels in 1..15.  n must be a multiple of 8 and at most 1 048 576."""
+    _need_gpu(z, "z")
+    if z.dim() < 2 or z.shape[0] < 1:
+        raise ValueError("z must be [B, ...] with at least one image")
+    B = z.shape[0]
+    _need_gpu(thresholds, "thresholds")
+    _same_device(thresholds, z, "thresholds")
+    if thresholds.dtype != torch.float32 or thresholds.dim() not in (1, 2) or (thresholds.dim() == 2 and thresholds.shape[0] != B):
+        raise ValueError(f"thresholds must be float32 [levels] or [{B}, levels]")
+    levels = thresholds.shape[-1]
+    if not 1 <= levels <= SOFT_MAX_LEVELS:
+        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 8 or n % 8 or n > ROW_MAX_BITS:
+        raise ValueError(f"level_pack needs a lattice of a multiple of 8 elements per image, at most {ROW_MAX_BITS} (got {n})")
+    P = level_planes(levels)
+    signs = torch.empty((B, n // 8), dtype=torch.uint8, device=z.device)
+    planes = torch.empty((B, P, n // 8), dtype=torch.uint8, device=z.device)
+    wsum = torch.empty((B,), dtype=torch.int32, device=z.device)
+    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_level_pack(z.data_ptr(), dt, thresholds.data_ptr(), levels if thresholds.dim() == 2 else 0, levels, signs.data_ptr(),
+                                       planes.data_ptr(), wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
+    return LevelRows(signs, planes, wsum, wsq, flags)
+
+
+def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`trace_keyed_topk` ranked by reliability-weighted margins: (idx int32 [B, k], score int32 [B, k]), best first, ties towards the lower
+    row; past the registry's end idx = -1 and score = INT32_MIN.
+
+    rows: `level_pack`'s result for the images (signs [B, n_bits / 8], planes [B, P, n_bits / 8], wsum [B]; the number of levels is taken
+    as 2**P - 1, which selects the same kernel as any `levels` with P planes), records: as `trace_keyed_topk`.
+    score = sum_j level_j (1 - 2 (sign_j ^ codeword_j)) = wsum - 2 sum_k 2**k popcount(plane_k & (signs ^ codeword)); for records that share
+    one key it is sum_t (2 r_t - 1) score[t] of `extract_soft`.  One search launch (gsw_trace_keyed_soft_topk); n_bits (1 + P) may not
+    exceed 1 048 576 (ValueError).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
+    signs, planes, wsum = rows.signs, rows.planes, rows.wsum
+    _need_gpu(signs, "rows.signs")
+    _need_gpu(planes, "rows.planes")
+    _need_gpu(wsum, "rows.wsum")
+    _need_gpu(records, "records")
+    if signs.dtype != torch.uint8 or signs.dim() != 2:
+        raise ValueError("rows.signs must be uint8 [B, n_bits / 8]")
+    B = signs.shape[0]
+    if planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != signs.shape[1] or not 1 <= planes.shape[1] <= 4:
+        raise ValueError(f"rows.planes must be uint8 [{B}, P, {signs.shape[1]}] with P in 1..4")
+    if wsum.dtype != torch.int32 or tuple(wsum.shape) != (B,):
+        raise ValueError(f"rows.wsum must be int32 [{B}]")
+    if records.dtype != torch.uint8 or records.dim() != 2:
+        raise ValueError("records must be uint8 [U, stride]")
+    for t, name in ((planes, "rows.planes"), (wsum, "rows.wsum"), (records, "records")):
+        _same_device(t, signs, name)
+    U, stride, P = records.shape[0], records.shape[1], planes.shape[1]
+    n_bits, msg_bytes, k = int(n_bits), int(msg_bytes), int(k)
+    if signs.shape[1] * 8 != n_bits:
+        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
+    _record_layout(stride, msg_bytes)
+    if n_bits * (1 + P) > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n_bits} bits with {P} level planes is beyond the search's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
+    lib = N.lib()
+    ws_bytes = lib.gsw_trace_keyed_workspace_bytes(B, U, k)
+    if ws_bytes == 0:
+        raise ValueError(f"libgswm: bad argument (B={B}, records={U}, k={k}: need B >= 1, 1 <= records < 2**31, 1 <= k <= 8)")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=signs.device)
+    idx = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    score = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    with torch.cuda.device(signs.device):
+        N.check(lib.gsw_trace_keyed_soft_topk(signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(), (1 << P) - 1, B, n_bits, records.data_ptr(), stride,
+                                              msg_bytes, U, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))
+    return idx, score
+
+
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)
 TILES =(8, 16, 32)             # supported tile edges, in lattice elements
 

@@ -29,6 +29,9 @@
 // (DESIGN.md section 4.16).  Bits come from
 // the wave's ballot (eight adjacent lanes hold a byte).  Integer sums throughout: no atomics, no workspace, nothing to zero first, every
 // output element written, and the results do not depend on the launch geometry.
+//
+// gsw_level_pack_kernel<T, STEPS> (further down) is the same quantiser and the same level search without a key: the packed sign row, the bits of
+// the levels as STEPS packed planes and the image's sum of levels and of squared levels, the operands of gsw_trace_keyed_soft_topk (DESIGN.md 4.17).
 
 namespace codec_soft {
 
@@ -71,6 +74,38 @@ template <> struct Group8<double> {
     }
 };
 
+// The level search, shared by the vote and by gsw_level_pack.
+// The first `levels` threads rank the row thr[0 .. levels) into s_thr[16]: ascending, -0.0 == 0.0, ties by index, NaNs last, the padding (NaN)
+// after them; the caller's barrier follows.
+__device__ __forceinline__ void rank_thresholds(const float* __restrict__ thr, uint32_t levels, float* s_thr, uint32_t tid) {
+    if (tid <= (uint32_t)SOFT_MAX_LEVELS) {
+        uint32_t rank = tid;                                         // the padding stays where it is
+        float t = __uint_as_float(0x7FC00000u);
+        if (tid < levels) {
+            t = thr[tid];
+            rank = 0;
+            for (uint32_t j = 0; j < levels; ++j) {
+                const float u = thr[j];
+                const bool before = t != t ? (u == u || j < tid) : (u < t || (u == t && j < tid));
+                rank += before ? 1u : 0u;
+            }
+        }
+        s_thr[rank] = t;
+    }
+}
+
+// lv[k] = #{ i : |v[k]| >= s_thr[i] } by bisection over the ranked row, STEPS = bit length of `levels`; v is left as |v|
+template <int STEPS, typename cmp_t>
+__device__ __forceinline__ void levels8(cmp_t (&v)[8], const float* s_thr, uint32_t (&lv)[8]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { v[k] = fabs(v[k]); lv[k] = 0; }   // NaN stays NaN: no threshold counts it
+#pragma unroll
+    for (int h = 1 << (STEPS - 1); h > 0; h >>= 1) {                 // slots lv .. lv + h - 1 hold thresholds <= |z| iff the last of them does
+#pragma unroll
+        for (int k = 0; k < 8; ++k) lv[k] += v[k] >= (cmp_t)s_thr[lv[k] + (uint32_t)h - 1u] ? (uint32_t)h : 0u;
+    }
+}
+
 template <typename T, int STEPS>
 __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArgs p) {
     typedef typename Group8<T>::cmp_t cmp_t;
@@ -85,21 +120,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
     const uint8_t* rec = p.records + (int64_t)b * p.stride;
     const uint8_t* row = reinterpret_cast<const uint8_t*>(lds);
 
-    if (tid <= (uint32_t)SOFT_MAX_LEVELS) {
-        uint32_t rank = tid;                                         // the padding stays where it is
-        float t = __uint_as_float(0x7FC00000u);
-        if (tid < p.levels) {
-            const float* thr = p.thr + (int64_t)b * p.thr_stride;
-            t = thr[tid];
-            rank = 0;
-            for (uint32_t j = 0; j < p.levels; ++j) {
-                const float u = thr[j];
-                const bool before = t != t ? (u == u || j < tid) : (u < t || (u == t && j < tid));
-                rank += before ? 1u : 0u;
-            }
-        }
-        s_thr[rank] = t;
-    }
+    rank_thresholds(p.thr + (int64_t)b * p.thr_stride, p.levels, s_thr, tid);
     record_keystream_to_lds<GSW_WG>(rec, p.nblk, lds);
     __syncthreads();
 
@@ -114,13 +135,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
             cmp_t v[8];
             const uint32_t c = Group8<T>::ld(z + ((size_t)g << 3), p.q, v, flags) ^ (uint32_t)row[g];
             uint32_t lv[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { v[k] = fabs(v[k]); lv[k] = 0; }   // NaN stays NaN: no threshold counts it
-#pragma unroll
-            for (int h = 1 << (STEPS - 1); h > 0; h >>= 1) {         // slots lv .. lv + h - 1 hold thresholds <= |z| iff the last of them does
-#pragma unroll
-                for (int k = 0; k < 8; ++k) lv[k] += v[k] >= (cmp_t)s_thr[lv[k] + (uint32_t)h - 1u] ? (uint32_t)h : 0u;
-            }
+            levels8<STEPS>(v, s_thr, lv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int32_t w = (int32_t)lv[k];
@@ -173,7 +188,110 @@ static int launch_soft(const ExtractSoftArgs& a, int B, hipStream_t st) {
     return launch_soft_steps<T, 4>(a, B, st);
 }
 
+// ---- gsw_level_pack: the operands of the level-weighted keyed search (gswm_keyed_soft.inc) -- the sign row of gsw_sign_pack, the bits of the
+// levels as P = STEPS packed planes, and the two sums of the levels.  [B] workgroups of 256; thread tid walks the groups of eight elements tid,
+// tid + 256, ... and writes one byte of the sign row and of every plane per group (adjacent lanes adjacent bytes).  The quantiser is the vote's
+// (Group8), the level search is levels8 above.  Integer sums, reduced by shuffles and one LDS round: no atomics, no workspace, nothing to zero.
+struct LevelPackArgs {
+    const void* z;          // [B][N]
+    const float* thr;       // [B][thr_stride] or one row
+    uint8_t* signs;         // [B][N / 8]
+    uint8_t* planes;        // [B][STEPS][N / 8], plane k = bit k of the levels
+    int32_t* wsum;          // [B]
+    int32_t* wsq;           // [B]
+    uint32_t* flags;        // [B]
+    int64_t thr_stride;     // floats
+    uint32_t n_elems;       // N
+    uint32_t levels;
+    Thr q;                  // gsw_extract's quantiser
+};
+
+template <typename T, int STEPS>
+__global__ __launch_bounds__(GSW_WG) void gsw_level_pack_kernel(LevelPackArgs p) {
+    typedef typename Group8<T>::cmp_t cmp_t;
+    __shared__ float s_thr[SOFT_MAX_LEVELS + 1];
+    __shared__ uint32_t s_flags[GSW_WG / 64], s_wsum[GSW_WG / 64], s_wsq[GSW_WG / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t b = blockIdx.x;
+    const uint32_t N = p.n_elems, nbytes = N >> 3;
+    rank_thresholds(p.thr + (int64_t)b * p.thr_stride, p.levels, s_thr, tid);
+    __syncthreads();
+
+    const T* z = reinterpret_cast<const T*>(p.z) + (size_t)b * N;
+    uint8_t* signs = p.signs + (size_t)b * nbytes;
+    uint8_t* planes = p.planes + (size_t)b * STEPS * nbytes;
+    uint32_t flags = 0, wsum = 0, wsq = 0;
+    for (uint32_t g = tid; g < nbytes; g += GSW_WG) {               // N % 8 == 0: whole, 16-byte aligned groups
+        cmp_t v[8];
+        signs[g] = (uint8_t)Group8<T>::ld(z + ((size_t)g << 3), p.q, v, flags);
+        uint32_t lv[8];
+        levels8<STEPS>(v, s_thr, lv);
+        uint32_t pl[STEPS];
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) pl[s] = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+#pragma unroll
+            for (int s = 0; s < STEPS; ++s) pl[s] |= ((lv[k] >> s) & 1u) << (7 - k);
+            wsum += lv[k];
+            wsq += lv[k] * lv[k];
+        }
+#pragma unroll
+        for (int s = 0; s < STEPS; ++s) planes[(size_t)s * nbytes + g] = (uint8_t)pl[s];
+    }
+    for (int s = 32; s > 0; s >>= 1) { flags |= __shfl_xor(flags, s, 64); wsum += __shfl_xor(wsum, s, 64); wsq += __shfl_xor(wsq, s, 64); }
+    if (lane == 0) { s_flags[tid >> 6] = flags; s_wsum[tid >> 6] = wsum; s_wsq[tid >> 6] = wsq; }
+    __syncthreads();
+    if (tid == 0) {
+        p.flags[b] = s_flags[0] | s_flags[1] | s_flags[2] | s_flags[3];
+        p.wsum[b] = (int32_t)(s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3]);
+        p.wsq[b] = (int32_t)(s_wsq[0] + s_wsq[1] + s_wsq[2] + s_wsq[3]);
+    }
+}
+
+template <typename T>
+static int launch_level_pack(const LevelPackArgs& a, int B, hipStream_t st) {
+    const dim3 grid((uint32_t)B), wg(GSW_WG);
+    if (a.levels < 2u) hipLaunchKernelGGL((gsw_level_pack_kernel<T, 1>), grid, wg, 0, st, a);   // the bit length of `levels`, as launch_soft
+    else if (a.levels < 4u) hipLaunchKernelGGL((gsw_level_pack_kernel<T, 2>), grid, wg, 0, st, a);
+    else if (a.levels < 8u) hipLaunchKernelGGL((gsw_level_pack_kernel<T, 3>), grid, wg, 0, st, a);
+    else hipLaunchKernelGGL((gsw_level_pack_kernel<T, 4>), grid, wg, 0, st, a);
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
 }  // namespace codec_soft
+
+int gsw_level_pack(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, uint8_t* signs_dev, uint8_t* planes_dev,
+                   int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int B, int64_t n_elems, void* stream) {
+    if (!z_dev || !thr_dev || !signs_dev || !planes_dev || !wsum_dev || !wsq_dev || !flags_dev || B < 1 || n_elems < 1) return GSW_ERR_BAD_ARG;
+    if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
+    if ((uintptr_t)z_dev & 15u) return GSW_ERR_BAD_ARG;                                      // 16-byte loads
+    if ((uintptr_t)thr_dev & 3u) return GSW_ERR_BAD_ARG;
+    if (levels < 1 || levels > codec_soft::SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
+    if (thr_stride != 0 && thr_stride < levels) return GSW_ERR_BAD_ARG;
+    if (n_elems % 8 || n_elems > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;                // (15^2 n fits int32 far beyond this)
+    codec_soft::LevelPackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.z = z_dev;
+    a.thr = thr_dev;
+    a.signs = signs_dev;
+    a.planes = planes_dev;
+    a.wsum = wsum_dev;
+    a.wsq = wsq_dev;
+    a.flags = flags_dev;
+    a.thr_stride = thr_stride;
+    a.n_elems = (uint32_t)n_elems;
+    a.levels = (uint32_t)levels;
+    a.q = make_thr(z_dtype);
+    hipStream_t st = (hipStream_t)stream;
+    switch (z_dtype) {
+        case GSW_F32: return codec_soft::launch_level_pack<float>(a, B, st);
+        case GSW_F16: return codec_soft::launch_level_pack<__half>(a, B, st);
+        case GSW_BF16: return codec_soft::launch_level_pack<__hip_bfloat16>(a, B, st);
+        default: return codec_soft::launch_level_pack<double>(a, B, st);
+    }
+}
 
 int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
                      int64_t thr_stride, int levels, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,

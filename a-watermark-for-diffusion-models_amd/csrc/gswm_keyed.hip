@@ -37,6 +37,7 @@
 // Kernels
 //   gsw_trace_keyed_scan_kernel<T, MSG4> : T in {1, 4, 16, 64} images per workgroup; MSG4: msg_bytes % 4 == 0 (message read as dwords)
 //   gsw_trace_keyed_finish_kernel        : per image: merge the partial lists, output.
+//   (gswm_keyed_soft.inc, included at the end: gsw_trace_keyed_soft_scan_kernel<T, MSG4, P>, the level-weighted search)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -331,3 +332,5 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 }
 
 }  // extern "C"
+
+#include "gswm_keyed_soft.inc"   // gsw_trace_keyed_soft_topk: the same search ranked by reliability-weighted margins

@@ -34,6 +34,12 @@ quantised and packed once (`codec.sign_pack`) and one launch (`codec.trace_keyed
 registers.  For records that share one key s IS the soft score above; under the null model s = 2 X - n, X ~ Bin(n, 1/2) exactly for
 any fixed record and any key, so `log10_p_soft` and the Bonferroni bound carry over.  Only the soft statistic exists across keys.
 
+Reliability levels across keys (`trace_latents_keyed_soft`, `--per_record_keys --keyed_reliability T`; l = 1): the image is quantised once
+into its sign row AND the bit planes of its levels (`codec.level_pack`), and one launch (`codec.trace_keyed_soft_topk`) ranks every record
+by s = sum_j level_j (1 - 2 (h_j XOR e_j)) -- for records of one key the number `reliability=T` ranks by.  Given the levels, the bits of a
+key-independent image under any key are fair coins, so the Hoeffding bound `soft.log10_p(s, sum level^2)` holds across keys as it does
+within one.
+
 Where (`tamper_tile=`, `--tamper_map DIR`): an attributed image can also be asked WHERE it still carries the record's watermark --
 `TraceResult.tamper`, the per-tile agreement with the attributed record's codeword (`tamper.TamperMap`, one `codec.tile_agreement` launch more
 per batch).  The record comes from the registry, not from the image, so each tile's count has the exact binomial null as well.
@@ -166,6 +172,40 @@ def keyed_topk_host(signs, codewords, k: int):
     for u0 in range(0, U, step):
         eb = np.unpackbits(e[u0:u0 + step], axis=1).astype(np.int64)
         scores[:, u0:u0 + step] = (2 * hb - 1) @ (2 * eb - 1).T              # agreeing bits minus differing bits = n - 2 popcount(h ^ e)
+    idx = np.full((B, k), -1, dtype=np.int32)
+    out = np.full((B, k), INT32_MIN, dtype=np.int32)
+    order = np.argsort(-scores, axis=1, kind="stable")[:, :k]
+    m = order.shape[1]
+    idx[:, :m] = order
+    out[:, :m] = np.take_along_axis(scores, order, axis=1)
+    return idx, out
+
+
+def keyed_soft_topk_host(signs, planes, wsum, codewords, k: int):
+    """NumPy restatement of `codec.trace_keyed_soft_topk` that takes the codewords as an argument (int64 arithmetic, a stable sort):
+    signs uint8 [B, n/8], planes uint8 [B, P, n/8] (plane k = bit k of the levels), wsum [B] (must be the sum of the levels the planes
+    hold), codewords uint8 [U, n/8] -> (idx int32 [B, k], score int32 [B, k]),
+    score = wsum - 2 sum_k 2^k popcount(plane_k & (signs ^ codeword)).  Shares no code with the device path."""
+    h = np.asarray(signs, dtype=np.uint8)
+    pl = np.asarray(planes, dtype=np.uint8)
+    e = np.asarray(codewords, dtype=np.uint8)
+    W = np.asarray(wsum).astype(np.int64)
+    if h.ndim != 2 or e.ndim != 2 or pl.ndim != 3 or h.shape[1] != e.shape[1] or pl.shape[0] != h.shape[0] or pl.shape[2] != h.shape[1]:
+        raise ValueError("sign rows, level planes and codewords disagree on the batch or the lattice size")
+    if not 1 <= pl.shape[1] <= 4 or W.shape != (h.shape[0],):
+        raise ValueError("planes must be [B, P, n/8] with P in 1..4 and wsum [B]")
+    B, U, n = h.shape[0], e.shape[0], 8 * h.shape[1]
+    lv = np.zeros((B, n), dtype=np.int64)
+    for p in range(pl.shape[1]):
+        lv += np.unpackbits(pl[:, p], axis=1).astype(np.int64) << p
+    if not np.array_equal(lv.sum(axis=1), W):
+        raise ValueError("wsum is not the sum of the levels in the planes")
+    scores = np.empty((B, U), dtype=np.int64)
+    step = max(1, (1 << 24) // max(n, 1))
+    signed = lv * (1 - 2 * np.unpackbits(h, axis=1).astype(np.int64))        # level_j (1 - 2 h_j)
+    for u0 in range(0, U, step):
+        eb = np.unpackbits(e[u0:u0 + step], axis=1).astype(np.int64)
+        scores[:, u0:u0 + step] = signed @ (1 - 2 * eb).T                     # 1 - 2 (h ^ e) = (1 - 2 h)(1 - 2 e): the weight of the agreeing bits minus the differing
     idx = np.full((B, k), -1, dtype=np.int32)
     out = np.full((B, k), INT32_MIN, dtype=np.int32)
     order = np.argsort(-scores, axis=1, kind="stable")[:, :k]
@@ -646,12 +686,12 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     under that candidate's own key: `codec.extract_batch` + `codec.bit_matches` for the reported candidates only, grouped by key.
     l: cipher bits per lattice element; the codewords then span n l bits.
     tamper_tile: as in `trace_latents`; the map of an image is taken under its best candidate's OWN key (one launch more per batch).
-    reliability: must be None -- a level-weighted search across keys would be a search kernel of its own."""
+    reliability: must be None -- the level-weighted search across keys is a search kernel of its own: `trace_latents_keyed_soft`."""
     import torch
     from . import _native as N
     if reliability is not None:
-        raise ValueError("reliability cannot be combined with trace_latents_keyed (--per_record_keys): the level-weighted search exists "
-                         "for the shared-key registry only")
+        raise ValueError("reliability cannot be combined with trace_latents_keyed (--per_record_keys): the level-weighted search across keys "
+                         "is trace_latents_keyed_soft (--keyed_reliability)")
     if not 0.0 < float(fpr) <= 1.0:
         raise ValueError("fpr must be in (0, 1]")
     z = latents.contiguous()
@@ -702,6 +742,72 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     return out
 
 
+def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
+                             fpr: float = 1e-6, tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed` ranked by reliability-weighted margins (one cipher bit per element): latents [B, ...] on the device -> one
+    TraceResult per image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
+
+    Every lattice element votes with an integer level 0..levels taken from its magnitude -- thresholds: float32 [levels] or [B, levels],
+    None: `soft.uniform_thresholds(latents, levels, clip)`, scaled to each image's RMS.  One `codec.level_pack` launch, one search launch
+    (`codec.trace_keyed_soft_topk`); a candidate's score is sum_j level_j (1 - 2 (sign_j ^ codeword_j)), for records of one key the number
+    `trace_latents(..., reliability=levels)` ranks by.  The p-value is the Hoeffding bound `soft.log10_p(score, wsq)`, Bonferroni over the
+    records: given the levels, the bits of a key-independent image under ANY key are fair coins, so the bound is as valid across keys as
+    within one -- a bound, not the exact binomial tail of `trace_latents_keyed`.  `Candidate.agree` counts the bits of the soft vote under
+    the candidate's own record: one `codec.extract_soft` launch over the reported (image, candidate) pairs.
+    tamper_tile: as in `trace_latents_keyed`, on the packed sign row.  n (1 + P) may not exceed 1 048 576, P the bit length of `levels`."""
+    import torch
+    from . import _native as N
+    from . import soft as S
+    if not 0.0 < float(fpr) <= 1.0:
+        raise ValueError("fpr must be in (0, 1]")
+    z = latents.contiguous()
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    M, mb = registry.message_bits, registry.message_bytes
+    codec.vote_copies(n, M, 1)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    if thresholds is None:
+        thr = S.uniform_thresholds(z, levels, clip)
+    else:
+        thr = thresholds.to(device=z.device, dtype=torch.float32).contiguous()
+    rec_dev = registry.to_device(z.device)
+    rows = codec.level_pack(z, thr)
+    idx, score = codec.trace_keyed_soft_topk(rows, n, rec_dev, mb, k=k)
+    pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy
+    idx_h, score_h = pairs[0], pairs[1]
+    flags_h, wsq_h = rows.flags.cpu().numpy(), rows.wsq.cpu().numpy()
+    U, limit = len(registry), math.log10(float(fpr))
+    out: List[Union[TraceResult, ValueError]] = []
+    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+    for b in range(B):
+        if flags_h[b] & N.GSW_FLAG_NAN:
+            out.append(ValueError("cannot convert float NaN to integer"))
+            continue
+        if flags_h[b] & N.GSW_FLAG_SATURATED:
+            out.append(ValueError("invalid literal for int() with base 2"))
+            continue
+        res = TraceResult()
+        for j in range(k):
+            i, s = int(idx_h[b, j]), int(score_h[b, j])
+            if i < 0:
+                break
+            c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U))
+            reported.append((b, c))
+            res.candidates.append(c)
+        if res.candidates and res.candidates[0].log10_p_any <= limit:
+            res.attributed = res.candidates[0].user_id
+        out.append(res)
+    if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
+        img = torch.tensor([b for b, _ in reported], device=z.device)
+        rec = torch.tensor([c.index for _, c in reported], device=z.device)
+        vote = codec.extract_soft(z.reshape(B, -1)[img].contiguous(), rec_dev[rec].contiguous(), mb, thr if thr.dim() == 1 else thr[img].contiguous())
+        for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
+            c.agree = int(a)
+    if tamper_tile is not None:
+        best = [registry.record_at(r.candidates[0].index) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
+        _attach_tamper_maps(out, z, rows.signs, best, M, 1, tamper_tile, fpr)
+    return out
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result, message_length: int) -> str:
     """One line of trace.txt / stdout"""
@@ -724,11 +830,21 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.keyed_reliability is not None:
+                if not a.per_record_keys:
+                    self.error("--keyed_reliability requires --per_record_keys: it ranks a registry whose records carry their own keys "
+                               "(one key for all users: --reliability)")
+                if a.hard:
+                    self.error("--keyed_reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
+                if a.reliability is not None:
+                    self.error("--keyed_reliability cannot be combined with --reliability: --reliability is the shared-key form of the same statistic")
+                if a.l != 1:
+                    self.error(f"--keyed_reliability cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
             if a.reliability is not None:
                 if a.hard:
                     self.error("--reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
                 if a.per_record_keys:
-                    self.error("--reliability cannot be combined with --per_record_keys: the level-weighted search exists for the shared-key registry only")
+                    self.error("--reliability cannot be combined with --per_record_keys: the level-weighted search across keys is --keyed_reliability")
                 if a.l != 1:
                     self.error(f"--reliability cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
             if a.per_record_keys:
@@ -761,6 +877,9 @@ def build_parser():
     p.add_argument("--reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
                    help="rank by level-weighted margins: every lattice element votes with one of LEVELS (1..15) reliability levels taken from its "
                         "magnitude, the p-value is a Hoeffding bound (shared key, --l 1, not with --hard)")
+    p.add_argument("--keyed_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
+                   help="with --per_record_keys: rank by level-weighted margins across keys, LEVELS (1..15) reliability levels per lattice element, "
+                        "the p-value is a Hoeffding bound (--l 1, not with --hard or --reliability)")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -795,6 +914,8 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
     def run(arrs):
         latents = X.invert_decoded_images(arrs, args)
         tile = args.tile if getattr(args, "tamper_map", None) else None
+        if args.per_record_keys and getattr(args, "keyed_reliability", None) is not None:
+            return trace_latents_keyed_soft(latents, registry, levels=args.keyed_reliability, k=args.top, fpr=args.fpr, tamper_tile=tile)
         if args.per_record_keys:
             return trace_latents_keyed(latents, registry, k=args.top, fpr=args.fpr, l=args.l, tamper_tile=tile)
         return trace_latents(latents, args.key, args.nonce, registry, message_length=args.message_length, k=args.top, fpr=args.fpr, soft=not args.hard,
@@ -825,6 +946,12 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
     return out
 
 
+def _statistic_name(args) -> str:
+    """the `statistic` field of trace.txt's header"""
+    levels = args.reliability if args.reliability is not None else getattr(args, "keyed_reliability", None)
+    return "hard" if args.hard else "soft" if levels is None else f"soft, {levels} reliability levels"
+
+
 def _report(job, outcomes, args, registry, synthetic: bool) -> None:
     from . import extract as X
     from datetime import datetime
@@ -834,7 +961,7 @@ def _report(job, outcomes, args, registry, synthetic: bool) -> None:
         keyed = [("keys", registry.n_keys)] if args.per_record_keys else []
         fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("key_hex", "per record" if keyed else args.key_hex),
                   ("nonce_hex", "per record" if keyed else args.nonce_hex), ("registry", args.registry),
-                  ("users", len(registry)), *keyed, ("message_length", M), ("statistic", "hard" if args.hard else "soft" if args.reliability is None else f"soft, {args.reliability} reliability levels"), ("fpr", args.fpr),
+                  ("users", len(registry)), *keyed, ("message_length", M), ("statistic", _statistic_name(args)), ("fpr", args.fpr),
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:

@@ -664,6 +664,38 @@ int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev,
                      uint8_t* bits_dev, int32_t* score_dev /* NULL ok */, int32_t* wsum_dev /* NULL ok */, int32_t* wsq_dev /* NULL ok */,
                      uint32_t* flags_dev, uint32_t* matches_dev /* NULL ok */, int B, int64_t n_elems, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Keyed registry search ranked by reliability-weighted margins: gsw_trace_keyed_topk with every lattice
+ * element weighted by gsw_extract_soft's level.  One cipher bit per element (l = 1).  Additive: gsw_version() stays 500.
+ *
+ * gsw_level_pack, one launch per batch: z_dev [B, n_elems] (16-byte aligned), thr_dev / thr_stride / levels as gsw_extract_soft;
+ * P = bit length of levels (1 .. 4).
+ *   signs_dev  : uint8 [B, n_elems / 8], bit for bit gsw_sign_pack's row
+ *   planes_dev : uint8 [B, P, n_elems / 8], plane k = bit k of level_j (gsw_extract_soft's level, same widening rules), packed MSB first
+ *   wsum_dev   : int32 [B], sum over the image of level_j          wsq_dev : int32 [B], sum of level_j^2
+ *   flags_dev  : uint32 [B], as gsw_sign_pack
+ * Every output element is written, no atomics, no workspace, nothing to zero first.
+ * GSW_ERR_BAD_ARG: null pointer, B < 1, n_elems < 1, unknown dtype, z_dev not 16-byte aligned, thr_dev not 4-byte aligned, thr_stride neither
+ * 0 nor >= levels, levels outside 1..15.  GSW_ERR_UNSUPPORTED: n_elems % 8 != 0 or n_elems > 1 048 576.
+ *
+ * gsw_trace_keyed_soft_topk: records_dev, record_stride, msg_bytes, n_records, k, idx_dev, score_dev and workspace_dev
+ * (gsw_trace_keyed_workspace_bytes(B, n_records, k) bytes) as gsw_trace_keyed_topk; signs_dev, planes_dev, wsum_dev as gsw_level_pack
+ * writes them for n_elems = n_bits and the same `levels`.
+ *   score = sum_j level_j (1 - 2 (signs_j ^ codeword[u]_j)) = wsum[b] - 2 sum_{k < P} 2^k popcount(plane_k[b] & (signs[b] ^ codeword[u])),
+ *           an exact int32; for records that share one key and nonce it is sum_t (2 r_t - 1) score[b, t] of gsw_extract_soft, r the
+ *           record's message.  With levels = 1 and thr = {0} on NaN-free images it is gsw_trace_keyed_topk's score.
+ *   out   : the k best records per image by (score descending, index ascending), idx = -1 / score = INT32_MIN past the end; the result
+ *           does not depend on the launch geometry.
+ * GSW_ERR_BAD_ARG: as gsw_trace_keyed_topk, plus levels outside 1..15 and wsum_dev not 4-byte aligned.  GSW_ERR_RAGGED: n_bits is not a
+ * multiple of 8 msg_bytes.  GSW_ERR_UNSUPPORTED: n_bits * (1 + P) > 1 048 576 (the sign row and the P plane rows of an image are staged in
+ * 128 KiB of LDS), B > 65535. */
+int gsw_level_pack(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride /* floats; 0: one table for all images */, int levels,
+                   uint8_t* signs_dev, uint8_t* planes_dev, int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int B, int64_t n_elems,
+                   void* stream);
+int gsw_trace_keyed_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_dev, const int32_t* wsum_dev, int levels, int B, int64_t n_bits,
+                              const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records, int k, int32_t* idx_dev,
+                              int32_t* score_dev, void* workspace_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
