@@ -387,6 +387,45 @@ def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, ms
     return idx, score
 
 
+# ------------------------------------------------------------------------------------------------ blind key search (no message)
+def key_search_topk(signs: torch.Tensor, n_bits: int, keys: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k keys of a keyring under which each image looks most like a watermarked one, whatever the message: (idx int32 [B, k], stat
+    int32 [B, k]), best first, ties towards the lower row; past the keyring's end idx = -1 and stat = INT32_MIN.
+
+    signs: uint8 [B, n_bits / 8] (`sign_pack` / `quant_pack`), keys: uint8 [K, stride] rows key[32] | nonce[16], bytes past 48 ignored
+    (`detect.Keyring.to_device`, or `trace.KeyedRegistry.to_device` as it is; stride >= 48, a multiple of 16).  With d the image's bits
+    decrypted under a key and c_t the ones among the n_bits / (8 msg_bytes) copies of message position t, stat = sum_t |2 c_t - copies|:
+    `trace_keyed_topk`'s score of the image's own majority-voted message (`detect.log10_p_blind` is its exact null tail).  One search
+    launch (gsw_key_search_topk).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
+    _need_gpu(signs, "signs")
+    _need_gpu(keys, "keys")
+    if signs.dtype != torch.uint8 or signs.dim() != 2:
+        raise ValueError("signs must be uint8 [B, n_bits / 8]")
+    if keys.dtype != torch.uint8 or keys.dim() != 2:
+        raise ValueError("keys must be uint8 [K, stride]")
+    _same_device(keys, signs, "keys")
+    B, K, stride = signs.shape[0], keys.shape[0], keys.shape[1]
+    n_bits, k = int(n_bits), int(k)
+    if signs.shape[1] * 8 != n_bits:
+        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
+    if isinstance(msg_bytes, bool) or not isinstance(msg_bytes, (int, np.integer)) or not 1 <= int(msg_bytes) <= N.GSW_MSG_INLINE_MAX:
+        raise ValueError(f"msg_bytes {msg_bytes!r} is outside 1..{N.GSW_MSG_INLINE_MAX}")
+    msg_bytes = int(msg_bytes)
+    if stride < KEYED_RECORD_HEAD or stride % 16:
+        raise ValueError(f"key rows of {stride} bytes cannot hold key | nonce at a multiple of 16")
+    lib = N.lib()
+    ws_bytes = lib.gsw_key_search_workspace_bytes(B, K, k)
+    if ws_bytes == 0:
+        raise ValueError(f"libgswm: bad argument (B={B}, keys={K}, k={k}: need B >= 1, 1 <= keys < 2**31, 1 <= k <= 8)")
+    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=signs.device)
+    idx = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    stat = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    with torch.cuda.device(signs.device):
+        N.check(lib.gsw_key_search_topk(signs.data_ptr(), B, n_bits, keys.data_ptr(), stride, msg_bytes, K, k,
+                                        idx.data_ptr(), stat.data_ptr(), ws.data_ptr(), _stream_ptr()))
+    return idx, stat
+
+
 # ------------------------------------------------------------------------------------------------ issuing (one record per image)
 def _records_operand(records: torch.Tensor, msg_bytes: int) -> Tuple[int, int, int]:
     """The checks `embed_records` and `extract_records` share -> (B, stride, msg_bytes)"""

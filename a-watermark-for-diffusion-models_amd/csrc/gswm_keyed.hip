@@ -38,6 +38,7 @@
 //   gsw_trace_keyed_scan_kernel<T, MSG4> : T in {1, 4, 16, 64} images per workgroup; MSG4: msg_bytes % 4 == 0 (message read as dwords)
 //   gsw_trace_keyed_finish_kernel        : per image: merge the partial lists, output.
 //   (gswm_keyed_soft.inc, included at the end: gsw_trace_keyed_soft_scan_kernel<T, MSG4, P>, the level-weighted search)
+//   (gswm_keysearch.inc, included after it: gsw_key_search_scan_kernel<PL, SG>, the blind key search)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -334,3 +335,4 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 }  // extern "C"
 
 #include "gswm_keyed_soft.inc"   // gsw_trace_keyed_soft_topk: the same search ranked by reliability-weighted margins
+#include "gswm_keysearch.inc"    // gsw_key_search_topk: every key of a keyring scored without a message

@@ -1,0 +1,461 @@
+"""Blind detection: is this image watermarked under one of my keys, and what does it say -- without a registry of messages.
+
+`trace` matches an image against messages that were registered when they were issued; `extract` needs the message to say anything about
+its result.  A deployment that rotates keys (per day, per customer, per model) has a list of keys, not a registry: the messages are
+timestamps, request ids and hashes nobody stored.  This module holds that list (`Keyring`), the search (`detect_latents`: one
+`codec.quant_pack` launch, one `codec.key_search_topk` launch over the keyring, one `codec.extract_records` launch that votes every image
+under its own best key) and the exact null distribution of the statistic (`log10_p_blind`), plus a front end
+(`python -m gswm_amd.detect`) on `trace`'s image -> latent -> inversion path.
+
+The statistic.  An image has n_bits quantised bits h, a keyring row u is a (key, nonce) pair, M = 8 msg_bytes, V = n_bits / M copies:
+    d      = h ^ keystream(u)
+    c_t    = #{ j < n_bits : j mod M == t, d_j = 1 }
+    S[b,u] = sum_t |2 c_t - V|
+S is the score `codec.trace_keyed_topk` would give the image's own majority-voted message under that key (a tie adds 0 either way): the
+maximum of the registry score over all 2^M messages.
+
+Null model (the paper's, as in `trace`): an image that is independent of the key decrypts to fair coins.  Then the c_t are independent
+Bin(V, 1/2) and S is the sum of M independent copies of |2 Bin(V, 1/2) - V|: an exact law with no free parameter (`log10_p_blind`).
+Over a keyring of K keys the reported value is the Bonferroni bound `trace.log10_p_any`; a key is named iff that is <= log10(fpr).
+"""
+from __future__ import annotations
+
+import math
+import os
+import sys
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Tuple, Union
+
+import numpy as np
+
+from . import codec
+from . import trace as T
+
+EXACT_MAX_BITS = 65536          # lattices up to here get the exact null tail, larger ones the Chernoff bound
+_LN10 = math.log(10.0)
+_TILTS = 128                    # exponential tilts per (M, V), spaced evenly in the mean they move the statistic to
+
+
+# ===================================================================================================================== statistics
+def _log_pmf_term(V: int) -> Tuple[np.ndarray, np.ndarray]:
+    """One message position under the null: the values a of |2 Bin(V, 1/2) - V| (V, V - 2, ... down to V mod 2, ascending) and
+    log P[a] = log C(V, (V + a) / 2) + [a > 0] log 2 - V log 2."""
+    a = np.arange(V % 2, V + 1, 2, dtype=np.int64)
+    lp = np.array([math.log(math.comb(V, (V + int(x)) // 2)) + (math.log(2.0) if x > 0 else 0.0) for x in a]) - V * math.log(2.0)
+    return a, lp
+
+
+def _tilted(a: np.ndarray, lp: np.ndarray, theta: float) -> Tuple[np.ndarray, float, float]:
+    """The term's pmf tilted by e^(theta a): (q, log Z, mean of q), log-sum-exp throughout"""
+    w = lp + theta * a
+    top = float(w.max())
+    e = np.exp(w - top)
+    z = float(e.sum())
+    q = e / z
+    return q, top + math.log(z), float((q * a).sum())
+
+
+def _theta_for_mean(a: np.ndarray, lp: np.ndarray, mean: float) -> float:
+    """theta >= 0 at which the tilted term has this mean (between the null mean and V, exclusive): bisection, the mean grows with theta"""
+    lo, hi = 0.0, 1.0
+    while _tilted(a, lp, hi)[2] < mean:
+        lo, hi = hi, 2.0 * hi
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        if _tilted(a, lp, mid)[2] < mean:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+class _NullLaw:
+    """The null law of S for one (M, V), as a family of exponentially tilted M-fold convolutions computed on demand.
+
+    Tilt i moves the mean of a term to mu_i = mu_0 + (V - mu_0) i / _TILTS (mu_0 the null mean, theta_0 = 0).  Its pmf q_i = p e^(theta a) / Z
+    is convolved M times in float64 -- positive terms only, no cancellation -- and
+        P[S >= s] = Z^M e^(-theta s) sum_{x >= s} Q_i(x) e^(-theta (x - s))
+    holds for every tilt; a query uses the tilt whose mean is the largest one <= s, so the terms that matter sit in the upper tail of Q_i within
+    one grid step of its mean and never underflow (at the top tilt the event "no term below V", probability >= e^(-M V / 256))."""
+
+    def __init__(self, M: int, V: int):
+        self.M, self.V = M, V
+        self.a, self.lp = _log_pmf_term(V)
+        self.x_min = M * (V % 2)                                     # the support of S is x_min, x_min + 2, .., M V
+        self.mu0 = float((np.exp(self.lp) * self.a).sum())
+        self._tilt: Dict[int, Tuple[float, float, np.ndarray]] = {}
+
+    def _get(self, i: int) -> Tuple[float, float, np.ndarray]:
+        t = self._tilt.get(i)
+        if t is None:
+            theta = 0.0 if i == 0 else _theta_for_mean(self.a, self.lp, self.mu0 + (self.V - self.mu0) * i / _TILTS)
+            q, log_z, _ = _tilted(self.a, self.lp, theta)
+            Q = np.ones(1)
+            for _ in range(self.M):                                 # index j of Q <-> the value x_min-so-far + 2 j
+                Q = np.convolve(Q, q)
+            # R[j] = sum_{j' >= j} Q[j'] e^(-2 theta (j' - j)), from the top down: positive terms
+            R = np.empty_like(Q)
+            decay, run = math.exp(-2.0 * theta), 0.0
+            for j in range(Q.size - 1, -1, -1):
+                run = Q[j] + decay * run
+                R[j] = run
+            t = self._tilt[i] = (theta, self.M * log_z, R)
+        return t
+
+    def log10_tail(self, s: int) -> float:
+        if s <= self.x_min:
+            return 0.0
+        j = (s - self.x_min + 1) // 2                               # the smallest support point >= s
+        x = self.x_min + 2 * j
+        span = self.V - self.mu0
+        i = 0 if span <= 0 else min(_TILTS - 1, max(0, int((x / self.M - self.mu0) / span * _TILTS)))
+        theta, m_log_z, R = self._get(i)
+        return min(0.0, (m_log_z - theta * x + math.log(R[j])) / _LN10)
+
+
+_LAWS: Dict[Tuple[int, int], _NullLaw] = {}
+
+
+def _chernoff_log10(s: int, M: int, V: int) -> float:
+    """log10 of inf_{theta >= 0} E[e^(theta S)] e^(-theta s), S the sum of M terms |2 Bin(V, 1/2) - V|"""
+    a, lp = _log_pmf_term(V)
+    mu0 = float((np.exp(lp) * a).sum())
+    if s <= M * mu0:
+        return 0.0
+    if s >= M * V:
+        return M * float(lp[-1]) / _LN10                             # theta -> infinity: P[every term = V], the exact value at the top
+    theta = _theta_for_mean(a, lp, s / M)
+    return min(0.0, (M * _tilted(a, lp, theta)[1] - theta * s) / _LN10)
+
+
+def log10_p_blind(stat: int, M: int, V: int) -> float:
+    """log10 P[S >= stat] for S = sum of M independent |2 Bin(V, 1/2) - V|: the blind statistic of an image that is independent of the
+    key, M message bits with V copies each.  Finite for every stat in 0 .. M V (0.0 at and below the smallest value S can take).
+
+    M V <= 65536: the EXACT tail to float64 rounding, by M-fold convolution of positive terms.  It does not underflow for strong detections
+    because the pmf is exponentially tilted before the convolution (a grid of 128 tilts per (M, V), computed on first use and cached; the
+    tilt is undone in logarithms).
+    M V > 65536: the CHERNOFF BOUND inf_theta E[e^(theta S)] e^(-theta stat) from the folded binomial's moment generating function -- an
+    upper bound of the tail, not the tail (at stat = M V it is the exact value)."""
+    stat, M, V = int(stat), int(M), int(V)
+    if M < 1 or V < 1:
+        raise ValueError("M and V must be positive")
+    if not 0 <= stat <= M * V:
+        raise ValueError(f"stat {stat} is outside 0..{M * V}")
+    if M * V > EXACT_MAX_BITS:
+        return _chernoff_log10(stat, M, V)
+    law = _LAWS.get((M, V))
+    if law is None:
+        law = _LAWS[(M, V)] = _NullLaw(M, V)
+    return law.log10_tail(stat)
+
+
+# ===================================================================================================================== keyring
+def _check_key_id(key_id) -> None:
+    if not isinstance(key_id, str) or not key_id or any(ch in key_id for ch in "\t\r\n"):
+        raise ValueError(f"key id {key_id!r} must be a non-empty string without tabs or line breaks")
+
+
+class Keyring:
+    """Ordered key_id -> (key, nonce) rows with unique ids: the keys a deployment has issued watermarks under"""
+
+    def __init__(self):
+        self._ids: List[str] = []
+        self._rows: List[Tuple[bytes, bytes]] = []
+        self._by_id: Dict[str, int] = {}
+        self._device_cache = {}
+
+    def __len__(self) -> int:
+        return len(self._ids)
+
+    @property
+    def key_ids(self) -> List[str]:
+        return list(self._ids)
+
+    def key_at(self, index: int) -> str:
+        return self._ids[index]
+
+    def row_at(self, index: int) -> Tuple[bytes, bytes]:
+        return self._rows[index]
+
+    def add(self, key_id: str, key: Union[str, bytes], nonce: Union[str, bytes]) -> int:
+        """Add (key, nonce) as `key_id`; returns the row index.  key (32 bytes) and nonce (16 bytes) are bytes or hex strings."""
+        _check_key_id(key_id)
+        try:
+            key, nonce = T._as_bytes(key, "key"), T._as_bytes(nonce, "nonce")
+        except ValueError:
+            raise ValueError(f"key {key_id!r}: key and nonce must be hexadecimal") from None
+        if key is None or len(key) != 32:
+            raise ValueError(f"key {key_id!r}: the ChaCha20 key must be 32 bytes")
+        if nonce is None or len(nonce) != 16:
+            raise ValueError(f"key {key_id!r}: the ChaCha20 nonce must be 16 bytes")
+        if key_id in self._by_id:
+            raise ValueError(f"key id {key_id!r} is already in the keyring")
+        self._by_id[key_id] = len(self._ids)
+        self._ids.append(key_id)
+        self._rows.append((key, nonce))
+        self._device_cache.clear()
+        return len(self._ids) - 1
+
+    # -- files
+    def save(self, path) -> None:
+        """one `key_id<TAB>key_hex<TAB>nonce_hex` per line"""
+        with open(path, "w") as f:
+            for kid, (key, nonce) in zip(self._ids, self._rows):
+                f.write(f"{kid}\t{key.hex()}\t{nonce.hex()}\n")
+
+    @classmethod
+    def load(cls, path) -> "Keyring":
+        ring = cls()
+        with open(path) as f:
+            for no, line in enumerate(f, 1):
+                line = line.rstrip("\r\n")
+                if not line:
+                    continue
+                cols = line.split("\t")
+                if len(cols) != 3:
+                    raise ValueError(f"{path}:{no}: expected 'key_id<TAB>key_hex<TAB>nonce_hex'")
+                try:
+                    key, nonce = (bytes.fromhex(c.strip()) for c in cols[1:])
+                except ValueError:
+                    raise ValueError(f"{path}:{no}: key {cols[0]!r} is not hexadecimal") from None
+                try:
+                    ring.add(cols[0], key, nonce)
+                except ValueError as e:
+                    raise ValueError(f"{path}:{no}: {e}") from None
+        if not len(ring):
+            raise ValueError(f"{path}: no keyring entries")
+        return ring
+
+    @classmethod
+    def from_info_data(cls, path) -> "Keyring":
+        """The distinct (key, nonce) pairs of the log gs_insert appends per issued watermark, in order of first use; ids
+        `info:<record number>` of the first record under that pair (numbered as `trace.Registry.from_info_data` numbers them)."""
+        ring, seen = cls(), set()
+        for number, key, nonce, _ in T._info_data_records(path):
+            if key is None or nonce is None:
+                raise ValueError(f"{path}: record {number} has no key / nonce")
+            pair = (bytes.fromhex(key), bytes.fromhex(nonce))
+            if pair not in seen:
+                seen.add(pair)
+                ring.add(f"info:{number}", *pair)
+        if not len(ring):
+            raise ValueError(f"{path}: no records")
+        return ring
+
+    @classmethod
+    def from_keyed_registry(cls, kreg: "T.KeyedRegistry") -> "Keyring":
+        """The distinct (key, nonce) pairs of a keyed registry, in order; a pair takes the id of its first record"""
+        ring, seen = cls(), set()
+        for i in range(len(kreg)):
+            key, nonce, _ = kreg.record_at(i)
+            if (key, nonce) not in seen:
+                seen.add((key, nonce))
+                ring.add(kreg.user_at(i), key, nonce)
+        if not len(ring):
+            raise ValueError("the registry is empty")
+        return ring
+
+    # -- device
+    def packed(self) -> np.ndarray:
+        """uint8 [K, 48]: a row is key[32] | nonce[16] (the key rows of `codec.key_search_topk`)"""
+        if not self._ids:
+            raise ValueError("the keyring is empty")
+        t = self._device_cache.get("host")
+        if t is None:
+            flat = np.frombuffer(b"".join(k + n for k, n in self._rows), dtype=np.uint8)
+            t = self._device_cache["host"] = flat.reshape(len(self._ids), codec.KEYED_RECORD_HEAD).copy()
+        return t
+
+    def to_device(self, device="cuda"):
+        import torch
+        k = str(torch.device(device))
+        t = self._device_cache.get(k)
+        if t is None:
+            t = self._device_cache[k] = torch.from_numpy(self.packed()).to(device)
+        return t
+
+
+# ===================================================================================================================== detection
+@dataclass
+class KeyCandidate:
+    key_id: str
+    index: int
+    stat: int
+    log10_p_any: float          # Bonferroni bound over the keyring
+
+
+@dataclass
+class DetectResult:
+    candidates: List[KeyCandidate] = field(default_factory=list)
+    key_id: Optional[str] = None        # the best candidate's key id if its bound is <= log10(fpr), else None: none of these keys
+    message: Optional[bytes] = None     # the majority-voted message under that key (None when no key is named)
+    flags: int = 0                      # GSW_FLAG_* of the image (a saturated or NaN latent: the reference refuses such an image)
+
+
+def _message_bytes(message_length) -> int:
+    m = int(message_length)
+    if m < 8 or m % 8 or m > 8 * 256:
+        raise ValueError(f"message_length {message_length!r} must be a multiple of 8 in 8..2048 bits")
+    return m // 8
+
+
+def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1, fpr: float = 1e-6, l: int = 1) -> List[DetectResult]:
+    """latents [B, ...] on the device -> one DetectResult per image: the k best keys of the keyring (best first) with their Bonferroni
+    bounds, the key that is named at false-positive rate `fpr` per image over the whole keyring (or None) and the message voted under it.
+
+    Three launches: `codec.quant_pack` (the image is quantised once, whatever the number of keys), `codec.key_search_topk` (every key's
+    keystream is generated inside it) and `codec.extract_records`, which votes every image under its own best key (its rows are that key
+    and nonce with a zero message; `matches` is ignored).  The host receives the B k (index, stat) pairs, the flags and the voted bytes.
+    l: cipher bits per lattice element the images were embedded with; the rows then hold n l bits.  Raises IndexError where
+    `extract_batch` does (n l is not a multiple of message_length)."""
+    import torch
+    if not 0.0 < float(fpr) <= 1.0:
+        raise ValueError("fpr must be in (0, 1]")
+    mb = _message_bytes(message_length)
+    M = 8 * mb
+    l = codec.check_window(l)
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    keys_host = keyring.packed()                                   # (an empty keyring fails here)
+    z = latents.contiguous()
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    V = codec.vote_copies(n, M, l)                                 # (a lattice the message does not tile fails here, as extract_batch would)
+    nb = n * l
+    keys_dev = keyring.to_device(z.device) if z.is_cuda else torch.from_numpy(keys_host)
+    packed, flags = codec.quant_pack(z, l)
+    idx, stat = codec.key_search_topk(packed, nb, keys_dev, mb, k=k)
+    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
+    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
+    bits, _, _ = codec.extract_records(z, rows, mb, l=l)
+    pairs = torch.stack([idx, stat]).cpu().numpy()                 # the B k (index, stat) pairs in one copy
+    idx_h, stat_h = pairs[0], pairs[1]
+    flags_h, bits_h = flags.cpu().numpy(), bits.cpu().numpy()
+    K, limit = len(keyring), math.log10(float(fpr))
+    out: List[DetectResult] = []
+    for b in range(B):
+        res = DetectResult(flags=int(flags_h[b]))
+        for j in range(k):
+            i, s = int(idx_h[b, j]), int(stat_h[b, j])
+            if i < 0:
+                break
+            res.candidates.append(KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), K)))
+        if res.candidates and res.candidates[0].log10_p_any <= limit:
+            res.key_id = res.candidates[0].key_id
+            res.message = bits_h[b].tobytes()
+        out.append(res)
+    return out
+
+
+# ===================================================================================================================== front end
+def format_line(name: str, result) -> str:
+    """One line of detect.txt / stdout"""
+    if isinstance(result, Exception):
+        return f"Error processing {name}: {result}"
+    if not result.candidates:
+        return f"{name}, key: none, log10 p, 0.0"
+    c = result.candidates[0]
+    text = f"{name}, key: {result.key_id if result.key_id is not None else 'none'}, log10 p, {c.log10_p_any:.3f}"
+    text += f", message: {result.message.hex() if result.message is not None else 'none'}"
+    for o in result.candidates[1:]:
+        text += f", next: {o.key_id} ({o.log10_p_any:.3f})"
+    if result.flags:
+        text += f", flags {result.flags}"
+    return text
+
+
+def _fpr(text: str) -> float:
+    v = float(text)
+    if not 0.0 < v <= 1.0:
+        raise ValueError("fpr must be in (0, 1]")
+    return v
+
+
+def build_parser():
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m gswm_amd.detect",
+                                description="Name the key of a keyring an image is watermarked under, and read its message, without a registry "
+                                            "of messages (single GPU)")
+    p.add_argument("--model_id", default="stabilityai/stable-diffusion-2-1-base")
+    p.add_argument("--images_directory_path", default="", help="The path of directory containing images to process")
+    p.add_argument("--single_image_path", default="")
+    p.add_argument("--keyring", required=True, help="keyring file: 'key_id<TAB>key_hex<TAB>nonce_hex' lines, or the info_data.txt log gs_insert "
+                                                     "appends (told apart by the first line; of a log, the distinct key / nonce pairs are used)")
+    p.add_argument("--message_length", type=int, default=256, help="Length of the message in bits (a multiple of 8, at most 2048)")
+    p.add_argument("--fpr", type=_fpr, default=1e-6, help="false-positive rate per image, over the whole keyring (Bonferroni), in (0, 1]")
+    p.add_argument("--top", type=int, default=1, choices=range(1, 9), metavar="K", help="candidate keys reported per image (1..8)")
+    p.add_argument("--l", type=int, default=1, choices=codec.WINDOWS, help="cipher bits per lattice element the images were embedded with")
+    p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
+    p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
+    p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
+    p.add_argument("--width", type=int, default=1024, help="Width of the input image")
+    p.add_argument("--height", type=int, default=1024, help="Height of the input image")
+    p.add_argument("--allow_synthetic_weights", action="store_true", help="run without a checkpoint (pipeline tests / benchmarks only)")
+    p.add_argument("--batch_size", type=int, default=16, help="images per device batch")
+    p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
+                   help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
+    return p
+
+
+def load_keyring(path) -> Keyring:
+    """gs_insert's log or the three-column format, told apart by the first line"""
+    return Keyring.from_info_data(path) if T.detect_format(path) == "info_data" else Keyring.load(path)
+
+
+def _detect_files(files, args, keyring) -> list:
+    """files -> outcomes in order (DetectResult or the exception that file raised): `trace`'s decode / invert / batch path with this
+    module's search in place of the registry search"""
+    return T._trace_files(files, args, keyring,
+                          trace_batch=lambda latents: detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l))
+
+
+def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
+    from . import extract as X
+    from datetime import datetime
+    with open(os.path.join(job.path, "detect.txt"), "a") as out:
+        bar = "=" * 40
+        fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("keyring", args.keyring), ("keys", len(keyring)),
+                  ("message_length", args.message_length), ("l", args.l), ("fpr", args.fpr),
+                  ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
+        out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
+        if synthetic:
+            out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
+        for f, r in zip(job.files, outcomes):
+            line = format_line(f if isinstance(r, Exception) else os.path.basename(f), r)
+            print(line)
+            out.write(line + "\n")
+        out.write(bar + "Batch End" + bar + "\n")
+
+
+def main(argv=None):
+    args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    from . import extract as X
+    _message_bytes(args.message_length)                            # fails before any model loads
+    keyring = load_keyring(args.keyring)
+    keyring.packed()
+    synthetic = X._no_checkpoint(args.model_id)
+    with X._strictness(args, synthetic):
+        if args.images_directory_path != "":
+            script = X._plan(args)
+            jobs = [j for kind, j in script if kind == "job"]
+            if any(j.files for j in jobs):
+                X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))      # fail before touching any result file
+            for kind, x in script:
+                if kind == "banner":
+                    print("=" * 20 + x + "=" * 20)
+                elif x.files:
+                    _report(x, _detect_files(x.files, args, keyring), args, keyring, synthetic)
+        elif args.single_image_path != "":
+            if synthetic:
+                X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))
+                print(f"{X.SYNTHETIC_MARKER}: '{args.model_id}' is not a local checkpoint, the detection below is not meaningful", file=sys.stderr)
+            r = _detect_files([args.single_image_path], args, keyring)[0]
+            print(format_line(args.single_image_path if isinstance(r, Exception) else os.path.basename(args.single_image_path), r))
+        else:
+            print("Please set the argument 'images_directory_path' or 'single_image_path'")
+
+
+if __name__ == "__main__":
+    main()

@@ -899,9 +899,10 @@ def build_parser():
     return p
 
 
-def _trace_files(files: Sequence[str], args, registry) -> list:
+def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list:
     """files -> outcomes in order (TraceResult or the exception that file raised): decode on host threads, invert and trace in device
-    batches; a batch that raises is redone image by image so that each reports its own error (extract._recover_items does the same)."""
+    batches; a batch that raises is redone image by image so that each reports its own error (extract._recover_items does the same).
+    trace_batch: None, or what to do with a batch of inverted latents instead of the registry search (`detect` runs its key search here)."""
     from concurrent.futures import ThreadPoolExecutor
     from . import extract as X
 
@@ -913,6 +914,8 @@ def _trace_files(files: Sequence[str], args, registry) -> list:
 
     def run(arrs):
         latents = X.invert_decoded_images(arrs, args)
+        if trace_batch is not None:
+            return trace_batch(latents)
         tile = args.tile if getattr(args, "tamper_map", None) else None
         if args.per_record_keys and getattr(args, "keyed_reliability", None) is not None:
             return trace_latents_keyed_soft(latents, registry, levels=args.keyed_reliability, k=args.top, fpr=args.fpr, tamper_tile=tile)

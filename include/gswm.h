@@ -696,6 +696,30 @@ int gsw_trace_keyed_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_de
                               const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records, int k, int32_t* idx_dev,
                               int32_t* score_dev, void* workspace_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Blind key search: which keys of a keyring does an image carry a watermark under, whatever the message.
+ * Additive: gsw_version() stays 500.
+ *
+ *   signs_dev : uint8 [B, n_bits / 8], the row gsw_sign_pack or gsw_quant_pack writes (any alignment)
+ *   keys_dev  : uint8 [n_keys, key_stride], 16-byte aligned; a row is key[32] | nonce16[16], bytes past 48 are ignored (the record rows of
+ *               gsw_trace_keyed_topk can be passed as they are); key_stride >= 48, % 16 == 0
+ *   M = 8 msg_bytes message positions, V = n_bits / M copies of each
+ *   d         = signs[b] ^ keystream(key_u, nonce16_u) over n_bits bits (initial counter and carry as gsw_keystream), generated inside the
+ *               launch and never stored
+ *   c_t       = #{ j < n_bits : j mod M == t, d_j = 1 }
+ *   stat[b,u] = sum_t |2 c_t - V|, an exact int32: the score gsw_trace_keyed_topk gives the image's own majority-voted message under key u
+ *               (a tie adds 0 whichever way it is broken), i.e. the maximum of that score over all 2^M messages.  For an image that is
+ *               independent of the key the c_t are independent Bin(V, 1/2).
+ *   out       : the k best keys per image by (stat descending, index ascending), idx = -1 / stat = INT32_MIN past the end of the keyring;
+ *               workspace_dev: gsw_key_search_workspace_bytes(B, n_keys, k) bytes owned by the caller.  Every output element is written,
+ *               no atomics; the result depends on neither the launch geometry nor the arrival order.
+ * GSW_ERR_BAD_ARG: null pointer, B < 1, k outside 1..8, msg_bytes outside 1..256, n_bits < 1, n_keys outside 1..2^31-1, a bad stride or
+ * alignment of keys_dev.  GSW_ERR_RAGGED: n_bits is not a multiple of 8 msg_bytes.  GSW_ERR_UNSUPPORTED: n_bits > 1 048 576, B > 65535.
+ * Every refusal happens before any launch.  gsw_key_search_workspace_bytes returns 0 for B, n_keys, k that gsw_key_search_topk refuses. */
+size_t gsw_key_search_workspace_bytes(int B, int64_t n_keys, int k);
+int gsw_key_search_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* keys_dev, int64_t key_stride, int msg_bytes, int64_t n_keys,
+                        int k, int32_t* idx_dev, int32_t* stat_dev, void* workspace_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
