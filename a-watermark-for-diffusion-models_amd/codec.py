@@ -309,14 +309,62 @@ def keyed_record_stride(msg_bytes: int) -> int:
     return (KEYED_RECORD_HEAD + int(msg_bytes) + 15) // 16 * 16
 
 
-def _record_layout(stride: int, msg_bytes) -> int:
-    """msg_bytes of a records operand with rows of `stride` bytes, as an int, or ValueError"""
+def _msg_bytes_arg(msg_bytes) -> int:
+    """msg_bytes as an int, or ValueError"""
     if isinstance(msg_bytes, bool) or not isinstance(msg_bytes, (int, np.integer)) or not 1 <= int(msg_bytes) <= N.GSW_MSG_INLINE_MAX:
         raise ValueError(f"msg_bytes {msg_bytes!r} is outside 1..{N.GSW_MSG_INLINE_MAX}")
-    msg_bytes = int(msg_bytes)
+    return int(msg_bytes)
+
+
+def _record_layout(stride: int, msg_bytes) -> int:
+    """msg_bytes of a records operand with rows of `stride` bytes, as an int, or ValueError"""
+    msg_bytes = _msg_bytes_arg(msg_bytes)
     if stride < KEYED_RECORD_HEAD + msg_bytes or stride % 16:
         raise ValueError(f"record rows of {stride} bytes cannot hold key | nonce | {msg_bytes}-byte message at a multiple of 16")
     return msg_bytes
+
+
+def _key_layout(stride: int, msg_bytes) -> int:
+    """... of a keys operand: a key row is a record's head, the bytes past it are ignored"""
+    msg_bytes = _msg_bytes_arg(msg_bytes)
+    if stride < KEYED_RECORD_HEAD or stride % 16:
+        raise ValueError(f"key rows of {stride} bytes cannot hold key | nonce at a multiple of 16")
+    return msg_bytes
+
+
+def _search_operands(signs, n_bits, rows, msg_bytes, k, *, rows_name="records", rows_shape="[U, stride]", layout=_record_layout, prefix="", extras=()):
+    """The checks the searches over packed sign rows share -> (B, U, stride, n_bits, msg_bytes, k).  rows: the records or keys; layout: their stride rule
+    (`_record_layout` takes msg_bytes through int() first, as these searches always did; `_key_layout` as it is); extras: (tensor, name, check(B)) of further
+    per-image operands, checked between the sign rows and `rows`."""
+    _need_gpu(signs, prefix + "signs")
+    for t, name, _ in extras:
+        _need_gpu(t, name)
+    _need_gpu(rows, rows_name)
+    if signs.dtype != torch.uint8 or signs.dim() != 2:
+        raise ValueError(f"{prefix}signs must be uint8 [B, n_bits / 8]")
+    B = signs.shape[0]
+    for _, _, check in extras:
+        check(B)
+    if rows.dtype != torch.uint8 or rows.dim() != 2:
+        raise ValueError(f"{rows_name} must be uint8 {rows_shape}")
+    for t, name in [e[:2] for e in extras] + [(rows, rows_name)]:
+        _same_device(t, signs, name)
+    n_bits = int(n_bits)
+    if layout is _record_layout:
+        msg_bytes = int(msg_bytes)
+    k = int(k)
+    if signs.shape[1] * 8 != n_bits:
+        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
+    return B, rows.shape[0], rows.shape[1], n_bits, layout(rows.shape[1], msg_bytes), k
+
+
+def _search_outputs(workspace_bytes, B: int, U: int, k: int, what: str, device):
+    """The workspace query of a search and its allocations -> (ws int64, idx int32 [B, k], score int32 [B, k])"""
+    ws_bytes = workspace_bytes(B, U, k)
+    if ws_bytes == 0:
+        raise ValueError(f"libgswm: bad argument (B={B}, {what}={U}, k={k}: need B >= 1, 1 <= {what} < 2**31, 1 <= k <= 8)")
+    return (torch.empty(ws_bytes // 8, dtype=torch.int64, device=device), torch.empty((B, k), dtype=torch.int32, device=device),
+            torch.empty((B, k), dtype=torch.int32, device=device))
 
 
 def sign_pack(z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -362,25 +410,9 @@ def trace_keyed_topk(signs: torch.Tensor, n_bits: int, records: torch.Tensor, ms
     (`trace.KeyedRegistry.to_device`; stride >= 48 + msg_bytes, a multiple of 16).  The codeword of a record is what `embed_batch`
     plants for its key, nonce and message; score = n_bits - 2 popcount(signs ^ codeword).  Raises IndexError when n_bits is not a
     multiple of 8 msg_bytes (as `extract_batch` does for such a message length)."""
-    _need_gpu(signs, "signs")
-    _need_gpu(records, "records")
-    if signs.dtype != torch.uint8 or signs.dim() != 2:
-        raise ValueError("signs must be uint8 [B, n_bits / 8]")
-    if records.dtype != torch.uint8 or records.dim() != 2:
-        raise ValueError("records must be uint8 [U, stride]")
-    _same_device(records, signs, "records")
-    B, U, stride = signs.shape[0], records.shape[0], records.shape[1]
-    n_bits, msg_bytes, k = int(n_bits), int(msg_bytes), int(k)
-    if signs.shape[1] * 8 != n_bits:
-        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
-    _record_layout(stride, msg_bytes)
+    B, U, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, records, msg_bytes, k)
     lib = N.lib()
-    ws_bytes = lib.gsw_trace_keyed_workspace_bytes(B, U, k)
-    if ws_bytes == 0:
-        raise ValueError(f"libgswm: bad argument (B={B}, records={U}, k={k}: need B >= 1, 1 <= records < 2**31, 1 <= k <= 8)")
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=signs.device)
-    idx = torch.empty((B, k), dtype=torch.int32, device=signs.device)
-    score = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    ws, idx, score = _search_outputs(lib.gsw_trace_keyed_workspace_bytes, B, U, k, "records", signs.device)
     with torch.cuda.device(signs.device):
         N.check(lib.gsw_trace_keyed_topk(signs.data_ptr(), B, n_bits, records.data_ptr(), stride, msg_bytes, U, k,
                                          idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))
@@ -397,29 +429,9 @@ def key_search_topk(signs: torch.Tensor, n_bits: int, keys: torch.Tensor, msg_by
     decrypted under a key and c_t the ones among the n_bits / (8 msg_bytes) copies of message position t, stat = sum_t |2 c_t - copies|:
     `trace_keyed_topk`'s score of the image's own majority-voted message (`detect.log10_p_blind` is its exact null tail).  One search
     launch (gsw_key_search_topk).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
-    _need_gpu(signs, "signs")
-    _need_gpu(keys, "keys")
-    if signs.dtype != torch.uint8 or signs.dim() != 2:
-        raise ValueError("signs must be uint8 [B, n_bits / 8]")
-    if keys.dtype != torch.uint8 or keys.dim() != 2:
-        raise ValueError("keys must be uint8 [K, stride]")
-    _same_device(keys, signs, "keys")
-    B, K, stride = signs.shape[0], keys.shape[0], keys.shape[1]
-    n_bits, k = int(n_bits), int(k)
-    if signs.shape[1] * 8 != n_bits:
-        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
-    if isinstance(msg_bytes, bool) or not isinstance(msg_bytes, (int, np.integer)) or not 1 <= int(msg_bytes) <= N.GSW_MSG_INLINE_MAX:
-        raise ValueError(f"msg_bytes {msg_bytes!r} is outside 1..{N.GSW_MSG_INLINE_MAX}")
-    msg_bytes = int(msg_bytes)
-    if stride < KEYED_RECORD_HEAD or stride % 16:
-        raise ValueError(f"key rows of {stride} bytes cannot hold key | nonce at a multiple of 16")
+    B, K, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, keys, msg_bytes, k, rows_name="keys", rows_shape="[K, stride]", layout=_key_layout)
     lib = N.lib()
-    ws_bytes = lib.gsw_key_search_workspace_bytes(B, K, k)
-    if ws_bytes == 0:
-        raise ValueError(f"libgswm: bad argument (B={B}, keys={K}, k={k}: need B >= 1, 1 <= keys < 2**31, 1 <= k <= 8)")
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=signs.device)
-    idx = torch.empty((B, k), dtype=torch.int32, device=signs.device)
-    stat = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    ws, idx, stat = _search_outputs(lib.gsw_key_search_workspace_bytes, B, K, k, "keys", signs.device)
     with torch.cuda.device(signs.device):
         N.check(lib.gsw_key_search_topk(signs.data_ptr(), B, n_bits, keys.data_ptr(), stride, msg_bytes, K, k,
                                         idx.data_ptr(), stat.data_ptr(), ws.data_ptr(), _stream_ptr()))
@@ -600,35 +612,22 @@ def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, m
     one key it is sum_t (2 r_t - 1) score[t] of `extract_soft`.  One search launch (gsw_trace_keyed_soft_topk); n_bits (1 + P) may not
     exceed 1 048 576 (ValueError).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
     signs, planes, wsum = rows.signs, rows.planes, rows.wsum
-    _need_gpu(signs, "rows.signs")
-    _need_gpu(planes, "rows.planes")
-    _need_gpu(wsum, "rows.wsum")
-    _need_gpu(records, "records")
-    if signs.dtype != torch.uint8 or signs.dim() != 2:
-        raise ValueError("rows.signs must be uint8 [B, n_bits / 8]")
-    B = signs.shape[0]
-    if planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != signs.shape[1] or not 1 <= planes.shape[1] <= 4:
-        raise ValueError(f"rows.planes must be uint8 [{B}, P, {signs.shape[1]}] with P in 1..4")
-    if wsum.dtype != torch.int32 or tuple(wsum.shape) != (B,):
-        raise ValueError(f"rows.wsum must be int32 [{B}]")
-    if records.dtype != torch.uint8 or records.dim() != 2:
-        raise ValueError("records must be uint8 [U, stride]")
-    for t, name in ((planes, "rows.planes"), (wsum, "rows.wsum"), (records, "records")):
-        _same_device(t, signs, name)
-    U, stride, P = records.shape[0], records.shape[1], planes.shape[1]
-    n_bits, msg_bytes, k = int(n_bits), int(msg_bytes), int(k)
-    if signs.shape[1] * 8 != n_bits:
-        raise ValueError(f"sign rows hold {signs.shape[1] * 8} bits, n_bits is {n_bits}")
-    _record_layout(stride, msg_bytes)
+
+    def planes_check(B):
+        if planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != signs.shape[1] or not 1 <= planes.shape[1] <= 4:
+            raise ValueError(f"rows.planes must be uint8 [{B}, P, {signs.shape[1]}] with P in 1..4")
+
+    def wsum_check(B):
+        if wsum.dtype != torch.int32 or tuple(wsum.shape) != (B,):
+            raise ValueError(f"rows.wsum must be int32 [{B}]")
+
+    B, U, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, records, msg_bytes, k, prefix="rows.",
+                                                          extras=((planes, "rows.planes", planes_check), (wsum, "rows.wsum", wsum_check)))
+    P = planes.shape[1]
     if n_bits * (1 + P) > ROW_MAX_BITS:
         raise ValueError(f"a lattice of {n_bits} bits with {P} level planes is beyond the search's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
     lib = N.lib()
-    ws_bytes = lib.gsw_trace_keyed_workspace_bytes(B, U, k)
-    if ws_bytes == 0:
-        raise ValueError(f"libgswm: bad argument (B={B}, records={U}, k={k}: need B >= 1, 1 <= records < 2**31, 1 <= k <= 8)")
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=signs.device)
-    idx = torch.empty((B, k), dtype=torch.int32, device=signs.device)
-    score = torch.empty((B, k), dtype=torch.int32, device=signs.device)
+    ws, idx, score = _search_outputs(lib.gsw_trace_keyed_workspace_bytes, B, U, k, "records", signs.device)
     with torch.cuda.device(signs.device):
         N.check(lib.gsw_trace_keyed_soft_topk(signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(), (1 << P) - 1, B, n_bits, records.data_ptr(), stride,
                                               msg_bytes, U, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))

@@ -34,6 +34,10 @@
 // Top-k.  gswm_topk.h: int64 keys (score << 32) | (0xFFFFFFFF - index); lane lists -> LDS -> one list per (workgroup, image) in the
 // caller's workspace -> gsw_trace_keyed_finish_kernel (one wave per image).  The result depends on neither geometry nor arrival order.
 //
+// Host side.  search_decide (gswm_search_plan.h, host-only: tests/test_search_plan_host.py tabulates it) refuses or plans a launch of this search, of the
+// level-weighted one and of the key search; an entry point fills KeyedArgs from the plan (keyed_args), dispatches the template and launches scan + finish
+// (launch_search).  The workspace queries answer through the same header.
+//
 // Kernels
 //   gsw_trace_keyed_scan_kernel<T, MSG4> : T in {1, 4, 16, 64} images per workgroup; MSG4: msg_bytes % 4 == 0 (message read as dwords)
 //   gsw_trace_keyed_finish_kernel        : per image: merge the partial lists, output.
@@ -41,21 +45,18 @@
 //   (gswm_keysearch.inc, included after it: gsw_key_search_scan_kernel<PL, SG>, the blind key search)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <climits>
 #include <cstdint>
 
 #include "../../include/gswm.h"
 #include "gswm_host.h"     // GSW_HIP, allow_dynamic_lds
-#include "gswm_record.h"   // the record: GSW_REC_HEAD, GSW_ROW_MAX_BITS, records_check (and gswm_chacha.h: CHACHA_QR, quad_perm)
+#include "gswm_record.h"   // the record: GSW_REC_HEAD, GSW_ROW_MAX_BITS (and gswm_chacha.h: CHACHA_QR, quad_perm)
+#include "gswm_search_plan.h"   // search_decide: every refusal and every launch decision of the three searches; KY_WAVES, KY_WG, KS_WG
 #include "gswm_topk.h"
 
 namespace {
 
-constexpr int KY_WAVES = 8;
-constexpr int KY_WG = 64 * KY_WAVES;
-constexpr int KY_MAX_GRID_X = 512;                   // record ranges (two rounds of one workgroup per CU at the largest tiles)
-constexpr uint32_t KY_TILE_LDS = (uint32_t)(GSW_ROW_MAX_BITS / 8);   // sign rows of one image tile: one image of the largest lattice
+static_assert(SEARCH_LIST == TR_LIST, "gswm_search_plan.h sizes the workspace and the top-k tail's LDS for gswm_topk.h's lists");
 
 struct KeyedArgs {
     const uint8_t* signs;     // [B, rowbytes]
@@ -262,33 +263,38 @@ __global__ __launch_bounds__(64) void gsw_trace_keyed_finish_kernel(KeyedArgs a)
     }
 }
 
-int grid_x_for(int64_t n_records) {
-    return (int)std::min<int64_t>((n_records + KY_WAVES - 1) / KY_WAVES, KY_MAX_GRID_X);
+// ---- the host side of the three searches: search_decide (gswm_search_plan.h) decides, these fill the arguments from its plan and launch
+
+SearchQuery search_query(int kind, const void* signs, const void* planes, const void* wsum, const void* records, bool outputs, int B, int64_t n_bits,
+                         int64_t record_stride, int msg_bytes, int64_t n_records, int k, int levels) {
+    auto aligned = [](const void* p, uintptr_t to) { return ((uintptr_t)p & (to - 1)) == 0; };
+    return SearchQuery{kind, B, n_bits, record_stride, n_records, msg_bytes, k, levels, aligned(signs, 4), aligned(planes, 4), aligned(wsum, 4), aligned(records, 16),
+                       !signs, !planes, !wsum, !records, !outputs};
 }
 
-// images per workgroup: the smallest tile that holds the batch (at most 64), halved twice at a time until its sign rows fit
-int tile_images(int B, int nblk) {
-    int t = B > 16 ? 64 : B > 4 ? 16 : B > 1 ? 4 : 1;
-    while (t > 1 && (uint32_t)t * (uint32_t)nblk * 64u > KY_TILE_LDS) t >>= 2;
-    return t;
+KeyedArgs keyed_args(const SearchQuery& q, const SearchPlan& p, const uint8_t* signs, const uint8_t* records, void* workspace, int32_t* idx, int32_t* score) {
+    return KeyedArgs{signs, records, (int64_t*)workspace, idx, score, q.record_stride, q.n_records, q.B, q.k, (int)q.n_bits, p.rowbytes, p.nblk, q.msg_bytes,
+                     p.grid_x, p.signs_aligned};
 }
 
-template <int T, bool MSG4>
-int launch_scan(const KeyedArgs& a, hipStream_t st) {
-    const uint32_t lds = std::max<uint32_t>((uint32_t)T * (uint32_t)a.nblk * 64u, (uint32_t)(KY_WAVES * T * TR_LIST * sizeof(int64_t)));
-    GSW_HIP(allow_dynamic_lds((const void*)gsw_trace_keyed_scan_kernel<T, MSG4>, lds));
-    hipLaunchKernelGGL((gsw_trace_keyed_scan_kernel<T, MSG4>), dim3(a.grid_x, (a.B + T - 1) / T), dim3(KY_WG), lds, st, a);
+// A scan kernel with the plan's grid and LDS, then the finish kernel.
+template <typename Args>
+int launch_search(void (*scan)(Args), const Args& args, const KeyedArgs& a, const SearchPlan& p, hipStream_t st) {
+    GSW_HIP(allow_dynamic_lds((const void*)scan, p.lds));
+    hipLaunchKernelGGL(scan, dim3(p.grid_x, p.grid_y), dim3(p.wg), p.lds, st, args);
+    GSW_HIP(hipGetLastError());
+    hipLaunchKernelGGL(gsw_trace_keyed_finish_kernel, dim3(a.B), dim3(64), 0, st, a);
     GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
 template <bool MSG4>
-int launch_scan_tile(const KeyedArgs& a, int t, hipStream_t st) {
-    switch (t) {
-        case 64: return launch_scan<64, MSG4>(a, st);
-        case 16: return launch_scan<16, MSG4>(a, st);
-        case 4: return launch_scan<4, MSG4>(a, st);
-        default: return launch_scan<1, MSG4>(a, st);
+int launch_scan_tile(const KeyedArgs& a, const SearchPlan& p, hipStream_t st) {
+    switch (p.T) {
+        case 64: return launch_search(gsw_trace_keyed_scan_kernel<64, MSG4>, a, a, p, st);
+        case 16: return launch_search(gsw_trace_keyed_scan_kernel<16, MSG4>, a, a, p, st);
+        case 4: return launch_search(gsw_trace_keyed_scan_kernel<4, MSG4>, a, a, p, st);
+        default: return launch_search(gsw_trace_keyed_scan_kernel<1, MSG4>, a, a, p, st);
     }
 }
 
@@ -297,39 +303,17 @@ int launch_scan_tile(const KeyedArgs& a, int t, hipStream_t st) {
 extern "C" {
 
 size_t gsw_trace_keyed_workspace_bytes(int B, int64_t n_records, int k) {
-    if (B < 1 || n_records < 1 || n_records > (int64_t)INT32_MAX || k < 1 || k > TR_LIST) return 0;
-    return (size_t)B * (size_t)grid_x_for(n_records) * (size_t)k * sizeof(int64_t);
+    return search_workspace_bytes(SEARCH_SIGN, B, n_records, k);
 }
 
 int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
                          int64_t n_records, int k, int32_t* idx_dev, int32_t* score_dev, void* workspace_dev, void* stream) {
-    if (!signs_dev || !idx_dev || !score_dev || !workspace_dev) return GSW_ERR_BAD_ARG;
-    if (B < 1 || k < 1 || k > TR_LIST || n_bits < 1 || n_records > (int64_t)INT32_MAX) return GSW_ERR_BAD_ARG;
-    int rc = records_check(records_dev, record_stride, msg_bytes, n_records);
-    if (rc != GSW_OK) return rc;
-    if (n_bits % (8 * (int64_t)msg_bytes)) return GSW_ERR_RAGGED;
-    if (n_bits > GSW_ROW_MAX_BITS || B > 65535) return GSW_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    KeyedArgs a;
-    a.signs = signs_dev;
-    a.records = records_dev;
-    a.partial = (int64_t*)workspace_dev;
-    a.idx = idx_dev;
-    a.score = score_dev;
-    a.stride = record_stride;
-    a.U = n_records;
-    a.B = B; a.k = k; a.n_bits = (int)n_bits;
-    a.rowbytes = (int)(n_bits / 8);
-    a.nblk = (a.rowbytes + 63) / 64;
-    a.msg_bytes = msg_bytes;
-    a.grid_x = grid_x_for(n_records);
-    a.signs_aligned = (a.rowbytes % 4 == 0) && ((uintptr_t)signs_dev % 4 == 0);
-    const int t = tile_images(B, a.nblk);
-    rc = (msg_bytes % 4 == 0) ? launch_scan_tile<true>(a, t, st) : launch_scan_tile<false>(a, t, st);
-    if (rc != GSW_OK) return rc;
-    hipLaunchKernelGGL(gsw_trace_keyed_finish_kernel, dim3(B), dim3(64), 0, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
+    const SearchQuery q = search_query(SEARCH_SIGN, signs_dev, nullptr, nullptr, records_dev, idx_dev && score_dev && workspace_dev, B, n_bits, record_stride,
+                                       msg_bytes, n_records, k, 0);
+    const SearchPlan p = search_decide(q);
+    if (p.status != GSW_OK) return p.status;
+    const KeyedArgs a = keyed_args(q, p, signs_dev, records_dev, workspace_dev, idx_dev, score_dev);
+    return p.msg4 ? launch_scan_tile<true>(a, p, (hipStream_t)stream) : launch_scan_tile<false>(a, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -12,10 +12,14 @@
 // four words of a block are one 16-byte fragment of every row and a wave reads 1 KiB linearly per row.  Per codeword word a lane forms
 // x = s ^ w once, then per plane v_and + v_bcnt_u32_b32 into a temporary of that plane (plane 0 counts straight into the image's
 // accumulator); the temporaries fold into the accumulator by shift-adds: P - 1 temporaries, not P x T accumulators.  The tile is the
-// largest T in {1, 4, 16, 64} that the batch fills and whose (1 + P) T nblk 64 bytes fit the 128 KiB of the sign search's tile: T decides
-// who computes, never what.  Rows are zero-padded to whole blocks and codeword bytes past the lattice are masked, as there.
+// largest T in {1, 4, 16, 64} that the batch fills and whose (1 + P) T nblk 64 bytes fit the 128 KiB of the sign search's tile (search_decide): T
+// decides who computes, never what.  Rows are zero-padded to whole blocks and codeword bytes past the lattice are masked, as there.
 //
 // The sign search itself is NOT this kernel with P = 0: its record loop stays as it was measured (profiles/trace_keyed_bench.txt).
+// One shared force-inlined body with an `if constexpr (P == 0)` branch was tried at compile level: all 40 instantiations came out with other instruction
+// streams (VGPRs: sign T = 64 134 -> 136 with MSG4, 146 -> 150 without; soft<4, false, *> 80 -> 95), the soft ones too, where only the wrapping changed.
+//
+// Host side: search_decide (gswm_search_plan.h) refuses or plans; the entry point fills the arguments from the plan and dispatches the template.
 //
 // Kernel
 //   gsw_trace_keyed_soft_scan_kernel<T, MSG4, P> : T images per workgroup; MSG4: msg_bytes % 4 == 0; P planes
@@ -170,40 +174,23 @@ __global__ __launch_bounds__(KY_WG) void gsw_trace_keyed_soft_scan_kernel(KeyedS
     workgroup_lists_to_partial<KY_WAVES, T>(wlist, img0, a.B, a.partial, a.grid_x, a.k);
 }
 
-// images per workgroup: the smallest tile that holds the batch (at most 64), divided by four until its (1 + P) rows per image fit
-int soft_tile_images(int B, int nblk, int planes) {
-    int t = B > 16 ? 64 : B > 4 ? 16 : B > 1 ? 4 : 1;
-    while (t > 1 && (uint32_t)(1 + planes) * (uint32_t)t * (uint32_t)nblk * 64u > KY_TILE_LDS) t >>= 2;
-    return t;
-}
-
-template <int T, bool MSG4, int P>
-int launch_soft_scan(const KeyedSoftArgs& s, hipStream_t st) {
-    const KeyedArgs& a = s.base;
-    const uint32_t lds = std::max<uint32_t>((uint32_t)(1 + P) * (uint32_t)T * (uint32_t)a.nblk * 64u, (uint32_t)(KY_WAVES * T * TR_LIST * sizeof(int64_t)));
-    GSW_HIP(allow_dynamic_lds((const void*)gsw_trace_keyed_soft_scan_kernel<T, MSG4, P>, lds));
-    hipLaunchKernelGGL((gsw_trace_keyed_soft_scan_kernel<T, MSG4, P>), dim3(a.grid_x, (a.B + T - 1) / T), dim3(KY_WG), lds, st, s);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
-}
-
 template <bool MSG4, int P>
-int launch_soft_scan_tile(const KeyedSoftArgs& s, int t, hipStream_t st) {
-    switch (t) {
-        case 64: return launch_soft_scan<64, MSG4, P>(s, st);
-        case 16: return launch_soft_scan<16, MSG4, P>(s, st);
-        case 4: return launch_soft_scan<4, MSG4, P>(s, st);
-        default: return launch_soft_scan<1, MSG4, P>(s, st);
+int launch_soft_scan_tile(const KeyedSoftArgs& s, const SearchPlan& p, hipStream_t st) {
+    switch (p.T) {
+        case 64: return launch_search(gsw_trace_keyed_soft_scan_kernel<64, MSG4, P>, s, s.base, p, st);
+        case 16: return launch_search(gsw_trace_keyed_soft_scan_kernel<16, MSG4, P>, s, s.base, p, st);
+        case 4: return launch_search(gsw_trace_keyed_soft_scan_kernel<4, MSG4, P>, s, s.base, p, st);
+        default: return launch_search(gsw_trace_keyed_soft_scan_kernel<1, MSG4, P>, s, s.base, p, st);
     }
 }
 
 template <bool MSG4>
-int launch_soft_scan_planes(const KeyedSoftArgs& s, int planes, int t, hipStream_t st) {
-    switch (planes) {
-        case 1: return launch_soft_scan_tile<MSG4, 1>(s, t, st);
-        case 2: return launch_soft_scan_tile<MSG4, 2>(s, t, st);
-        case 3: return launch_soft_scan_tile<MSG4, 3>(s, t, st);
-        default: return launch_soft_scan_tile<MSG4, 4>(s, t, st);
+int launch_soft_scan_planes(const KeyedSoftArgs& s, const SearchPlan& p, hipStream_t st) {
+    switch (p.planes) {
+        case 1: return launch_soft_scan_tile<MSG4, 1>(s, p, st);
+        case 2: return launch_soft_scan_tile<MSG4, 2>(s, p, st);
+        case 3: return launch_soft_scan_tile<MSG4, 3>(s, p, st);
+        default: return launch_soft_scan_tile<MSG4, 4>(s, p, st);
     }
 }
 
@@ -214,38 +201,12 @@ extern "C" {
 int gsw_trace_keyed_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_dev, const int32_t* wsum_dev, int levels, int B, int64_t n_bits,
                               const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records, int k, int32_t* idx_dev,
                               int32_t* score_dev, void* workspace_dev, void* stream) {
-    if (!signs_dev || !planes_dev || !wsum_dev || !idx_dev || !score_dev || !workspace_dev) return GSW_ERR_BAD_ARG;
-    if (B < 1 || k < 1 || k > TR_LIST || n_bits < 1 || n_records > (int64_t)INT32_MAX || levels < 1 || levels > 15) return GSW_ERR_BAD_ARG;
-    if ((uintptr_t)wsum_dev & 3u) return GSW_ERR_BAD_ARG;
-    int rc = records_check(records_dev, record_stride, msg_bytes, n_records);
-    if (rc != GSW_OK) return rc;
-    if (n_bits % (8 * (int64_t)msg_bytes)) return GSW_ERR_RAGGED;
-    const int planes = levels < 2 ? 1 : levels < 4 ? 2 : levels < 8 ? 3 : 4;              // the bit length of `levels`
-    if (n_bits * (1 + planes) > GSW_ROW_MAX_BITS || B > 65535) return GSW_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    KeyedSoftArgs s;
-    KeyedArgs& a = s.base;
-    a.signs = signs_dev;
-    a.records = records_dev;
-    a.partial = (int64_t*)workspace_dev;
-    a.idx = idx_dev;
-    a.score = score_dev;
-    a.stride = record_stride;
-    a.U = n_records;
-    a.B = B; a.k = k; a.n_bits = (int)n_bits;
-    a.rowbytes = (int)(n_bits / 8);
-    a.nblk = (a.rowbytes + 63) / 64;
-    a.msg_bytes = msg_bytes;
-    a.grid_x = grid_x_for(n_records);
-    a.signs_aligned = (a.rowbytes % 4 == 0) && ((uintptr_t)signs_dev % 4 == 0) && ((uintptr_t)planes_dev % 4 == 0);
-    s.planes = planes_dev;
-    s.wsum = wsum_dev;
-    const int t = soft_tile_images(B, a.nblk, planes);
-    rc = (msg_bytes % 4 == 0) ? launch_soft_scan_planes<true>(s, planes, t, st) : launch_soft_scan_planes<false>(s, planes, t, st);
-    if (rc != GSW_OK) return rc;
-    hipLaunchKernelGGL(gsw_trace_keyed_finish_kernel, dim3(B), dim3(64), 0, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
+    const SearchQuery q = search_query(SEARCH_LEVEL, signs_dev, planes_dev, wsum_dev, records_dev, idx_dev && score_dev && workspace_dev, B, n_bits,
+                                       record_stride, msg_bytes, n_records, k, levels);
+    const SearchPlan p = search_decide(q);
+    if (p.status != GSW_OK) return p.status;
+    const KeyedSoftArgs s{keyed_args(q, p, signs_dev, records_dev, workspace_dev, idx_dev, score_dev), planes_dev, wsum_dev};
+    return p.msg4 ? launch_soft_scan_planes<true>(s, p, (hipStream_t)stream) : launch_soft_scan_planes<false>(s, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -22,6 +22,8 @@
 // The lattice limit is gsw_trace_keyed_topk's (1 048 576 bits).  A row and one key's keystream of it fit the 128 KiB of LDS together up to
 // 523 264 bits; beyond that (SG) the tile is one image whose row is read from global memory and LDS holds the keystream alone.
 //
+// T, G, KPI, the row offset, PL and SG are search_decide's (gswm_search_plan.h), with the refusals; the entry point here fills KeySearchArgs from its plan.
+//
 // Top-k.  gswm_topk.h: group lists -> LDS -> one list per (workgroup, image) in the caller's workspace -> gsw_trace_keyed_finish_kernel.
 // All arithmetic is integer; the result depends on neither geometry nor arrival order.
 //
@@ -29,10 +31,6 @@
 //   gsw_key_search_scan_kernel<PL, SG> : PL counter planes (0: the bit-by-bit path), SG: sign rows read from global memory
 
 namespace {
-
-constexpr int KS_WG = 256;
-constexpr int KS_MAX_GRID_X = 512;
-constexpr uint32_t KS_LDS = (uint32_t)(GSW_ROW_MAX_BITS / 8);   // sign rows of the tile + keystreams of one step
 
 struct KeySearchArgs {
     KeyedArgs base;           // signs, records (= the key rows), partial, idx, score, stride, U, B, k, n_bits, rowbytes, nblk, msg_bytes, grid_x, signs_aligned
@@ -186,52 +184,14 @@ __global__ __launch_bounds__(KS_WG) void gsw_key_search_scan_kernel(KeySearchArg
     }
 }
 
-int key_search_grid_cap(int64_t n_keys) {
-    return (int)std::min<int64_t>(n_keys, KS_MAX_GRID_X);
-}
-
-// Decides T, G, kpi, srow and grid_x of a launch; returns the dynamic LDS bytes.  `sg`: the row does not share the LDS with a keystream.
-uint32_t key_search_plan(KeySearchArgs& s, bool fast, bool sg) {
-    KeyedArgs& a = s.base;
-    const uint32_t rowpad = (uint32_t)a.nblk * 64u;
-    const int units = fast ? a.msg_bytes / 4 : 8 * a.msg_bytes;    // message words or message positions per (key, image) pair
-    int T = 1;
-    if (!sg) {
-        T = a.B > 16 ? 64 : a.B > 4 ? 16 : a.B > 1 ? 4 : 1;
-        while (T > 1 && (uint32_t)T * (rowpad + 128u) > KS_LDS / 2) T >>= 2;
-    }
-    int G = 1;
-    while (G < 64 && G < units) G <<= 1;
-    while (KS_WG / G < T) G >>= 1;
-    s.srow = a.nblk * 16;
-    if (!sg && G < 32)
-        while (s.srow % 32 != G) ++s.srow;                          // groups of one 32-lane half read different banks
-    const uint32_t sign_bytes = sg ? 0u : (uint32_t)T * (uint32_t)s.srow * 4u;
-    int64_t kpi = KS_WG / G / T;
-    kpi = std::min<int64_t>(kpi, (KS_LDS - sign_bytes) / rowpad);
-    kpi = std::min<int64_t>(kpi, a.U);
-    s.T = T; s.G = G; s.kpi = (int)kpi;
-    a.grid_x = (int)std::min<int64_t>((a.U + kpi - 1) / kpi, key_search_grid_cap(a.U));
-    return std::max<uint32_t>(sign_bytes + (uint32_t)kpi * rowpad, (uint32_t)(KS_WG / G * TR_LIST * sizeof(int64_t)));
-}
-
-template <int PL, bool SG>
-int launch_key_search(const KeySearchArgs& s, uint32_t lds, hipStream_t st) {
-    const KeyedArgs& a = s.base;
-    GSW_HIP(allow_dynamic_lds((const void*)gsw_key_search_scan_kernel<PL, SG>, lds));
-    hipLaunchKernelGGL((gsw_key_search_scan_kernel<PL, SG>), dim3(a.grid_x, (a.B + s.T - 1) / s.T), dim3(KS_WG), lds, st, s);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
-}
-
 template <bool SG>
-int launch_key_search_planes(const KeySearchArgs& s, int planes, uint32_t lds, hipStream_t st) {
-    switch (planes) {
-        case 0: return launch_key_search<0, SG>(s, lds, st);
-        case 4: return launch_key_search<4, SG>(s, lds, st);
-        case 8: return launch_key_search<8, SG>(s, lds, st);
-        case 12: return launch_key_search<12, SG>(s, lds, st);
-        default: return launch_key_search<16, SG>(s, lds, st);
+int launch_key_search_planes(const KeySearchArgs& s, const SearchPlan& p, hipStream_t st) {
+    switch (p.planes) {
+        case 0: return launch_search(gsw_key_search_scan_kernel<0, SG>, s, s.base, p, st);
+        case 4: return launch_search(gsw_key_search_scan_kernel<4, SG>, s, s.base, p, st);
+        case 8: return launch_search(gsw_key_search_scan_kernel<8, SG>, s, s.base, p, st);
+        case 12: return launch_search(gsw_key_search_scan_kernel<12, SG>, s, s.base, p, st);
+        default: return launch_search(gsw_key_search_scan_kernel<16, SG>, s, s.base, p, st);
     }
 }
 
@@ -240,43 +200,17 @@ int launch_key_search_planes(const KeySearchArgs& s, int planes, uint32_t lds, h
 extern "C" {
 
 size_t gsw_key_search_workspace_bytes(int B, int64_t n_keys, int k) {
-    if (B < 1 || n_keys < 1 || n_keys > (int64_t)INT32_MAX || k < 1 || k > TR_LIST) return 0;
-    return (size_t)B * (size_t)key_search_grid_cap(n_keys) * (size_t)k * sizeof(int64_t);
+    return search_workspace_bytes(SEARCH_KEY, B, n_keys, k);
 }
 
 int gsw_key_search_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* keys_dev, int64_t key_stride, int msg_bytes, int64_t n_keys,
                         int k, int32_t* idx_dev, int32_t* stat_dev, void* workspace_dev, void* stream) {
-    if (!signs_dev || !keys_dev || !idx_dev || !stat_dev || !workspace_dev) return GSW_ERR_BAD_ARG;
-    if (B < 1 || k < 1 || k > TR_LIST || n_bits < 1 || n_keys < 1 || n_keys > (int64_t)INT32_MAX) return GSW_ERR_BAD_ARG;
-    if (msg_bytes < 1 || msg_bytes > GSW_MSG_INLINE_MAX) return GSW_ERR_BAD_ARG;
-    if (key_stride < (int64_t)GSW_REC_HEAD || key_stride % 16 || ((uintptr_t)keys_dev & 15u)) return GSW_ERR_BAD_ARG;
-    if (n_bits % (8 * (int64_t)msg_bytes)) return GSW_ERR_RAGGED;
-    if (n_bits > GSW_ROW_MAX_BITS || B > 65535) return GSW_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    KeySearchArgs s;
-    KeyedArgs& a = s.base;
-    a.signs = signs_dev;
-    a.records = keys_dev;
-    a.partial = (int64_t*)workspace_dev;
-    a.idx = idx_dev;
-    a.score = stat_dev;
-    a.stride = key_stride;
-    a.U = n_keys;
-    a.B = B; a.k = k; a.n_bits = (int)n_bits;
-    a.rowbytes = (int)(n_bits / 8);
-    a.nblk = (a.rowbytes + 63) / 64;
-    a.msg_bytes = msg_bytes;
-    a.signs_aligned = (a.rowbytes % 4 == 0) && ((uintptr_t)signs_dev % 4 == 0);
-    s.copies = (int)(n_bits / (8 * (int64_t)msg_bytes));
-    const bool sg = 2u * ((uint32_t)a.nblk * 64u + 128u) > KS_LDS;  // a (padded) row and one keystream of it do not fit together
-    const bool fast = msg_bytes % 4 == 0 && (!sg || a.signs_aligned);   // (from global memory the words are read in place)
-    const int planes = !fast ? 0 : s.copies < 16 ? 4 : s.copies < 256 ? 8 : s.copies < 4096 ? 12 : 16;
-    const uint32_t lds = key_search_plan(s, fast, sg);
-    const int rc = sg ? launch_key_search_planes<true>(s, planes, lds, st) : launch_key_search_planes<false>(s, planes, lds, st);
-    if (rc != GSW_OK) return rc;
-    hipLaunchKernelGGL(gsw_trace_keyed_finish_kernel, dim3(B), dim3(64), 0, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
+    const SearchQuery q = search_query(SEARCH_KEY, signs_dev, nullptr, nullptr, keys_dev, idx_dev && stat_dev && workspace_dev, B, n_bits, key_stride, msg_bytes,
+                                       n_keys, k, 0);
+    const SearchPlan p = search_decide(q);
+    if (p.status != GSW_OK) return p.status;
+    const KeySearchArgs s{keyed_args(q, p, signs_dev, keys_dev, workspace_dev, idx_dev, stat_dev), p.T, p.G, p.kpi, p.srow, p.copies};
+    return p.sg ? launch_key_search_planes<true>(s, p, (hipStream_t)stream) : launch_key_search_planes<false>(s, p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,11 +1,9 @@
 // gswm_record.h -- "an image under its own record", the decisions every kernel family of that kind shares (gswm_codec_keyed.inc,
 // gswm_codec_soft.inc, gswm_keyed.hip, gswm_tamper.hip): the record layout and its operand check, the message repeated over a row, the
 // record's keystream in LDS, and the tail of a per-image vote.  The block function and the counter rule are gswm_chacha.h's.
-// Include after <hip/hip_runtime.h> and include/gswm.h.
+// Include after <hip/hip_runtime.h> and include/gswm.h.  A host compiler (gswm_search_plan.h's table program) sees the layout and the operand check only.
 #pragma once
 #include <stdint.h>
-
-#include "gswm_chacha.h"
 
 // A record is key[32] | nonce16[16] | message[msg_bytes]: uint8 rows, 16-byte aligned, at a stride that is a multiple of 16.
 constexpr int GSW_REC_HEAD = 48;                     // key[32] | nonce16[16]
@@ -13,19 +11,24 @@ constexpr int GSW_REC_HEAD = 48;                     // key[32] | nonce16[16]
 // 1 048 576 bits are 128 KiB of the CU's 160.
 constexpr int64_t GSW_ROW_MAX_BITS = 1048576;
 
-// what every entry point asks of its records
-static inline int records_check(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records) {
-    if (!records_dev || n_records < 1) return GSW_ERR_BAD_ARG;
+// what every entry point asks of its records; the pointer as two facts (gswm_search_plan.h decides without pointers)
+static inline int records_layout_check(bool present, bool aligned16, int64_t record_stride, int msg_bytes, int64_t n_records) {
+    if (!present || n_records < 1) return GSW_ERR_BAD_ARG;
     if (msg_bytes < 1 || msg_bytes > GSW_MSG_INLINE_MAX) return GSW_ERR_BAD_ARG;
     if (record_stride < (int64_t)GSW_REC_HEAD + msg_bytes || record_stride % 16) return GSW_ERR_BAD_ARG;
-    if ((uintptr_t)records_dev & 15u) return GSW_ERR_BAD_ARG;
-    return GSW_OK;
+    return aligned16 ? GSW_OK : GSW_ERR_BAD_ARG;
+}
+static inline int records_check(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records) {
+    return records_layout_check(records_dev != nullptr, ((uintptr_t)records_dev & 15u) == 0, record_stride, msg_bytes, n_records);
 }
 // ... of the entry points that keep the stride in 32 bits
 static inline int records_check32(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records) {
     if (record_stride > (int64_t)0x7FFFFFF0) return GSW_ERR_BAD_ARG;
     return records_check(records_dev, record_stride, msg_bytes, n_records);
 }
+
+#ifdef __HIPCC__      // device code from here on
+#include "gswm_chacha.h"
 
 // The message repeated over the row: the four bytes at offset o, o + 1, .. (mod msg_bytes, o < msg_bytes) as a little-endian word.
 // `dword`: msg_bytes % 4 == 0, o % 4 == 0 and the message is 4-byte aligned -- one load.  Otherwise byte by byte, wrapping by compare;
@@ -93,3 +96,4 @@ __device__ __forceinline__ void store_matches_flags(const uint32_t* s_match, con
         }
     }
 }
+#endif  // __HIPCC__

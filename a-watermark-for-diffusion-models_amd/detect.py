@@ -310,8 +310,7 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
     l: cipher bits per lattice element the images were embedded with; the rows then hold n l bits.  Raises IndexError where
     `extract_batch` does (n l is not a multiple of message_length)."""
     import torch
-    if not 0.0 < float(fpr) <= 1.0:
-        raise ValueError("fpr must be in (0, 1]")
+    limit = T._log10_fpr(fpr)
     mb = _message_bytes(message_length)
     M = 8 * mb
     l = codec.check_window(l)
@@ -330,23 +329,11 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
     rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
     rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
     bits, _, _ = codec.extract_records(z, rows, mb, l=l)
-    pairs = torch.stack([idx, stat]).cpu().numpy()                 # the B k (index, stat) pairs in one copy
-    idx_h, stat_h = pairs[0], pairs[1]
-    flags_h, bits_h = flags.cpu().numpy(), bits.cpu().numpy()
-    K, limit = len(keyring), math.log10(float(fpr))
-    out: List[DetectResult] = []
-    for b in range(B):
-        res = DetectResult(flags=int(flags_h[b]))
-        for j in range(k):
-            i, s = int(idx_h[b, j]), int(stat_h[b, j])
-            if i < 0:
-                break
-            res.candidates.append(KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), K)))
-        if res.candidates and res.candidates[0].log10_p_any <= limit:
-            res.key_id = res.candidates[0].key_id
-            res.message = bits_h[b].tobytes()
-        out.append(res)
-    return out
+    idx_h, stat_h = T._pairs_to_host(idx, stat)
+    flags_h, bits_h, K = flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
+    return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), K)),
+                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
+                              refuse=False)
 
 
 # ===================================================================================================================== front end

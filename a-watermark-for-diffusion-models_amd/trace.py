@@ -587,6 +587,58 @@ def _attach_tamper_maps(out, z, packed, records, M: int, l: int, tile: int, fpr:
         out[b].tamper = TM.make_map(agree[b], n_t, tile, fpr, "registry")
 
 
+def _log10_fpr(fpr) -> float:
+    """log10 of a false-positive rate in (0, 1], or ValueError"""
+    if not 0.0 < float(fpr) <= 1.0:
+        raise ValueError("fpr must be in (0, 1]")
+    return math.log10(float(fpr))
+
+
+def _pairs_to_host(idx, score):
+    """(idx, score) [B, k] of a search on the device -> the two host arrays: the B k pairs in one copy"""
+    import torch
+    pairs = torch.stack([idx, score]).cpu().numpy()
+    return pairs[0], pairs[1]
+
+
+def _flag_error(flags: int) -> Optional[ValueError]:
+    """The ValueError the reference raises for an image with these GSW_FLAG_* (a NaN / saturated latent, extract.py:84-86), or None"""
+    from . import _native as N
+    if flags & N.GSW_FLAG_NAN:
+        return ValueError("cannot convert float NaN to integer")
+    if flags & N.GSW_FLAG_SATURATED:
+        return ValueError("invalid literal for int() with base 2")
+
+
+def _candidate_lists(idx_h, score_h, flags_h, limit: float, candidate, result, refuse: bool = True) -> list:
+    """One result per image from the host pairs of a search: result(b, candidates, attributed) with candidate(b, j, index, score) for every entry before
+    the list's end (index -1), best first; the attribution rule: the best candidate's bound is <= limit.  refuse: a flagged image gets the reference's
+    ValueError instead of a result (`detect_latents` reports the flags and goes on)."""
+    out = []
+    for b in range(idx_h.shape[0]):
+        err = _flag_error(int(flags_h[b])) if refuse else None
+        if err is not None:
+            out.append(err)
+            continue
+        found = []
+        for j in range(idx_h.shape[1]):
+            i = int(idx_h[b, j])
+            if i < 0:
+                break
+            found.append(candidate(b, j, i, int(score_h[b, j])))
+        out.append(result(b, found, bool(found) and found[0].log10_p_any <= limit))
+    return out
+
+
+def _trace_result(b, candidates, attributed):
+    return TraceResult(candidates, candidates[0].user_id if attributed else None)
+
+
+def _best_records(out, record_at) -> list:
+    """`_attach_tamper_maps`' records: record_at(index of the best candidate) of every attributed image, None for the others"""
+    return [record_at(r.candidates[0].index) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
+
+
 def reliability_counts(score, levels: int, copies: int):
     """The (counts', copies') that make `codec.trace_topk`'s soft weight 2 c' - copies' equal to 2 score[b, t], the level-weighted vote of
     `codec.extract_soft`: c' = score + levels copies (0 <= c' <= copies'), copies' = 2 levels copies.  Works on tensors and arrays; raises
@@ -614,9 +666,7 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
     `reliability_counts`), `Candidate.agree` counts the soft vote's bits and the p-value is the Hoeffding bound `soft.log10_p` with the
     image's wsq -- a bound, not the exact binomial tail of the margin statistic.  Not with soft=False, l = 1 only."""
     import torch
-    from . import _native as N
-    if not 0.0 < float(fpr) <= 1.0:
-        raise ValueError("fpr must be in (0, 1]")
+    limit = _log10_fpr(fpr)
     l = codec.check_window(l)
     if reliability is not None:
         if not soft:
@@ -642,34 +692,17 @@ def trace_latents(latents, key: bytes, nonce: bytes, registry: Registry, *, mess
         idx, score = codec.trace_topk(counts, copies, reg_dev, k=k, soft=True)
         score = torch.where(idx >= 0, score // 2, score)                 # the search weighs 2 score[b, t]: every score is even
         wsq_h = vote.wsq.cpu().numpy()
-    pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy; flags and voted bits are the vote's own outputs
-    idx_h, score_h = pairs[0], pairs[1]
-    flags_h, bits_h = flags.cpu().numpy(), bits.cpu().numpy()
-    U, limit = len(registry), math.log10(float(fpr))
-    out: List[Union[TraceResult, ValueError]] = []
-    for b in range(B):
-        if flags_h[b] & N.GSW_FLAG_NAN:
-            out.append(ValueError("cannot convert float NaN to integer"))
-            continue
-        if flags_h[b] & N.GSW_FLAG_SATURATED:
-            out.append(ValueError("invalid literal for int() with base 2"))
-            continue
-        res = TraceResult()
-        for j in range(k):
-            i, s = int(idx_h[b, j]), int(score_h[b, j])
-            if i < 0:
-                break
-            agree = M - int(np.unpackbits(bits_h[b] ^ rows[i]).sum())
-            if wsq_h is not None:
-                lp = S.log10_p(s, int(wsq_h[b]))
-            else:
-                lp = log10_p_soft(s, M * V) if soft else log10_p_hard(agree, M, V)
-            res.candidates.append(Candidate(registry.user_at(i), i, s, agree, log10_p_any(lp, U)))
-        if res.candidates and res.candidates[0].log10_p_any <= limit:
-            res.attributed = res.candidates[0].user_id
-        out.append(res)
+    idx_h, score_h = _pairs_to_host(idx, score)          # flags and voted bits are the vote's own outputs
+    flags_h, bits_h, U = flags.cpu().numpy(), bits.cpu().numpy(), len(registry)
+
+    def candidate(b, j, i, s):
+        agree = M - int(np.unpackbits(bits_h[b] ^ rows[i]).sum())
+        lp = S.log10_p(s, int(wsq_h[b])) if wsq_h is not None else log10_p_soft(s, M * V) if soft else log10_p_hard(agree, M, V)
+        return Candidate(registry.user_at(i), i, s, agree, log10_p_any(lp, U))
+
+    out = _candidate_lists(idx_h, score_h, flags_h, limit, candidate, _trace_result)
     if tamper_tile is not None:
-        best = [(key, nonce, bytes(rows[r.candidates[0].index])) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
+        best = _best_records(out, lambda i: (key, nonce, bytes(rows[i])))
         if any(r is not None for r in best):
             _attach_tamper_maps(out, z, codec.quant_pack(z, l)[0], best, M, l, tamper_tile, fpr)
     return out
@@ -688,12 +721,10 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     tamper_tile: as in `trace_latents`; the map of an image is taken under its best candidate's OWN key (one launch more per batch).
     reliability: must be None -- the level-weighted search across keys is a search kernel of its own: `trace_latents_keyed_soft`."""
     import torch
-    from . import _native as N
     if reliability is not None:
         raise ValueError("reliability cannot be combined with trace_latents_keyed (--per_record_keys): the level-weighted search across keys "
                          "is trace_latents_keyed_soft (--keyed_reliability)")
-    if not 0.0 < float(fpr) <= 1.0:
-        raise ValueError("fpr must be in (0, 1]")
+    limit = _log10_fpr(fpr)
     z = latents.contiguous()
     B = z.shape[0]
     n = z.numel() // max(B, 1)
@@ -703,31 +734,17 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     rec_dev = registry.to_device(z.device)
     signs, flags = codec.quant_pack(z, l)
     idx, score = codec.trace_keyed_topk(signs, nb, rec_dev, registry.message_bytes, k=k)
-    pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy
-    idx_h, score_h = pairs[0], pairs[1]
-    flags_h = flags.cpu().numpy()
-    U, limit = len(registry), math.log10(float(fpr))
-    out: List[Union[TraceResult, ValueError]] = []
+    idx_h, score_h = _pairs_to_host(idx, score)
+    flags_h, U = flags.cpu().numpy(), len(registry)
     reported: Dict[Tuple[bytes, bytes], Dict[bytes, List[Tuple[int, Candidate]]]] = {}      # (key, nonce) -> message -> (image, candidate)
-    for b in range(B):
-        if flags_h[b] & N.GSW_FLAG_NAN:
-            out.append(ValueError("cannot convert float NaN to integer"))
-            continue
-        if flags_h[b] & N.GSW_FLAG_SATURATED:
-            out.append(ValueError("invalid literal for int() with base 2"))
-            continue
-        res = TraceResult()
-        for j in range(k):
-            i, s = int(idx_h[b, j]), int(score_h[b, j])
-            if i < 0:
-                break
-            c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(log10_p_soft(s, nb), U))
-            key, nonce, msg = registry.record_at(i)
-            reported.setdefault((key, nonce), {}).setdefault(msg, []).append((b, c))
-            res.candidates.append(c)
-        if res.candidates and res.candidates[0].log10_p_any <= limit:
-            res.attributed = res.candidates[0].user_id
-        out.append(res)
+
+    def candidate(b, j, i, s):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(log10_p_soft(s, nb), U))
+        key, nonce, msg = registry.record_at(i)
+        reported.setdefault((key, nonce), {}).setdefault(msg, []).append((b, c))
+        return c
+
+    out = _candidate_lists(idx_h, score_h, flags_h, limit, candidate, _trace_result)
     for (key, nonce), by_message in reported.items():
         images = sorted({b for pairs_ in by_message.values() for b, _ in pairs_})
         row = {b: r for r, b in enumerate(images)}
@@ -737,8 +754,7 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
             for b, c in pairs_:
                 c.agree = int(agree[row[b]])
     if tamper_tile is not None:
-        best = [registry.record_at(r.candidates[0].index) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
-        _attach_tamper_maps(out, z, signs, best, M, l, tamper_tile, fpr)
+        _attach_tamper_maps(out, z, signs, _best_records(out, registry.record_at), M, l, tamper_tile, fpr)
     return out
 
 
@@ -756,10 +772,8 @@ def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 
     the candidate's own record: one `codec.extract_soft` launch over the reported (image, candidate) pairs.
     tamper_tile: as in `trace_latents_keyed`, on the packed sign row.  n (1 + P) may not exceed 1 048 576, P the bit length of `levels`."""
     import torch
-    from . import _native as N
     from . import soft as S
-    if not 0.0 < float(fpr) <= 1.0:
-        raise ValueError("fpr must be in (0, 1]")
+    limit = _log10_fpr(fpr)
     z = latents.contiguous()
     B = z.shape[0]
     n = z.numel() // max(B, 1)
@@ -772,30 +786,16 @@ def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 
     rec_dev = registry.to_device(z.device)
     rows = codec.level_pack(z, thr)
     idx, score = codec.trace_keyed_soft_topk(rows, n, rec_dev, mb, k=k)
-    pairs = torch.stack([idx, score]).cpu().numpy()     # the B k (index, score) pairs in one copy
-    idx_h, score_h = pairs[0], pairs[1]
-    flags_h, wsq_h = rows.flags.cpu().numpy(), rows.wsq.cpu().numpy()
-    U, limit = len(registry), math.log10(float(fpr))
-    out: List[Union[TraceResult, ValueError]] = []
+    idx_h, score_h = _pairs_to_host(idx, score)
+    flags_h, wsq_h, U = rows.flags.cpu().numpy(), rows.wsq.cpu().numpy(), len(registry)
     reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
-    for b in range(B):
-        if flags_h[b] & N.GSW_FLAG_NAN:
-            out.append(ValueError("cannot convert float NaN to integer"))
-            continue
-        if flags_h[b] & N.GSW_FLAG_SATURATED:
-            out.append(ValueError("invalid literal for int() with base 2"))
-            continue
-        res = TraceResult()
-        for j in range(k):
-            i, s = int(idx_h[b, j]), int(score_h[b, j])
-            if i < 0:
-                break
-            c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U))
-            reported.append((b, c))
-            res.candidates.append(c)
-        if res.candidates and res.candidates[0].log10_p_any <= limit:
-            res.attributed = res.candidates[0].user_id
-        out.append(res)
+
+    def candidate(b, j, i, s):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U))
+        reported.append((b, c))
+        return c
+
+    out = _candidate_lists(idx_h, score_h, flags_h, limit, candidate, _trace_result)
     if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
         img = torch.tensor([b for b, _ in reported], device=z.device)
         rec = torch.tensor([c.index for _, c in reported], device=z.device)
@@ -803,8 +803,7 @@ def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 
         for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
             c.agree = int(a)
     if tamper_tile is not None:
-        best = [registry.record_at(r.candidates[0].index) if isinstance(r, TraceResult) and r.attributed is not None else None for r in out]
-        _attach_tamper_maps(out, z, rows.signs, best, M, 1, tamper_tile, fpr)
+        _attach_tamper_maps(out, z, rows.signs, _best_records(out, registry.record_at), M, 1, tamper_tile, fpr)
     return out
 
 

@@ -69,7 +69,11 @@ CASES = [(144, 3, 1, 1, 1, 48), (144, 6, 3, 5, 3, 64), (144, 18, 17, 64, 8, 80),
          (1024, 16, 70, 64, 8, 48), (1024, 128, 17, 5, 1, 64), (16384, 32, 17, 257, 3, 48), (16384, 32, 70, 5, 8, 80), (16384, 256, 3, 64, 8, 80),
          # beyond the issue's list: 4096 and more copies (16 counter planes); the largest lattice whose row shares the LDS with a keystream; rows
          # read from global memory, both counting paths
-         (131072, 4, 1, 3, 1, 48), (523264, 4, 2, 2, 3, 64), (1048576, 32, 2, 3, 3, 48), (1044480, 255, 1, 2, 2, 48)]
+         (131072, 4, 1, 3, 1, 48), (523264, 4, 2, 2, 3, 64), (1048576, 32, 2, 3, 3, 48), (1044480, 255, 1, 2, 2, 48),
+         # the plan classes of csrc/gswm_search_plan.h the cases above do not launch: 16, 256 and 4095 copies of a 4-byte message (8 and 12 counter planes, at
+         # their first and last count); the first lattice past 523 264 bits (rows read from global memory, the word path); a tile of 16 images on the bit-by-bit
+         # path with a partial block (504 = 21 x 24 bits) and k past the keys; one key per step with grid_x at its cap of 512
+         (512, 4, 2, 9, 8, 48), (8192, 4, 5, 9, 3, 64), (131040, 4, 1, 5, 8, 48), (523296, 4, 1, 2, 1, 48), (504, 3, 5, 5, 8, 48), (4096, 256, 3, 600, 1, 48)]
 
 
 @pytest.mark.parametrize("n_bits,mb,B,K,k,stride", CASES)
@@ -125,7 +129,7 @@ def test_unaligned_sign_rows_through_the_c_abi(G):
     from gswm_amd import _native as N
     lib = N.lib()
     rng = np.random.default_rng(5)
-    for n_bits, mb in ((576, 8), (144, 3)):
+    for n_bits, mb in ((576, 8), (144, 3), (523296, 4)):        # (the last: rows read in place from global memory lose the word path to the misalignment)
         B, K, k = 5, 9, 4
         pairs = _pairs(rng, K)
         signs = rng.integers(0, 256, (B, n_bits // 8), dtype=np.uint8)

@@ -131,6 +131,9 @@ CASES = [(1, 8, 1, 1, 1), (2, 256, 32, 3, 4), (63, 520, 5, 64, 8), (64, 16384, 3
          (4097, 256, 8, 64, 1), (2 ** 17 + 3, 520, 5, 3, 4), (2 ** 17 + 3, 8, 1, 130, 8), (1000, 16384, 128, 64, 4), (4097, 256, 32, 130, 8),
          (65, 65536, 32, 64, 1), (63, 36864, 8, 130, 4), (2, 262144, 256, 3, 1), (1000, 256, 1, 1, 8), (64, 16384, 8, 4, 8), (2 ** 17 + 3, 256, 32, 64, 1),
          (5, 1048576, 32, 2, 4)]
+# every tile (1, 4, 16, 64 images: B = 1, 2, 5, 17) x message form (dwords at 4 bytes, byte by byte at 3) of csrc/gswm_search_plan.h at the smallest lattice that has
+# them (one ChaCha block, whole at 512 bits, partial at 504 = 21 x 24: 512 is no multiple of 24); 9 records: one wave takes a second record; 5 with k = 8: an empty tail
+CASES += [(9 if B in (1, 5) else 5, 512 if mb == 4 else 504, mb, B, 3 if B in (1, 5) else 8) for B in (1, 2, 5, 17) for mb in (4, 3)]
 
 
 @pytest.mark.parametrize("U,n,msg_bytes,B,k", CASES)

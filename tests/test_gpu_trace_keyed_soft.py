@@ -127,6 +127,10 @@ def _device_rows(codec, signs, planes, wsum):
 # U x n x msg_bytes x B x k x levels
 CASES = [(1, 8, 1, 1, 1, 1), (2, 256, 32, 3, 4, 3), (63, 520, 5, 64, 8, 15), (64, 16384, 32, 130, 1, 15), (65, 36864, 128, 1, 4, 7), (4097, 256, 8, 64, 1, 2),
          (1000, 65536, 256, 3, 8, 15), (2 ** 17 + 3, 520, 5, 3, 4, 8), (5, 196608, 32, 2, 4, 15), (5, 524288, 32, 2, 4, 1)]
+# every plane count (levels 1, 3, 7, 15) x tile (B = 1, 2, 5, 17) of csrc/gswm_search_plan.h at the smallest lattice, the message form alternating (dwords at
+# 512 bits of 4-byte messages, byte by byte at 504 bits of 3-byte ones); 9 records: one wave takes a second record; 5 with k = 8: an empty tail
+CASES += [(9 if (i + j) % 2 else 5, 512 if (i + j) % 2 else 504, 4 if (i + j) % 2 else 3, B, 3 if (i + j) % 2 else 8, levels)
+          for i, levels in enumerate((1, 3, 7, 15)) for j, B in enumerate((1, 2, 5, 17))]
 
 
 @pytest.mark.parametrize("U,n,msg_bytes,B,k,levels", CASES)
