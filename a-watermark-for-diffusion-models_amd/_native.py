@@ -153,6 +153,7 @@ _PROTOTYPES = {
                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsw_key_search_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "gsw_key_search_topk": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsw_rows_align": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -438,6 +438,85 @@ def key_search_topk(signs: torch.Tensor, n_bits: int, keys: torch.Tensor, msg_by
     return idx, stat
 
 
+# ------------------------------------------------------------------------------------------------ alignment search (flips, quarter turns, lattice shifts)
+def align_table(aligns, shape: Sequence[int]) -> np.ndarray:
+    """A list of alignments (d, dy, dx) for a [C, H, W] lattice as the int32 [A, 3] host table `rows_align` uploads, or ValueError: the list is
+    empty or not [A, 3] integers, a d is outside 0..7, or an odd d (an odd number of quarter turns) meets H != W."""
+    C_, H, W = _lattice_shape(shape)
+    if isinstance(aligns, torch.Tensor):
+        if aligns.dtype != torch.int32:
+            raise ValueError(f"aligns must be an int32 [A, 3] tensor, got {aligns.dtype}")
+        t = aligns.detach().cpu().numpy()
+    else:
+        try:
+            t = np.asarray(list(aligns), dtype=np.int64)
+        except (TypeError, ValueError):
+            raise ValueError("aligns must be a list of (d, dy, dx) integer triples") from None
+    if t.ndim != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"aligns must hold at least one (d, dy, dx) row, got shape {tuple(t.shape)}")
+    if np.abs(t).max() >= 2 ** 31:
+        raise ValueError("aligns does not fit int32")
+    d = t[:, 0]
+    if ((d < 0) | (d > 7)).any():
+        raise ValueError(f"alignment d must be in 0..7, got {int(d[(d < 0) | (d > 7)][0])}")
+    if H != W and (d & 1).any():
+        raise ValueError(f"an odd d (a quarter turn) needs a square lattice, got H = {H}, W = {W}")
+    return np.ascontiguousarray(t, dtype=np.int32)
+
+
+def _lattice_shape(shape) -> Tuple[int, int, int]:
+    try:
+        C_, H, W = (int(s) for s in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"shape must be (C, H, W), got {shape!r}") from None
+    if C_ < 1 or H < 1 or W < 1:
+        raise ValueError(f"shape must be positive (C, H, W), got {shape!r}")
+    return C_, H, W
+
+
+def _rows_align_launch(packed: torch.Tensor, shape: Tuple[int, int, int], l: int, aligns_dev: torch.Tensor) -> torch.Tensor:
+    """`rows_align` after its checks: packed uint8 [B, rowbytes] and an `align_table` on packed's device"""
+    B, rowbytes = packed.shape
+    A = aligns_dev.shape[0]
+    out = torch.empty((B, A, rowbytes), dtype=torch.uint8, device=packed.device)
+    with torch.cuda.device(packed.device):
+        N.check(N.lib().gsw_rows_align(packed.data_ptr(), B, shape[0], shape[1], shape[2], l, aligns_dev.data_ptr(), A, out.data_ptr(), _stream_ptr()))
+    return out
+
+
+def rows_align(packed: torch.Tensor, shape: Sequence[int], l: int, aligns) -> torch.Tensor:
+    """Every candidate alignment of packed quantised rows, in one launch: uint8 [B, A, rowbytes].
+
+    packed: uint8 [B, C H W l / 8] (`sign_pack` / `quant_pack` of latents [B, C, H, W]); shape = (C, H, W); aligns: int32 [A, 3] rows
+    (d, dy, dx) on packed's device, or a list of such triples that is uploaded here (`align.alignments`).  Row (b, a) of the result is
+    bit for bit `quant_pack(align.apply(z[b], aligns[a]), l)`: the l-bit groups of the row are permuted (gsw_rows_align), nothing is
+    quantised again, so every row is an operand of `key_search_topk`.  ValueError for a host tensor, a ragged lattice (C H W l is not a
+    multiple of 8), more than 1 048 576 bits, l outside (1, 2, 4), an empty list, a d outside 0..7 and an odd d with H != W -- all before any
+    launch.  A device list is copied to the host for that check; `align.search_keys` checks its list once for all its launches."""
+    l = check_window(l)
+    shape = _lattice_shape(shape)
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise ValueError(f"packed must live on a HIP device (got {getattr(packed, 'device', type(packed).__name__)}); rows_align has no CPU path")
+    _need_gpu(packed, "packed")
+    n_bits = shape[0] * shape[1] * shape[2] * l
+    if n_bits % 8:
+        raise ValueError(f"a lattice of {shape} at l = {l} holds {n_bits} bits: not whole bytes")
+    if n_bits > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {shape} at l = {l} holds {n_bits} bits, more than {ROW_MAX_BITS}")
+    if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[0] < 1 or packed.shape[1] * 8 != n_bits:
+        raise ValueError(f"packed must be uint8 [B, {n_bits // 8}] with B >= 1 for a lattice of {shape} at l = {l}, got {packed.dtype} {tuple(packed.shape)}")
+    table = align_table(aligns, shape)
+    if isinstance(aligns, torch.Tensor):
+        _need_gpu(aligns, "aligns")
+        _same_device(aligns, packed, "aligns")
+        if aligns.dim() != 2:
+            raise ValueError("aligns must be int32 [A, 3]")
+        aligns_dev = aligns
+    else:
+        aligns_dev = torch.from_numpy(table).to(packed.device)
+    return _rows_align_launch(packed, shape, l, aligns_dev)
+
+
 # ------------------------------------------------------------------------------------------------ issuing (one record per image)
 def _records_operand(records: torch.Tensor, msg_bytes: int) -> Tuple[int, int, int]:
     """The checks `embed_records` and `extract_records` share -> (B, stride, msg_bytes)"""

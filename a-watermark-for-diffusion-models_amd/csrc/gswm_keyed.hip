@@ -320,3 +320,4 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 
 #include "gswm_keyed_soft.inc"   // gsw_trace_keyed_soft_topk: the same search ranked by reliability-weighted margins
 #include "gswm_keysearch.inc"    // gsw_key_search_topk: every key of a keyring scored without a message
+#include "gswm_align.inc"        // gsw_rows_align: every candidate alignment of a packed row, the input of an alignment search

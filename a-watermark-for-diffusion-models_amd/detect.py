@@ -282,7 +282,8 @@ class KeyCandidate:
     key_id: str
     index: int
     stat: int
-    log10_p_any: float          # Bonferroni bound over the keyring
+    log10_p_any: float          # Bonferroni bound over the keyring (with `align`: over the keyring x the candidate alignments)
+    alignment: Optional[Tuple[int, int, int]] = None     # with `align`: this key's best alignment (d, dy, dx) of the image (`align.apply` undoes the attack)
 
 
 @dataclass
@@ -291,6 +292,7 @@ class DetectResult:
     key_id: Optional[str] = None        # the best candidate's key id if its bound is <= log10(fpr), else None: none of these keys
     message: Optional[bytes] = None     # the majority-voted message under that key (None when no key is named)
     flags: int = 0                      # GSW_FLAG_* of the image (a saturated or NaN latent: the reference refuses such an image)
+    alignment: Optional[Tuple[int, int, int]] = None     # with `align`: the named key's alignment, the one the message was read under (None when no key is named)
 
 
 def _message_bytes(message_length) -> int:
@@ -300,7 +302,7 @@ def _message_bytes(message_length) -> int:
     return m // 8
 
 
-def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1, fpr: float = 1e-6, l: int = 1) -> List[DetectResult]:
+def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1, fpr: float = 1e-6, l: int = 1, align=None) -> List[DetectResult]:
     """latents [B, ...] on the device -> one DetectResult per image: the k best keys of the keyring (best first) with their Bonferroni
     bounds, the key that is named at false-positive rate `fpr` per image over the whole keyring (or None) and the message voted under it.
 
@@ -308,8 +310,15 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
     keystream is generated inside it) and `codec.extract_records`, which votes every image under its own best key (its rows are that key
     and nonce with a zero message; `matches` is ignored).  The host receives the B k (index, stat) pairs, the flags and the voted bytes.
     l: cipher bits per lattice element the images were embedded with; the rows then hold n l bits.  Raises IndexError where
-    `extract_batch` does (n l is not a multiple of message_length)."""
+    `extract_batch` does (n l is not a multiple of message_length).
+
+    align: a list of candidate alignments (`align.alignments`) for images that may have been mirrored, turned by a quarter or shifted on the
+    lattice; latents must then be [B, C, H, W].  The candidates come from `align.search_keys` (one more launch, `codec.rows_align`, in front of
+    the search), the Bonferroni factor is K A, every candidate carries its best alignment, and each image is read after `align.apply` of
+    its best candidate's alignment.  None: exactly the path above."""
     import torch
+    if align is not None:
+        return _detect_latents_aligned(latents, keyring, message_length, k, fpr, l, align)
     limit = T._log10_fpr(fpr)
     mb = _message_bytes(message_length)
     M = 8 * mb
@@ -336,6 +345,40 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
                               refuse=False)
 
 
+def _detect_latents_aligned(latents, keyring: Keyring, message_length: int, k: int, fpr: float, l: int, aligns) -> List[DetectResult]:
+    """`detect_latents` with candidate alignments"""
+    import torch
+    from . import align as AL
+    limit = T._log10_fpr(fpr)
+    mb = _message_bytes(message_length)
+    M = 8 * mb
+    l = codec.check_window(l)
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    keyring.packed()                                               # (an empty keyring fails here)
+    if latents.dim() != 4:
+        raise ValueError(f"align needs latents [B, C, H, W], got {tuple(latents.shape)}")
+    z = latents.contiguous()
+    B = z.shape[0]
+    table = AL._as_list(aligns, z.shape[2], z.shape[3])
+    V = codec.vote_copies(z.numel() // max(B, 1), M, l)
+    keys_dev = keyring.to_device(z.device)
+    packed, flags = codec.quant_pack(z, l)
+    idx, aidx, stat = AL._search_packed(packed, z.shape[1:], l, keys_dev, mb, table, k)
+    host = torch.stack([idx, aidx, stat]).cpu().numpy()
+    idx_h, aidx_h, stat_h = host[0], host[1], host[2]
+    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
+    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
+    bits, _, _ = codec.extract_records(AL.unalign(z, table, aidx_h[:, 0]), rows, mb, l=l)
+    flags_h, bits_h, pairs = flags.cpu().numpy(), bits.cpu().numpy(), len(keyring) * len(table)
+    return T._candidate_lists(idx_h, stat_h, flags_h, limit,
+                              lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), pairs), table[int(aidx_h[b, j])]),
+                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b]),
+                                                               c[0].alignment if named else None),
+                              refuse=False)
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result) -> str:
     """One line of detect.txt / stdout"""
@@ -350,6 +393,9 @@ def format_line(name: str, result) -> str:
         text += f", next: {o.key_id} ({o.log10_p_any:.3f})"
     if result.flags:
         text += f", flags {result.flags}"
+    if c.alignment is not None:                                    # only a search with `align` sets it: the best candidate's, named or not
+        from . import align as AL
+        text += f", alignment: {AL.describe(c.alignment)}"
     return text
 
 
@@ -374,6 +420,10 @@ def build_parser():
     p.add_argument("--fpr", type=_fpr, default=1e-6, help="false-positive rate per image, over the whole keyring (Bonferroni), in (0, 1]")
     p.add_argument("--top", type=int, default=1, choices=range(1, 9), metavar="K", help="candidate keys reported per image (1..8)")
     p.add_argument("--l", type=int, default=1, choices=codec.WINDOWS, help="cipher bits per lattice element the images were embedded with")
+    p.add_argument("--align", default="none", choices=("none", "flips", "d4"),
+                   help="also try every alignment of the lattice in this group: flips (half turn and the two mirrors) or d4 (all eight orientations); "
+                        "the Bonferroni factor grows by the number of candidates")
+    p.add_argument("--align_shift", type=int, default=0, metavar="R", help="with --align: also every lattice shift in [-R, R]^2 (8 R pixels)")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -394,8 +444,14 @@ def load_keyring(path) -> Keyring:
 def _detect_files(files, args, keyring) -> list:
     """files -> outcomes in order (DetectResult or the exception that file raised): `trace`'s decode / invert / batch path with this
     module's search in place of the registry search"""
-    return T._trace_files(files, args, keyring,
-                          trace_batch=lambda latents: detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l))
+    def batch(latents):
+        cands = None
+        if getattr(args, "align", "none") != "none":
+            from . import align as AL
+            cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
+        return detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l, align=cands)
+
+    return T._trace_files(files, args, keyring, trace_batch=batch)
 
 
 def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
@@ -406,6 +462,8 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
         fields = [("Time", datetime.now().strftime("%Y-%m-%d %H:%M:%S")), ("keyring", args.keyring), ("keys", len(keyring)),
                   ("message_length", args.message_length), ("l", args.l), ("fpr", args.fpr),
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
+        if getattr(args, "align", "none") != "none":
+            fields += [("align", args.align), ("align_shift", args.align_shift)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
@@ -420,6 +478,8 @@ def main(argv=None):
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     from . import extract as X
     _message_bytes(args.message_length)                            # fails before any model loads
+    if args.align_shift < 0 or (args.align == "none" and args.align_shift):
+        raise SystemExit("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
     keyring = load_keyring(args.keyring)
     keyring.packed()
     synthetic = X._no_checkpoint(args.model_id)

@@ -51,6 +51,49 @@ def _soft_wanted(args, l: int) -> bool:
     return True
 
 
+class _AlignedBits(str):
+    """A recovered bit string that also says under which alignment of the lattice it was read (--align)"""
+    alignment = None
+    log10_p = 0.0
+
+
+def _align_wanted(args) -> bool:
+    """--align flips|d4 as a bool; the votes it does not exist for are refused by name"""
+    if getattr(args, "align", None) in (None, "none"):
+        return False
+    for flag in ("soft", "robust"):
+        if int(getattr(args, flag, 0) or 0):
+            raise ValueError(f"--align cannot be combined with --{flag} 1: the alignment search reads the reference's vote")
+    if getattr(args, "tamper_map", None):
+        raise ValueError("--align cannot be combined with --tamper_map")
+    return True
+
+
+def _vote_aligned(z, args, m: int, l: int):
+    """--align: `align.extract_aligned` under the run's key -> (one _AlignedBits or ValueError per image)"""
+    from . import align as AL
+    if z.dim() != 4:
+        raise ValueError(f"--align needs the latents as [B, C, h, w] (got {tuple(z.shape)})")
+    cands = AL.alignments(args.align, int(getattr(args, "align_shift", 0) or 0), z.shape[-2], z.shape[-1])
+    out = []
+    for r in AL.extract_aligned(z, args.key, args.nonce, m, cands, l=l):
+        if r.flags & N.GSW_FLAG_NAN:
+            out.append(ValueError("cannot convert float NaN to integer"))
+        elif r.flags & N.GSW_FLAG_SATURATED:
+            out.append(ValueError("invalid literal for int() with base 2"))
+        else:
+            s = _AlignedBits(codec.bits_to_str(r.bits)[:m])
+            s.alignment, s.log10_p = r.alignment, r.log10_p
+            out.append(s)
+    return out
+
+
+def _alignment_note(r) -> str:
+    """what --align adds to an image's line: the alignment it was read under and its bound over the candidates"""
+    from . import align as AL
+    return f", alignment: {AL.describe(r.alignment)}, log10 p, {r.log10_p:.3f}" if isinstance(r, _AlignedBits) else ""
+
+
 def _vote(z, args, m: int, l: int):
     """(bits, flags) of the reference's vote, with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations), with
     --soft 1 of the level-weighted vote (soft.extract_soft, thresholds scaled to each image's RMS)"""
@@ -84,6 +127,14 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     l = _window(args)
     z = _to_device_latents(reversed_latents, device)
     m = int(args.message_length)
+    if _align_wanted(args):                                  # the alignments act on the lattice: the search needs the image's [C, h, w]
+        shape = tuple(int(d) for d in np.shape(reversed_latents))
+        if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
+            raise ValueError(f"--align needs the latents of ONE image as [..., C, h, w] (got {shape})")
+        r = _vote_aligned(z.view(1, *shape[-3:]), args, m, l)[0]
+        if isinstance(r, Exception):
+            raise r
+        return r
     if int(getattr(args, "robust", 0) or 0):                 # the tiles are cut from the lattice: the weighted vote needs the image's [C, h, w]
         shape = tuple(int(d) for d in np.shape(reversed_latents))
         if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
@@ -103,6 +154,8 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
     Mirrors the per-image try/except of extract.py:148-155."""
     l = _window(args)
     m = int(args.message_length)
+    if _align_wanted(args):
+        return _vote_aligned(latents.contiguous(), args, m, l)
     bits, flags = _vote(latents.contiguous(), args, m, l)
     bits_h, flags_h = bits.cpu().numpy(), flags.cpu().numpy()
     out = []
@@ -369,7 +422,8 @@ def get_result_for_one_image(args):
         write_tamper_maps(reversed_latents, [args.single_image_path], args)
     extracted_message_bin = recover_exactracted_message(reversed_latents, args)
     original_message_bin, bit_accuracy = calculate_bit_accuracy(args.original_message_hex, extracted_message_bin)
-    print(f"{os.path.basename(args.single_image_path)}\nOriginal Message: {original_message_bin} \nExtracted Message: {extracted_message_bin}\nBit Accuracy: {bit_accuracy}\n")
+    print(f"{os.path.basename(args.single_image_path)}\nOriginal Message: {original_message_bin} \nExtracted Message: {extracted_message_bin}\n"
+          f"Bit Accuracy: {bit_accuracy}{_alignment_note(extracted_message_bin)}\n")
     return original_message_bin, extracted_message_bin, bit_accuracy
 
 
@@ -503,8 +557,8 @@ def _report(job, args, synthetic):
                 continue
             original_message_bin, bit_accuracy = calculate_bit_accuracy(args.original_message_hex, r)
             name = os.path.basename(f)
-            print(f"{name}\nOriginal Message: {original_message_bin} \nExtracted Message: {r}\nBit Accuracy: {bit_accuracy}\n")
-            out.write(f"{name}, Bit Accuracy, {bit_accuracy}\n")
+            print(f"{name}\nOriginal Message: {original_message_bin} \nExtracted Message: {r}\nBit Accuracy: {bit_accuracy}{_alignment_note(r)}\n")
+            out.write(f"{name}, Bit Accuracy, {bit_accuracy}{_alignment_note(r)}\n")
             accs.append(float(bit_accuracy))
         if accs:
             mean = sum(accs) / len(accs)
@@ -606,6 +660,10 @@ def build_parser():
                 self.error("--soft 1 cannot be combined with --robust 1: level weights and tile weights are separate votes")
             if a.soft and a.l != 1:
                 self.error(f"--soft 1 cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
+            if a.align != "none" and (a.soft or a.robust or a.tamper_map):
+                self.error("--align cannot be combined with --soft 1, --robust 1 or --tamper_map: the alignment search reads the reference's vote")
+            if a.align_shift < 0 or (a.align == "none" and a.align_shift):
+                self.error("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
             return a
 
     parser = Parser(description="Extract watermark from a image")
@@ -644,6 +702,10 @@ def build_parser():
     parser.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                         help="(not a reference flag) 1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning "
                              "(default: 1; 0 opts into the library kernels, counted and warned about once per reason)")
+    parser.add_argument("--align", default="none", choices=("none", "flips", "d4"),
+                        help="(not a reference flag) read the message under the best alignment of the lattice (align.extract_aligned): flips = half turn and "
+                             "the two mirrors, d4 = all eight orientations; none: the reference's vote as it is")
+    parser.add_argument("--align_shift", type=int, default=0, metavar="R", help="(not a reference flag) with --align: also every lattice shift in [-R, R]^2")
     return parser
 
 

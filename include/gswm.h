@@ -720,6 +720,24 @@ size_t gsw_key_search_workspace_bytes(int B, int64_t n_keys, int k);
 int gsw_key_search_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const uint8_t* keys_dev, int64_t key_stride, int msg_bytes, int64_t n_keys,
                         int k, int32_t* idx_dev, int32_t* stat_dev, void* workspace_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Alignment search: every candidate alignment of a packed quantised row, written in one launch; the rows are the
+ * operand of gsw_key_search_topk (or any search over packed rows).  Additive: gsw_version() stays 500.
+ *
+ *   rows_dev   : uint8 [B, C H W l / 8], the row gsw_sign_pack (l = 1) or gsw_quant_pack writes (any alignment): element e = (c H + y) W + x
+ *                owns bits [e l, e l + l), MSB first, byte j holds bits 8 j .. 8 j + 7
+ *   aligns_dev : int32 [A, 3] rows (d, dy, dx), 4-byte aligned.  The alignment acts on the [H, W] planes of the lattice: mirror the last axis if
+ *                d & 4, then d & 3 quarter turns counterclockwise (torch.rot90 over the last two axes), then a cyclic roll by (dy, dx) (any
+ *                integers, taken modulo H and W)
+ *   out_dev    : uint8 [B, A, C H W l / 8] (any alignment); row (b, a) is bit for bit what gsw_quant_pack writes for that transform of image
+ *                b's latent: the l-bit groups are permuted, no value is touched, so the result does not depend on the latent's dtype
+ * The list is device memory and is not read on the host: an entry with d outside 0..7, or an odd d when H != W, writes a row of zeros (the
+ * callers of this package refuse such a list before it is uploaded).  Every output byte is written, no atomics, no workspace, integer
+ * arithmetic only.  Rows of up to 65 536 bytes are staged in LDS once per workgroup, longer ones are read in place.
+ * GSW_ERR_BAD_ARG: null pointer, aligns_dev not 4-byte aligned, B, C, H, W or A < 1, l outside {1, 2, 4}.  GSW_ERR_UNSUPPORTED: C H W l >
+ * 1 048 576 bits, B > 65535.  GSW_ERR_RAGGED: C H W l is not a multiple of 8.  Every refusal happens before any launch. */
+int gsw_rows_align(const uint8_t* rows_dev, int B, int C, int H, int W, int l, const int32_t* aligns_dev, int A, uint8_t* out_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
