@@ -681,15 +681,8 @@ def level_pack(z: torch.Tensor, thresholds: torch.Tensor) -> LevelRows:
     return LevelRows(signs, planes, wsum, wsq, flags)
 
 
-def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
-    """`trace_keyed_topk` ranked by reliability-weighted margins: (idx int32 [B, k], score int32 [B, k]), best first, ties towards the lower
-    row; past the registry's end idx = -1 and score = INT32_MIN.
-
-    rows: `level_pack`'s result for the images (signs [B, n_bits / 8], planes [B, P, n_bits / 8], wsum [B]; the number of levels is taken
-    as 2**P - 1, which selects the same kernel as any `levels` with P planes), records: as `trace_keyed_topk`.
-    score = sum_j level_j (1 - 2 (sign_j ^ codeword_j)) = wsum - 2 sum_k 2**k popcount(plane_k & (signs ^ codeword)); for records that share
-    one key it is sum_t (2 r_t - 1) score[t] of `extract_soft`.  One search launch (gsw_trace_keyed_soft_topk); n_bits (1 + P) may not
-    exceed 1 048 576 (ValueError).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
+def _level_rows_checks(rows: "LevelRows", with_wsum: bool):
+    """(planes_check, wsum_check) of a `LevelRows` operand for `_search_operands`' extras"""
     signs, planes, wsum = rows.signs, rows.planes, rows.wsum
 
     def planes_check(B):
@@ -700,8 +693,20 @@ def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, m
         if wsum.dtype != torch.int32 or tuple(wsum.shape) != (B,):
             raise ValueError(f"rows.wsum must be int32 [{B}]")
 
-    B, U, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, records, msg_bytes, k, prefix="rows.",
-                                                          extras=((planes, "rows.planes", planes_check), (wsum, "rows.wsum", wsum_check)))
+    return ((planes, "rows.planes", planes_check),) + (((wsum, "rows.wsum", wsum_check),) if with_wsum else ())
+
+
+def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`trace_keyed_topk` ranked by reliability-weighted margins: (idx int32 [B, k], score int32 [B, k]), best first, ties towards the lower
+    row; past the registry's end idx = -1 and score = INT32_MIN.
+
+    rows: `level_pack`'s result for the images (signs [B, n_bits / 8], planes [B, P, n_bits / 8], wsum [B]; the number of levels is taken
+    as 2**P - 1, which selects the same kernel as any `levels` with P planes), records: as `trace_keyed_topk`.
+    score = sum_j level_j (1 - 2 (sign_j ^ codeword_j)) = wsum - 2 sum_k 2**k popcount(plane_k & (signs ^ codeword)); for records that share
+    one key it is sum_t (2 r_t - 1) score[t] of `extract_soft`.  One search launch (gsw_trace_keyed_soft_topk); n_bits (1 + P) may not
+    exceed 1 048 576 (ValueError).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
+    signs, planes, wsum = rows.signs, rows.planes, rows.wsum
+    B, U, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, records, msg_bytes, k, prefix="rows.", extras=_level_rows_checks(rows, True))
     P = planes.shape[1]
     if n_bits * (1 + P) > ROW_MAX_BITS:
         raise ValueError(f"a lattice of {n_bits} bits with {P} level planes is beyond the search's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
@@ -711,6 +716,30 @@ def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, m
         N.check(lib.gsw_trace_keyed_soft_topk(signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(), (1 << P) - 1, B, n_bits, records.data_ptr(), stride,
                                               msg_bytes, U, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))
     return idx, score
+
+
+# ------------------------------------------------------------------------------------------------ blind key search ranked by reliability levels
+def key_search_soft_topk(rows: LevelRows, n_bits: int, keys: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`key_search_topk` ranked by reliability levels: (idx int32 [B, k], stat int32 [B, k]), best first, ties towards the lower row; past
+    the keyring's end idx = -1 and stat = INT32_MIN.
+
+    rows: `level_pack`'s result for the images (signs [B, n_bits / 8], planes [B, P, n_bits / 8]; wsum is not read), keys: as
+    `key_search_topk`.  With d the image's signs decrypted under a key and w_j the element's level from the planes,
+    stat = sum_t |sum_{j mod 8 msg_bytes == t} w_j (2 d_j - 1)|: sum_t |score[t]| of `extract_soft` under that key, and with one plane of all
+    ones `key_search_topk`'s stat (`detect.log10_p_blind_soft` bounds its null tail).  One search launch (gsw_key_search_soft_topk);
+    n_bits (1 + P) may not exceed 1 048 576 (ValueError).  Raises IndexError when n_bits is not a multiple of 8 msg_bytes."""
+    signs, planes = rows.signs, rows.planes
+    B, K, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, keys, msg_bytes, k, rows_name="keys", rows_shape="[K, stride]", layout=_key_layout,
+                                                          prefix="rows.", extras=_level_rows_checks(rows, False))
+    P = planes.shape[1]
+    if n_bits * (1 + P) > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n_bits} bits with {P} level planes is beyond the search's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
+    lib = N.lib()
+    ws, idx, stat = _search_outputs(lib.gsw_key_search_soft_workspace_bytes, B, K, k, "keys", signs.device)
+    with torch.cuda.device(signs.device):
+        N.check(lib.gsw_key_search_soft_topk(signs.data_ptr(), planes.data_ptr(), P, B, n_bits, keys.data_ptr(), stride, msg_bytes, K, k,
+                                             idx.data_ptr(), stat.data_ptr(), ws.data_ptr(), _stream_ptr()))
+    return idx, stat
 
 
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)

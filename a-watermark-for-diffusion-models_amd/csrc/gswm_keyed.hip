@@ -43,6 +43,7 @@
 //   gsw_trace_keyed_finish_kernel        : per image: merge the partial lists, output.
 //   (gswm_keyed_soft.inc, included at the end: gsw_trace_keyed_soft_scan_kernel<T, MSG4, P>, the level-weighted search)
 //   (gswm_keysearch.inc, included after it: gsw_key_search_scan_kernel<PL, SG>, the blind key search)
+//   (gswm_keysearch_soft.inc, after that: gsw_key_search_soft_scan_kernel<CP, P, SG>, the blind key search ranked by reliability levels)
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -52,6 +53,7 @@
 #include "gswm_host.h"     // GSW_HIP, allow_dynamic_lds
 #include "gswm_record.h"   // the record: GSW_REC_HEAD, GSW_ROW_MAX_BITS (and gswm_chacha.h: CHACHA_QR, quad_perm)
 #include "gswm_search_plan.h"   // search_decide: every refusal and every launch decision of the three searches; KY_WAVES, KY_WG, KS_WG
+#include "gswm_keysearch_soft_plan.h"   // key_soft_decide: the same for the level-weighted key search
 #include "gswm_topk.h"
 
 namespace {
@@ -320,4 +322,5 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 
 #include "gswm_keyed_soft.inc"   // gsw_trace_keyed_soft_topk: the same search ranked by reliability-weighted margins
 #include "gswm_keysearch.inc"    // gsw_key_search_topk: every key of a keyring scored without a message
+#include "gswm_keysearch_soft.inc"   // gsw_key_search_soft_topk: the same search ranked by reliability levels
 #include "gswm_align.inc"        // gsw_rows_align: every candidate alignment of a packed row, the input of an alignment search

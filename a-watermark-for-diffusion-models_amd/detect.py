@@ -17,6 +17,10 @@ maximum of the registry score over all 2^M messages.
 Null model (the paper's, as in `trace`): an image that is independent of the key decrypts to fair coins.  Then the c_t are independent
 Bin(V, 1/2) and S is the sum of M independent copies of |2 Bin(V, 1/2) - V|: an exact law with no free parameter (`log10_p_blind`).
 Over a keyring of K keys the reported value is the Bonferroni bound `trace.log10_p_any`; a key is named iff that is <= log10(fpr).
+
+Reliability levels (`detect_latents(..., reliability=L)`, `--reliability L`; l = 1): element j votes with its level w_j in 0..L (`codec.level_pack`),
+X_t = sum_{j mod M == t} w_j (2 d_j - 1) and S = sum_t |X_t| (`codec.key_search_soft_topk`).  Given the levels the X_t of a key-independent image are
+independent weighted Rademacher sums: `log10_p_blind_soft` computes their exact pmfs and bounds the tail of S by Chernoff -- an upper bound, not the tail.
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ from typing import Dict, List, Optional, Tuple, Union
 import numpy as np
 
 from . import codec
+from . import soft as S
 from . import trace as T
 
 EXACT_MAX_BITS = 65536          # lattices up to here get the exact null tail, larger ones the Chernoff bound
@@ -148,6 +153,94 @@ def log10_p_blind(stat: int, M: int, V: int) -> float:
     if law is None:
         law = _LAWS[(M, V)] = _NullLaw(M, V)
     return law.log10_tail(stat)
+
+
+class _SoftNullLaw:
+    """The null law of the level-weighted statistic of ONE image, given its levels: the exact pmf of every |X_t| and the Chernoff bound of their sum.
+
+    levels [n] ints in 0..15, element j votes on message position j mod M.  Under a key the image is independent of, the decrypted bits are fair coins
+    independent of the levels, so X_t = sum_j w_j e_j (e_j = +-1) over the V copies of position t, independently over t.  With Y_t = sum_j w_j d_j
+    (d_j in {0, 1}) X_t = 2 Y_t - W_t, and the pmf of Y_t is the dynamic programme p <- (p + p shifted by w_j) / 2 over the copies, run for all M positions at
+    once on an [M, max W_t + 1] array: V steps.  Up to V = 1000 in probabilities (the smallest, 2^-V, is a normal float64 and every sum is of positive terms),
+    beyond that the same recursion in logarithms."""
+
+    LINEAR_MAX_COPIES = 1000
+
+    def __init__(self, levels, M: int):
+        lv = np.asarray(levels)
+        M = int(M)
+        if lv.ndim != 1 or lv.size < 1 or lv.dtype.kind not in "iu":
+            raise ValueError("levels must be a one-dimensional integer array")
+        if M < 1 or lv.size % M:
+            raise ValueError(f"{lv.size} levels are not whole copies of {M} message positions")
+        lv = lv.astype(np.int64)
+        if lv.min() < 0 or lv.max() > codec.SOFT_MAX_LEVELS:
+            raise ValueError(f"levels must be in 0..{codec.SOFT_MAX_LEVELS}")
+        w = lv.reshape(-1, M)                                        # [V, M]
+        self.M, self.V = M, w.shape[0]
+        self.W = w.sum(axis=0)                                       # [M]
+        self.total = int(self.W.sum())
+        size = int(self.W.max()) + 1
+        y = np.arange(size, dtype=np.int64)
+        linear = self.V <= self.LINEAR_MAX_COPIES
+        p = np.zeros((M, size)) if linear else np.full((M, size), -np.inf)
+        p[:, 0] = 1.0 if linear else 0.0
+        for i in range(self.V):
+            src = y[None, :] - w[i][:, None]
+            moved = np.take_along_axis(p, np.maximum(src, 0), axis=1)
+            if linear:
+                p = 0.5 * (p + np.where(src >= 0, moved, 0.0))
+            else:
+                p = np.logaddexp(p, np.where(src >= 0, moved, -np.inf)) - math.log(2.0)
+        with np.errstate(divide="ignore"):
+            self.lp = np.log(p) if linear else p                     # [M, size] log P[Y_t = y]; -inf past W_t and where no pattern lands
+        self.a = np.abs(2 * y[None, :] - self.W[:, None]).astype(np.float64)     # |X_t| at Y_t = y
+        rows = np.arange(M)
+        top = np.logaddexp(self.lp[rows, 0], self.lp[rows, self.W])   # P[|X_t| = W_t] = P[Y = 0] + P[Y = W_t]
+        self.log_top = float(np.where(self.W > 0, top, 0.0).sum())   # (W_t = 0: the position is 0 with certainty)
+        self.mean0 = self._tilted(0.0)[1]
+
+    def _tilted(self, theta: float) -> Tuple[float, float]:
+        """(sum_t log E e^(theta |X_t|), sum_t the mean of |X_t| under that tilt), log-sum-exp"""
+        x = self.lp + theta * self.a
+        top = x.max(axis=1)
+        e = np.exp(x - top[:, None])
+        z = e.sum(axis=1)
+        return float((top + np.log(z)).sum()), float(((e * self.a).sum(axis=1) / z).sum())
+
+    def log10_bound(self, s: int) -> float:
+        s = int(s)
+        if not 0 <= s <= self.total:
+            raise ValueError(f"stat {s} is outside 0..{self.total}")
+        if s <= self.mean0:
+            return 0.0
+        if s >= self.total:
+            return self.log_top / _LN10                              # theta -> infinity: every position at its extreme, the exact value at the top
+        lo, hi = 0.0, 1.0                                            # the tilted mean grows with theta from E[S] to sum W: bisection
+        while self._tilted(hi)[1] < s:
+            lo, hi = hi, 2.0 * hi
+        for _ in range(100):
+            mid = 0.5 * (lo + hi)
+            if mid <= lo or mid >= hi:
+                break
+            if self._tilted(mid)[1] < s:
+                lo = mid
+            else:
+                hi = mid
+        theta = 0.5 * (lo + hi)
+        return min(0.0, (self._tilted(theta)[0] - theta * s) / _LN10)
+
+
+def log10_p_blind_soft(stat: int, levels, M: int) -> float:
+    """An UPPER BOUND of log10 P[S >= stat] for the level-weighted blind statistic S = sum_t |X_t| (`codec.key_search_soft_topk`) of an image that is
+    independent of the key, given the image's levels: `levels` int [n] in 0..15, element j on message position j mod M.
+
+    Conditionally on the levels the X_t are independent weighted Rademacher sums; their pmfs are exact (integer dynamic programming, `_SoftNullLaw`), the
+    tail of their sum is bounded by Chernoff: min_theta [sum_t log E e^(theta |X_t|) - theta stat] / ln 10, in log-sum-exp.  0.0 at and below E[S]; at
+    stat = sum_t W_t the exact value prod_t P[|X_t| = W_t]; finite everywhere; ValueError outside 0 .. sum_t W_t.  It is a bound, NOT the tail: for unit
+    levels, where the exact tail is known (`log10_p_blind`), the same bound is 1.1 to 1.5 decades weaker than it at 4096-element lattices with 64-bit
+    messages.  The exact tail (a tilted convolution of M non-identical terms) is not computed."""
+    return _SoftNullLaw(levels, M).log10_bound(stat)
 
 
 # ===================================================================================================================== keyring
@@ -302,7 +395,8 @@ def _message_bytes(message_length) -> int:
     return m // 8
 
 
-def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1, fpr: float = 1e-6, l: int = 1, align=None) -> List[DetectResult]:
+def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1, fpr: float = 1e-6, l: int = 1, align=None,
+                   reliability: int = 0) -> List[DetectResult]:
     """latents [B, ...] on the device -> one DetectResult per image: the k best keys of the keyring (best first) with their Bonferroni
     bounds, the key that is named at false-positive rate `fpr` per image over the whole keyring (or None) and the message voted under it.
 
@@ -315,8 +409,18 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
     align: a list of candidate alignments (`align.alignments`) for images that may have been mirrored, turned by a quarter or shifted on the
     lattice; latents must then be [B, C, H, W].  The candidates come from `align.search_keys` (one more launch, `codec.rows_align`, in front of
     the search), the Bonferroni factor is K A, every candidate carries its best alignment, and each image is read after `align.apply` of
-    its best candidate's alignment.  None: exactly the path above."""
+    its best candidate's alignment.  None: exactly the path above.
+
+    reliability: 0, or the number of reliability levels (1..15) every lattice element votes with: `soft.uniform_thresholds`, one `codec.level_pack`, one
+    `codec.key_search_soft_topk` in place of the sign search, and the message of the best key read by one `codec.extract_soft` launch with the same
+    thresholds.  `KeyCandidate.stat` is then the level-weighted statistic and the bound under it `log10_p_blind_soft` -- a Chernoff bound given the image's
+    levels, which the host reads from the planes already on the device.  One cipher bit per element only (l = 1), and not with `align` yet (ValueError)."""
     import torch
+    reliability = _reliability_levels(reliability)
+    if reliability:
+        if align is not None:
+            raise ValueError("reliability cannot be combined with align yet: the level planes are not carried through the alignment search")
+        return _detect_latents_soft(latents, keyring, message_length, k, fpr, l, reliability)
     if align is not None:
         return _detect_latents_aligned(latents, keyring, message_length, k, fpr, l, align)
     limit = T._log10_fpr(fpr)
@@ -341,6 +445,49 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
     idx_h, stat_h = T._pairs_to_host(idx, stat)
     flags_h, bits_h, K = flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
     return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), K)),
+                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
+                              refuse=False)
+
+
+def _reliability_levels(reliability) -> int:
+    if isinstance(reliability, bool) or not isinstance(reliability, (int, np.integer)) or not 0 <= int(reliability) <= codec.SOFT_MAX_LEVELS:
+        raise ValueError(f"reliability must be 0 (the sign statistic) or a number of levels in 1..{codec.SOFT_MAX_LEVELS}, got {reliability!r}")
+    return int(reliability)
+
+
+def levels_from_planes(planes: np.ndarray) -> np.ndarray:
+    """`codec.level_pack`'s planes on the host, uint8 [B, P, n / 8] -> the levels int64 [B, n]"""
+    bits = np.unpackbits(planes, axis=2).astype(np.int64)
+    return sum(bits[:, p] << p for p in range(planes.shape[1]))
+
+
+def _detect_latents_soft(latents, keyring: Keyring, message_length: int, k: int, fpr: float, l: int, levels: int) -> List[DetectResult]:
+    """`detect_latents` ranked by `levels` reliability levels"""
+    import torch
+    limit = T._log10_fpr(fpr)
+    mb = _message_bytes(message_length)
+    M = 8 * mb
+    if codec.check_window(l) != 1:
+        raise ValueError(f"reliability cannot be combined with l = {l}: reliability levels are defined for one cipher bit per element")
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    keyring.packed()                                               # (an empty keyring fails here)
+    z = latents.contiguous()
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    codec.vote_copies(n, M, 1)                                     # (a lattice the message does not tile fails here, as extract_batch would)
+    keys_dev = keyring.to_device(z.device)
+    thr = S.uniform_thresholds(z, levels)
+    packed = codec.level_pack(z, thr)
+    idx, stat = codec.key_search_soft_topk(packed, n, keys_dev, mb, k=k)
+    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
+    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
+    bits = codec.extract_soft(z, rows, mb, thr).bits
+    idx_h, stat_h = T._pairs_to_host(idx, stat)
+    flags_h, bits_h, K = packed.flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
+    laws = [_SoftNullLaw(lv, M) for lv in levels_from_planes(packed.planes.cpu().numpy())]       # one dynamic programme per image, shared by its candidates
+    return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(laws[b].log10_bound(s), K)),
                               lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
                               refuse=False)
 
@@ -420,6 +567,9 @@ def build_parser():
     p.add_argument("--fpr", type=_fpr, default=1e-6, help="false-positive rate per image, over the whole keyring (Bonferroni), in (0, 1]")
     p.add_argument("--top", type=int, default=1, choices=range(1, 9), metavar="K", help="candidate keys reported per image (1..8)")
     p.add_argument("--l", type=int, default=1, choices=codec.WINDOWS, help="cipher bits per lattice element the images were embedded with")
+    p.add_argument("--reliability", type=int, default=0, choices=range(0, 16), metavar="L",
+                   help="rank the keys by level-weighted margins: every lattice element votes with one of L (1..15) reliability levels taken from its "
+                        "magnitude, the p-value is a Chernoff bound given the levels (--l 1, not with --align); 0: the sign statistic")
     p.add_argument("--align", default="none", choices=("none", "flips", "d4"),
                    help="also try every alignment of the lattice in this group: flips (half turn and the two mirrors) or d4 (all eight orientations); "
                         "the Bonferroni factor grows by the number of candidates")
@@ -449,7 +599,7 @@ def _detect_files(files, args, keyring) -> list:
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
-        return detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l, align=cands)
+        return detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l, align=cands, reliability=getattr(args, "reliability", 0))
 
     return T._trace_files(files, args, keyring, trace_batch=batch)
 
@@ -464,6 +614,8 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
         if getattr(args, "align", "none") != "none":
             fields += [("align", args.align), ("align_shift", args.align_shift)]
+        if getattr(args, "reliability", 0):
+            fields += [("reliability", args.reliability)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
@@ -480,6 +632,8 @@ def main(argv=None):
     _message_bytes(args.message_length)                            # fails before any model loads
     if args.align_shift < 0 or (args.align == "none" and args.align_shift):
         raise SystemExit("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
+    if args.reliability and (args.l != 1 or args.align != "none"):
+        raise SystemExit("--reliability needs --l 1 and cannot be combined with --align yet")
     keyring = load_keyring(args.keyring)
     keyring.packed()
     synthetic = X._no_checkpoint(args.model_id)

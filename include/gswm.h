@@ -738,6 +738,28 @@ int gsw_key_search_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const u
  * 1 048 576 bits, B > 65535.  GSW_ERR_RAGGED: C H W l is not a multiple of 8.  Every refusal happens before any launch. */
 int gsw_rows_align(const uint8_t* rows_dev, int B, int C, int H, int W, int l, const int32_t* aligns_dev, int A, uint8_t* out_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Blind key search ranked by reliability levels: gsw_key_search_topk with every lattice element weighted by
+ * gsw_level_pack's level.  One cipher bit per element (l = 1).  Additive: gsw_version() stays 500.
+ *
+ *   signs_dev  : uint8 [B, n_bits / 8], gsw_level_pack's sign row (any alignment)
+ *   planes_dev : uint8 [B, P, n_bits / 8], gsw_level_pack's plane rows, plane k = bit k of the levels (any alignment); P in 1 .. 4,
+ *                w_j = sum_k 2^k plane_k[j] in 0 .. 2^P - 1
+ *   keys_dev   : as gsw_key_search_topk
+ *   d          = signs[b] ^ keystream(key_u, nonce16_u), M = 8 msg_bytes, V = n_bits / M
+ *   X_t        = sum_{j mod M == t} w_j (2 d_j - 1)
+ *   stat[b,u]  = sum_t |X_t|, an exact int32 (at most 15 n_bits): sum_t |score[t]| of gsw_extract_soft under key u; with one plane of all
+ *                ones it is gsw_key_search_topk's stat bit for bit
+ *   out        : as gsw_key_search_topk; workspace_dev: gsw_key_search_soft_workspace_bytes(B, n_keys, k) bytes owned by the caller.  Every
+ *                output element is written, no atomics; the result depends on neither the launch geometry nor the arrival order.
+ * GSW_ERR_BAD_ARG: as gsw_key_search_topk, plus planes_dev null and P outside 1..4.  GSW_ERR_RAGGED: n_bits is not a multiple of 8 msg_bytes.
+ * GSW_ERR_UNSUPPORTED: n_bits (1 + P) > 1 048 576 (gsw_trace_keyed_soft_topk's domain), B > 65535.  Every refusal happens before any launch.
+ * gsw_key_search_soft_workspace_bytes returns 0 for B, n_keys, k that gsw_key_search_soft_topk refuses. */
+size_t gsw_key_search_soft_workspace_bytes(int B, int64_t n_keys, int k);
+int gsw_key_search_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int B, int64_t n_bits, const uint8_t* keys_dev,
+                             int64_t key_stride, int msg_bytes, int64_t n_keys, int k, int32_t* idx_dev, int32_t* stat_dev, void* workspace_dev,
+                             void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
