@@ -157,6 +157,8 @@ _PROTOTYPES = {
     "gsw_key_search_soft_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "gsw_key_search_soft_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsw_level_rows_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
 }
 
 _lib = None

@@ -18,6 +18,12 @@ The search reports the alignment that UNDOES the attack: `apply(attacked, found)
 Null law.  Under a key the image is independent of, the keystream is uniform, so the decrypted bits of ANY fixed permutation of the row are fair
 coins: `detect.log10_p_blind` holds for every (key, alignment) pair, and the Bonferroni bound over the K A pairs is valid whatever the
 dependence between the alignments of one image.
+
+Reliability levels (`search_keys_soft`, `extract_aligned_soft`, `detect.detect_latents_aligned_soft`; l = 1): the same search with every lattice
+element weighted by its level.  `codec.level_rows_align` writes every alignment of `codec.level_pack`'s sign row AND of its level planes in one
+launch and `codec.key_search_soft_topk` scores them; the thresholds are those of the un-aligned latents, since a permutation moves an element
+with its level.  The null bound (`detect.log10_p_blind_soft`) is taken given the levels UNDER the alignment: it changes which elements vote on
+which message position.
 """
 from __future__ import annotations
 
@@ -152,13 +158,14 @@ def _merge(key: torch.Tensor, stat: torch.Tensor, align: torch.Tensor, k: int):
     return key.contiguous(), align.contiguous(), stat.contiguous()
 
 
-def _merge_best(key: torch.Tensor, stat: torch.Tensor, n_keys: int):
+def _merge_best(key: torch.Tensor, stat: torch.Tensor, n_keys: int, stat_bits: int = 21):
     """`_merge` for k = 1, where a row's candidate IS its alignment's best key: the one entry that leads by (stat descending, key ascending, alignment
     ascending), found as the maximum of one int64 per entry -- a dozen launches instead of four sorts.  key, stat [B, A], column = alignment index.
+    stat_bits: the bits of the largest statistic (21: the sign search's, at most 1 048 576 lattice bits; `search_keys_soft` passes 25 for 15 times that).
     None when the three fields do not fit 63 bits (the caller then sorts)."""
     n = key.shape[1]
     ab, kb = max(1, (n - 1).bit_length()), max(1, (int(n_keys) - 1).bit_length())
-    if 21 + kb + ab > 62:                                            # stat <= 1 048 576 lattice bits
+    if stat_bits + kb + ab > 62:
         return None
     pos = torch.arange(n, dtype=torch.int64, device=key.device)
     c = stat.long() * (1 << (kb + ab)) - key.long() * (1 << ab) - pos
@@ -232,6 +239,68 @@ def search_keys(latents: torch.Tensor, keys_dev: torch.Tensor, msg_bytes: int, a
     return _search_packed(packed, latents.shape[1:], l, keys_dev, msg_bytes, _as_list(aligns, *latents.shape[2:]), k, budget_bytes)
 
 
+SOFT_STAT_BITS = 25                     # the level-weighted statistic is at most 15 x 1 048 576 < 2^24 (`_merge_best`'s stat field, with its sign)
+
+
+def _search_level_rows(rows: "codec.LevelRows", shape, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], k: int,
+                       budget_bytes: Optional[int] = None):
+    """`search_keys_soft` from `codec.level_pack`'s rows on: `_search_packed` with 1 + P rows per aligned image"""
+    shape = tuple(int(s) for s in shape)
+    table = _device_table(aligns, shape, rows.signs.device)
+    A = table.shape[0]
+    B, rowbytes = rows.signs.shape
+    P = rows.planes.shape[1]
+    n_bits = rowbytes * 8
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    budget = int(ROWS_BUDGET_BYTES if budget_bytes is None else budget_bytes)
+    per_row = (1 + P) * rowbytes                                                            # an aligned image: its sign row and its P planes
+    a_step = max(1, min(A, SEARCH_MAX_ROWS, budget // per_row))                             # alignments per launch (all of them unless one image's rows pass the budget)
+    b_step = max(1, min(B, SEARCH_MAX_ROWS // a_step, budget // (a_step * per_row)))        # images per launch
+    join = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, 1)
+    outs = []
+    for b0 in range(0, B, b_step):
+        rows_b = codec.LevelRows(*(t[b0:b0 + b_step] for t in rows))
+        nb = rows_b.signs.shape[0]
+        keys, stats = [], []
+        for a0 in range(0, A, a_step):
+            na = min(a_step, A - a0)
+            signs, planes = codec._level_rows_align_launch(rows_b, shape, table[a0:a0 + na])
+            al = codec.LevelRows(signs.view(nb * na, rowbytes), planes.view(nb * na, P, rowbytes), rows_b.wsum, rows_b.wsq, rows_b.flags)   # (the search reads signs and planes alone)
+            idx, stat = codec.key_search_soft_topk(al, n_bits, keys_dev, msg_bytes, k=k)
+            keys.append(idx.view(nb, na * k))
+            stats.append(stat.view(nb, na * k))
+        best = _merge_best(join(keys), join(stats), keys_dev.shape[0], SOFT_STAT_BITS) if k == 1 else None
+        if best is None:
+            als = torch.arange(A, dtype=torch.int32, device=rows.signs.device).repeat_interleave(k).expand(nb, A * k)
+            best = _merge(join(keys), join(stats), als, k)
+        outs.append(best)
+    return outs[0] if len(outs) == 1 else tuple(torch.cat([o[i] for o in outs]) for i in range(3))
+
+
+def search_keys_soft(latents: torch.Tensor, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], *, levels: int = 15,
+                     thresholds: Optional[torch.Tensor] = None, k: int = 1, budget_bytes: Optional[int] = None):
+    """`search_keys` ranked by reliability levels: (key_idx, align_idx, stat), int32 [B, k] each, on the device; stat is
+    `codec.key_search_soft_topk`'s level-weighted statistic of the image under that alignment.
+
+    latents [B, C, H, W] on the device, one cipher bit per element.  thresholds: float32 [levels] or [B, levels] as `codec.level_pack` takes
+    them (`levels` is then not read); None: `soft.uniform_thresholds(latents, levels)`, computed ONCE on the un-aligned latents (an alignment
+    permutes the elements, so their levels travel with them).  One `codec.level_pack`, then per chunk of images one `codec.level_rows_align` launch and one
+    `codec.key_search_soft_topk` on its [B A] rows, and `search_keys`' merge per image.  The cuts are `search_keys`' with (1 + P) rows counted
+    per aligned image against `budget_bytes`; the result does not depend on them."""
+    if latents.dim() != 4:
+        raise ValueError(f"search_keys_soft needs latents [B, C, H, W], got {tuple(latents.shape)}")
+    table = _as_list(aligns, *latents.shape[2:])
+    z = latents.contiguous()
+    if thresholds is None:
+        from . import soft as S
+        thresholds = S.uniform_thresholds(z, levels)
+    rows = codec.level_pack(z, thresholds)
+    codec._level_rows_align_checks(rows, z.shape[1:])
+    return _search_level_rows(rows, z.shape[1:], keys_dev, msg_bytes, table, k, budget_bytes)
+
+
 # ===================================================================================================================== known key
 @dataclass
 class AlignedExtract:
@@ -272,4 +341,21 @@ def extract_aligned(latents: torch.Tensor, key: bytes, nonce: bytes, message_len
         i, s = int(pairs[0, b]), int(pairs[1, b])
         p = T.log10_p_any(D.log10_p_blind(s, M, V), len(table))
         out.append(AlignedExtract(table[i], i, s, p, p <= limit, bits_h[b].copy(), int(flags_h[b])))
+    return out
+
+
+def extract_aligned_soft(latents: torch.Tensor, key: bytes, nonce: bytes, message_length: int, aligns: Sequence[Alignment], *, levels: int = 15,
+                         fpr: float = 1e-6) -> List[AlignedExtract]:
+    """`extract_aligned` ranked by reliability levels (l = 1), a keyring of one through `detect.detect_latents_aligned_soft`: per image the best
+    alignment by the level-weighted statistic, its Chernoff bound given the levels under that alignment over the A candidates, and the soft vote
+    (`codec.extract_soft`, the same thresholds) on the latent with that alignment applied."""
+    from . import detect as D
+    codec._check_key_nonce(key, nonce)
+    ring = D.Keyring()
+    ring.add("key", key, nonce)
+    results, aidx, bits = D._aligned_soft(latents, ring, message_length, aligns, levels, 1, fpr)
+    out = []
+    for r, i, row in zip(results, aidx, bits):
+        c = r.candidates[0]
+        out.append(AlignedExtract(c.alignment, int(i), c.stat, c.log10_p_any, r.key_id is not None, row.copy(), r.flags))
     return out

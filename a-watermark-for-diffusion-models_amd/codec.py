@@ -742,6 +742,72 @@ def key_search_soft_topk(rows: LevelRows, n_bits: int, keys: torch.Tensor, msg_b
     return idx, stat
 
 
+# ------------------------------------------------------------------------------------------------ alignment search ranked by reliability levels
+def _level_rows_align_launch(rows: LevelRows, shape: Tuple[int, int, int], aligns_dev: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`level_rows_align` after its checks -> (signs uint8 [B, A, rowbytes], planes uint8 [B, A, P, rowbytes])"""
+    B, rowbytes = rows.signs.shape
+    P, A = rows.planes.shape[1], aligns_dev.shape[0]
+    signs = torch.empty((B, A, rowbytes), dtype=torch.uint8, device=rows.signs.device)
+    planes = torch.empty((B, A, P, rowbytes), dtype=torch.uint8, device=rows.signs.device)
+    with torch.cuda.device(rows.signs.device):
+        N.check(N.lib().gsw_level_rows_align(rows.signs.data_ptr(), rows.planes.data_ptr(), P, B, shape[0], shape[1], shape[2], aligns_dev.data_ptr(), A,
+                                             signs.data_ptr(), planes.data_ptr(), _stream_ptr()))
+    return signs, planes
+
+
+def _level_rows_align_checks(rows: LevelRows, shape) -> Tuple[int, int, int]:
+    """The operand checks of `level_rows_align` (everything but the list of alignments) -> (C, H, W)"""
+    shape = _lattice_shape(shape)
+    signs, planes = rows.signs, rows.planes
+    _need_gpu(signs, "rows.signs")
+    n = shape[0] * shape[1] * shape[2]
+    if n % 8:
+        raise ValueError(f"a lattice of {shape} holds {n} bits: not whole bytes")
+    if signs.dtype != torch.uint8 or signs.dim() != 2 or signs.shape[0] < 1 or signs.shape[1] * 8 != n:
+        raise ValueError(f"rows.signs must be uint8 [B, {n // 8}] with B >= 1 for a lattice of {shape}, got {signs.dtype} {tuple(signs.shape)}")
+    B = signs.shape[0]
+    for t, name, check in _level_rows_checks(rows, True) + ((rows.wsq, "rows.wsq", None), (rows.flags, "rows.flags", None)):
+        _need_gpu(t, name)
+        _same_device(t, signs, name)
+        if check is not None:
+            check(B)
+        elif t.dtype != torch.int32 or tuple(t.shape) != (B,):
+            raise ValueError(f"{name} must be int32 [{B}]")
+    P = planes.shape[1]
+    if n * (1 + P) > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n} bits with {P} level planes is beyond the search's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
+    if B > 65535:
+        raise ValueError(f"level_rows_align takes at most 65535 images per launch, got {B}")
+    return shape
+
+
+def level_rows_align(rows: LevelRows, shape: Sequence[int], aligns) -> LevelRows:
+    """Every candidate alignment of `level_pack`'s rows, in one launch (gsw_level_rows_align): signs uint8 [B A, n/8] and planes uint8
+    [B A, P, n/8], row b A + a the rows of image b under aligns[a] -- the operand of `key_search_soft_topk` as it is.
+
+    rows: `level_pack`'s result for latents [B, C, H, W]; shape = (C, H, W); aligns: int32 [A, 3] rows (d, dy, dx) on the rows' device, or a list
+    of such triples that is uploaded here (`align.alignments`).  Every row is bit for bit `rows_align` of that input row at l = 1, and the rows of
+    (b, a) are `level_pack(align.apply(z[b], aligns[a]), thresholds[b])` for the thresholds the rows were packed with: the kernel computes where
+    an element comes from once and moves its sign and its level bits together.  wsum, wsq and flags are those of the image, repeated A times (a
+    permutation keeps them).  RuntimeError for host tensors (there is no CPU fallback); ValueError for a ragged lattice, n (1 + P) beyond 1 048 576,
+    more than 65 535 images, and the list checks of `rows_align` -- all before any launch."""
+    shape = _level_rows_align_checks(rows, shape)
+    table = align_table(aligns, shape)
+    if isinstance(aligns, torch.Tensor):
+        _need_gpu(aligns, "aligns")
+        _same_device(aligns, rows.signs, "aligns")
+        if aligns.dim() != 2:
+            raise ValueError("aligns must be int32 [A, 3]")
+        aligns_dev = aligns if aligns.is_contiguous() else aligns.contiguous()
+    else:
+        aligns_dev = torch.from_numpy(table).to(rows.signs.device)
+    A = table.shape[0]
+    signs, planes = _level_rows_align_launch(rows, shape, aligns_dev)
+    B, P, rowbytes = rows.planes.shape
+    return LevelRows(signs.view(B * A, rowbytes), planes.view(B * A, P, rowbytes), rows.wsum.repeat_interleave(A), rows.wsq.repeat_interleave(A),
+                     rows.flags.repeat_interleave(A))
+
+
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)
 TILES =(8, 16, 32)             # supported tile edges, in lattice elements
 

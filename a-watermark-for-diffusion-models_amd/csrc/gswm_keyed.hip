@@ -324,3 +324,4 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 #include "gswm_keysearch.inc"    // gsw_key_search_topk: every key of a keyring scored without a message
 #include "gswm_keysearch_soft.inc"   // gsw_key_search_soft_topk: the same search ranked by reliability levels
 #include "gswm_align.inc"        // gsw_rows_align: every candidate alignment of a packed row, the input of an alignment search
+#include "gswm_align_soft.inc"   // gsw_level_rows_align: the same for a sign row and its level planes, one index walk for all of them

@@ -21,6 +21,10 @@ Over a keyring of K keys the reported value is the Bonferroni bound `trace.log10
 Reliability levels (`detect_latents(..., reliability=L)`, `--reliability L`; l = 1): element j votes with its level w_j in 0..L (`codec.level_pack`),
 X_t = sum_{j mod M == t} w_j (2 d_j - 1) and S = sum_t |X_t| (`codec.key_search_soft_topk`).  Given the levels the X_t of a key-independent image are
 independent weighted Rademacher sums: `log10_p_blind_soft` computes their exact pmfs and bounds the tail of S by Chernoff -- an upper bound, not the tail.
+
+Both at once (`detect_latents_aligned_soft`, `--align ... --align_reliability L`; l = 1): the level-weighted statistic over every (key, alignment) pair
+(`align.search_keys_soft`), the Chernoff bound given the image's levels under THAT alignment, Bonferroni over K A.  `detect_latents(reliability=, align=)` still
+refuses the combination; the new names leave every existing path as it was.
 """
 from __future__ import annotations
 
@@ -526,6 +530,71 @@ def _detect_latents_aligned(latents, keyring: Keyring, message_length: int, k: i
                               refuse=False)
 
 
+def _aligned_soft(latents, keyring: Keyring, message_length: int, aligns, levels: int, k: int, fpr: float):
+    """`detect_latents_aligned_soft` -> (results, the best candidate's alignment index int [B], the bytes voted under it uint8 [B, msg_bytes])"""
+    import torch
+    from . import align as AL
+    limit = T._log10_fpr(fpr)
+    mb = _message_bytes(message_length)
+    M = 8 * mb
+    levels = _reliability_levels(levels)
+    if not levels:
+        raise ValueError(f"levels must be in 1..{codec.SOFT_MAX_LEVELS}: a search without levels is detect_latents(align=...)")
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    keyring.packed()                                               # (an empty keyring fails here)
+    if latents.dim() != 4:
+        raise ValueError(f"align needs latents [B, C, H, W], got {tuple(latents.shape)}")
+    z = latents.contiguous()
+    B, shape = z.shape[0], tuple(z.shape[1:])
+    table = AL._as_list(aligns, shape[1], shape[2])
+    codec.vote_copies(z.numel() // max(B, 1), M, 1)                # (a lattice the message does not tile fails here, as extract_batch would)
+    keys_dev = keyring.to_device(z.device)
+    thr = S.uniform_thresholds(z, levels)                          # once, on the un-aligned latents: the search, the bound and the vote share it
+    packed = codec.level_pack(z, thr)
+    codec._level_rows_align_checks(packed, shape)
+    idx, aidx, stat = AL._search_level_rows(packed, shape, keys_dev, mb, table, k)
+    host = torch.stack([idx, aidx, stat]).cpu().numpy()
+    idx_h, aidx_h, stat_h = host[0], host[1], host[2]
+    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
+    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
+    bits = codec.extract_soft(AL.unalign(z, table, aidx_h[:, 0]), rows, mb, thr).bits
+    flags_h, bits_h, pairs = packed.flags.cpu().numpy(), bits.cpu().numpy(), len(keyring) * len(table)
+    lv = levels_from_planes(packed.planes.cpu().numpy()).reshape(B, *shape)
+    laws: Dict[Tuple[int, int], _SoftNullLaw] = {}                 # one dynamic programme per distinct (image, alignment) among the reported candidates
+
+    def law(b: int, a: int) -> _SoftNullLaw:
+        t = laws.get((b, a))
+        if t is None:                                              # W_t depends on the alignment: it moves elements between message positions
+            t = laws[(b, a)] = _SoftNullLaw(AL.apply(torch.from_numpy(lv[b]), table[a]).reshape(-1).numpy(), M)
+        return t
+
+    out = T._candidate_lists(idx_h, stat_h, flags_h, limit,
+                             lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(law(b, int(aidx_h[b, j])).log10_bound(s), pairs),
+                                                             table[int(aidx_h[b, j])]),
+                             lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b]),
+                                                              c[0].alignment if named else None),
+                             refuse=False)
+    return out, aidx_h[:, 0], bits_h
+
+
+def detect_latents_aligned_soft(latents, keyring: Keyring, message_length: int, aligns, *, levels: int = 15, k: int = 1,
+                                fpr: float = 1e-6) -> List[DetectResult]:
+    """`detect_latents(align=...)` ranked by `levels` reliability levels (1..15; l = 1): the alignment search with every lattice element
+    weighted by its level.  latents [B, C, H, W] on the device, aligns from `align.alignments`.
+
+    `soft.uniform_thresholds` once on the un-aligned latents, one `codec.level_pack`, `align.search_keys_soft`'s search (per chunk of images one
+    `codec.level_rows_align` and one `codec.key_search_soft_topk`), and the message of the best key read by one `codec.extract_soft` launch on the
+    latents with their best alignment applied, under the SAME threshold table.  `KeyCandidate.stat` is the level-weighted statistic and
+    `alignment` that key's best alignment.  The bound is `log10_p_blind_soft` given the image's levels UNDER THAT ALIGNMENT -- an alignment moves
+    elements between message positions, so the W_t and with them the null law differ from one alignment to the next; the host permutes the levels
+    it read from the planes and runs one dynamic programme per distinct (image, alignment) among the reported candidates -- then Bonferroni over
+    the K A (key, alignment) pairs: under a key the image is independent of, the bits of any fixed permutation are fair coins independent of
+    the levels, so the bound holds for every pair and the union bound needs nothing else."""
+    return _aligned_soft(latents, keyring, message_length, aligns, levels, k, fpr)[0]
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result) -> str:
     """One line of detect.txt / stdout"""
@@ -574,6 +643,9 @@ def build_parser():
                    help="also try every alignment of the lattice in this group: flips (half turn and the two mirrors) or d4 (all eight orientations); "
                         "the Bonferroni factor grows by the number of candidates")
     p.add_argument("--align_shift", type=int, default=0, metavar="R", help="with --align: also every lattice shift in [-R, R]^2 (8 R pixels)")
+    p.add_argument("--align_reliability", type=int, default=0, choices=range(0, 16), metavar="L",
+                   help="with --align: rank every (key, alignment) pair by level-weighted margins, L (1..15) reliability levels per lattice element; the "
+                        "p-value is a Chernoff bound given the levels under the alignment (--l 1, not with --reliability); 0: the sign statistic")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -599,6 +671,8 @@ def _detect_files(files, args, keyring) -> list:
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
+            if getattr(args, "align_reliability", 0):
+                return detect_latents_aligned_soft(latents, keyring, args.message_length, cands, levels=args.align_reliability, k=args.top, fpr=args.fpr)
         return detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l, align=cands, reliability=getattr(args, "reliability", 0))
 
     return T._trace_files(files, args, keyring, trace_batch=batch)
@@ -616,6 +690,8 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
             fields += [("align", args.align), ("align_shift", args.align_shift)]
         if getattr(args, "reliability", 0):
             fields += [("reliability", args.reliability)]
+        if getattr(args, "align_reliability", 0):
+            fields += [("align_reliability", args.align_reliability)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
@@ -634,6 +710,8 @@ def main(argv=None):
         raise SystemExit("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
     if args.reliability and (args.l != 1 or args.align != "none"):
         raise SystemExit("--reliability needs --l 1 and cannot be combined with --align yet")
+    if args.align_reliability and (args.align == "none" or args.l != 1 or args.reliability):
+        raise SystemExit("--align_reliability needs --align flips or --align d4 and --l 1, and cannot be combined with --reliability")
     keyring = load_keyring(args.keyring)
     keyring.packed()
     synthetic = X._no_checkpoint(args.model_id)

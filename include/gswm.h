@@ -760,6 +760,27 @@ int gsw_key_search_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_dev
                              int64_t key_stride, int msg_bytes, int64_t n_keys, int k, int32_t* idx_dev, int32_t* stat_dev, void* workspace_dev,
                              void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Alignment search ranked by reliability levels: every candidate alignment of gsw_level_pack's sign row AND of its
+ * P level planes, written in one launch; the outputs, viewed as [B A, ...], are the operands of gsw_key_search_soft_topk without a copy.
+ * One cipher bit per element (l = 1).  Additive: gsw_version() stays 500.
+ *
+ *   signs_dev      : uint8 [B, n / 8], n = C H W, gsw_level_pack's sign row (any alignment)
+ *   planes_dev     : uint8 [B, P, n / 8], gsw_level_pack's plane rows (any alignment); P in 1 .. 4
+ *   aligns_dev     : int32 [A, 3] rows (d, dy, dx), 4-byte aligned, as gsw_rows_align
+ *   out_signs_dev  : uint8 [B, A, n / 8] (any alignment)
+ *   out_planes_dev : uint8 [B, A, P, n / 8] (any alignment)
+ * Row (b, a) of out_signs and row (b, a, p) of out_planes are bit for bit what gsw_rows_align writes for that input row at l = 1: a
+ * permutation of bits, so the levels travel with their elements and their sums do not change.  The source position of an element is computed
+ * once for all 1 + P rows.  An entry with d outside 0..7, or an odd d when H != W, writes zeros to all its 1 + P rows (the callers of this
+ * package refuse such a list before it is uploaded).  Every output byte is written, no atomics, no workspace, integer arithmetic only.  The
+ * 1 + P rows of an image are staged in LDS once per workgroup while they total at most 65 536 bytes (each padded to 16), else read in place.
+ * GSW_ERR_BAD_ARG: null pointer, aligns_dev not 4-byte aligned, P outside 1..4, B, C, H, W or A < 1.  GSW_ERR_UNSUPPORTED:
+ * C H W (1 + P) > 1 048 576 bits (gsw_key_search_soft_topk's domain), B > 65535.  GSW_ERR_RAGGED: C H W is not a multiple of 8.  Every
+ * refusal happens before any launch. */
+int gsw_level_rows_align(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int B, int C, int H, int W, const int32_t* aligns_dev, int A,
+                         uint8_t* out_signs_dev, uint8_t* out_planes_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
