@@ -46,10 +46,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cstdint>
 #include <cstdlib>
 
 #include "../../include/gswm.h"
+#include "gswm_attn_plan.h"
 
 extern __attribute__((visibility("hidden"))) thread_local int g_last_hip_error;   // gswm_kernels.hip
 
@@ -625,57 +627,47 @@ __global__ __launch_bounds__(256) void gsw_attn_combine_kernel(AttnArgs p) {
 
 }  // namespace
 
+// Launches what attn_decide (gswm_attn_plan.h) decided; every condition of the policy lives there.
 template <typename T, int QB, int DU>
-static int launch_attn_cfg(const AttnArgs& a, uint32_t grid, bool ragged, float* ws, int64_t ws_bytes, hipStream_t st) {
-    constexpr int KC = (DU + 1) / 2, DBF = DU * 8 / 32, TR = DU * 8 % 32, NACC = DBF * 16 + (TR ? 8 : 0);
-    constexpr uint32_t stage = 64 * (KC * 32 + 16) + (DBF * 32 + (TR ? 16 : 0)) * VP;
-    // Key-split form: few query tiles against many key tiles (one image's self-attention at 64 x 64: 62 -> 49 us).  As many splits as keep every workgroup
-    // resident at once (2 per CU); only from 32 key tiles up -- the second launch and the partial results cost ~12 us, and at 16 tiles (32 x 32: 17.6 -> 21.4 us)
-    // that is more than the split saves.  Needs the caller's workspace (gsw_attention_ws); GSW_ATTN_KVS=0 switches it off (A/B), k > 1 forces k ways from 8 tiles up.
+static int launch_attn_cfg(const AttnArgs& a, const AttnLaunch& d, float* ws, hipStream_t st) {
     if constexpr (QB == 1 && (DU == 8 || DU == 5)) {
-        static const int kvs_env = getenv("GSW_ATTN_KVS") ? atoi(getenv("GSW_ATTN_KVS")) : 1;
-        const int32_t nt = a.Sk >> 6;
-        if (!ragged && kvs_env && ws && a.Sk_valid == a.Sk && a.total <= 256u && nt >= (kvs_env > 1 ? 8 : 32)) {
-            uint32_t ksplit = (uint32_t)std::min<int64_t>(std::min<int64_t>(512 / a.total, nt / 4), 8);
-            if (kvs_env > 1) ksplit = (uint32_t)std::min<int>(kvs_env, nt);                                   // (tests: force a split count)
-            const int64_t need = (int64_t)a.total * ksplit * 4 * (NACC + 2) * 64 * (int64_t)sizeof(float);
-            if (ksplit >= 2 && need <= ws_bytes) {
-                AttnArgs k = a;
-                k.ksplit = ksplit; k.part = ws;
-                hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, 1, DU, false, false, true>), dim3(a.total * ksplit), dim3(256), 2 * stage, st, k);
-                hipLaunchKernelGGL((gsw_attn_combine_kernel<T, DU>), dim3(a.total), dim3(256), 0, st, k);
-                return GSW_OK;
-            }
-        }
-    }
-    static const int pair_env = getenv("GSW_ATTN_PAIR") ? atoi(getenv("GSW_ATTN_PAIR")) : 1;      // A/B switch for profiling
-    const bool pair = !ragged && pair_env && 4 * stage <= 80 * 1024 && (a.Sk >> 6) >= 16;      // long key sequences only: +2 % at 4096 keys, a loss at 256
-    const uint32_t lds = (pair ? 4 : 2) * stage;
-    const void* fn = pair ? (const void*)gsw_attn_fwd_kernel<T, QB, DU, true, false>
-                          : (ragged ? (const void*)gsw_attn_fwd_kernel<T, 1, DU, false, true> : (const void*)gsw_attn_fwd_kernel<T, QB, DU, false, false>);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { g_last_hip_error = (int)e; return GSW_ERR_HIP; }
-    }
-    if constexpr (DU == 8) {
-        static const int dma_env = getenv("GSW_ATTN_DMA") ? atoi(getenv("GSW_ATTN_DMA")) : 1;      // A/B switch
-        if (pair && dma_env && ((a.Sk >> 6) & 3) == 0) {      // K / V^T tiles by LDS-DMA into four static stages (64 KiB)
-            hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, QB, DU, true, false, false, true>), dim3(grid), dim3(256), 0, st, a);
+        if (d.ksplit > 1) {
+            AttnArgs k = a;
+            k.ksplit = d.ksplit; k.part = ws;
+            hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, 1, DU, false, false, true>), dim3(d.grid), dim3(256), d.lds_bytes, st, k);
+            hipLaunchKernelGGL((gsw_attn_combine_kernel<T, DU>), dim3(d.total), dim3(256), 0, st, k);
             return GSW_OK;
         }
     }
-    if (pair) hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, QB, DU, true, false>), dim3(grid), dim3(256), lds, st, a);
-    else if (ragged) hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, 1, DU, false, true>), dim3(grid), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, QB, DU, false, false>), dim3(grid), dim3(256), lds, st, a);
+    if constexpr (DU == 8) {
+        if (d.dma) {
+            hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, QB, DU, true, false, false, true>), dim3(d.grid), dim3(256), 0, st, a);
+            return GSW_OK;
+        }
+    }
+    const void* fn = d.pair ? (const void*)gsw_attn_fwd_kernel<T, QB, DU, true, false>
+                            : (d.ragged ? (const void*)gsw_attn_fwd_kernel<T, 1, DU, false, true> : (const void*)gsw_attn_fwd_kernel<T, QB, DU, false, false>);
+    if (d.lds_bytes > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds_bytes);
+        if (e != hipSuccess) { g_last_hip_error = (int)e; return GSW_ERR_HIP; }
+    }
+    if (d.pair) hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, QB, DU, true, false>), dim3(d.grid), dim3(256), d.lds_bytes, st, a);
+    else if (d.ragged) hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, 1, DU, false, true>), dim3(d.grid), dim3(256), d.lds_bytes, st, a);
+    else hipLaunchKernelGGL((gsw_attn_fwd_kernel<T, QB, DU, false, false>), dim3(d.grid), dim3(256), d.lds_bytes, st, a);
     return GSW_OK;
 }
 
 template <typename T>
-static int launch_attn(const AttnArgs& a, int head_dim, int QB, uint32_t grid, bool ragged, float* ws, int64_t wsb, hipStream_t st) {
-    if (head_dim == 64) return QB == 2 ? launch_attn_cfg<T, 2, 8>(a, grid, ragged, ws, wsb, st) : launch_attn_cfg<T, 1, 8>(a, grid, ragged, ws, wsb, st);
-    if (head_dim == 40) return QB == 2 ? launch_attn_cfg<T, 2, 5>(a, grid, ragged, ws, wsb, st) : launch_attn_cfg<T, 1, 5>(a, grid, ragged, ws, wsb, st);
-    if (head_dim == 80) return launch_attn_cfg<T, 1, 10>(a, grid, ragged, ws, wsb, st);
-    return launch_attn_cfg<T, 1, 20>(a, grid, ragged, ws, wsb, st);
+static int launch_attn(const AttnArgs& a, int head_dim, const AttnLaunch& d, float* ws, hipStream_t st) {
+    if (head_dim == 64) return d.QB == 2 ? launch_attn_cfg<T, 2, 8>(a, d, ws, st) : launch_attn_cfg<T, 1, 8>(a, d, ws, st);
+    if (head_dim == 40) return d.QB == 2 ? launch_attn_cfg<T, 2, 5>(a, d, ws, st) : launch_attn_cfg<T, 1, 5>(a, d, ws, st);
+    if (head_dim == 80) return launch_attn_cfg<T, 1, 10>(a, d, ws, st);
+    return launch_attn_cfg<T, 1, 20>(a, d, ws, st);
+}
+
+static int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v ? atoi(v) : dflt;
 }
 
 int gsw_attention(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int B, int H, int head_dim, int Sq, int Sk, int Sk_valid,
@@ -685,33 +677,27 @@ int gsw_attention(const void* q_dev, const void* k_dev, const void* vt_dev, void
 
 int gsw_attention_ws(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int B, int H, int head_dim, int Sq, int Sk, int Sk_valid,
                      int ldq, int ldk, int ldo, float scale, int dtype, void* workspace_dev, int64_t workspace_bytes, void* stream) {
-    if (workspace_bytes < 0 || (workspace_bytes > 0 && !workspace_dev) || ((uintptr_t)workspace_dev & 15)) return GSW_ERR_BAD_ARG;
     // q: [B, Sq, >= H*head_dim] (row stride ldq), k: [B, Sk, >= H*head_dim] (row stride ldk), vt: [B, H*head_dim, Sk] contiguous (V
     // transposed), out: [B, Sq, >= H*head_dim] (row stride ldo).  head_dim 40 / 64 / 80 / 160; any Sq; Sk % 8 == 0; row strides
-    // multiples of 8 elements; keys in [Sk_valid, Sk) are padding and get zero weight.
-    if (!q_dev || !k_dev || !vt_dev || !out_dev || B <= 0 || H <= 0 || Sq <= 0 || Sk <= 0 || Sk_valid <= 0 || Sk_valid > Sk) return GSW_ERR_BAD_ARG;
+    // multiples of 8 elements; keys in [Sk_valid, Sk) are padding and get zero weight.  The kernels form max(s) * scale before the exponentials: that is the
+    // maximum of the scaled scores only for a scale that is finite and > 0.
+    if ((workspace_bytes > 0 && !workspace_dev) || ((uintptr_t)workspace_dev & 15)) return GSW_ERR_BAD_ARG;
+    if (!q_dev || !k_dev || !vt_dev || !out_dev || !(scale > 0.f && scale <= FLT_MAX)) return GSW_ERR_BAD_ARG;
     if (dtype != GSW_F16 && dtype != GSW_BF16) return GSW_ERR_BAD_ARG;
-    if (head_dim != 40 && head_dim != 64 && head_dim != 80 && head_dim != 160) return GSW_ERR_UNSUPPORTED;
+    static const AttnSwitches sw = {env_int("GSW_ATTN_QB", 2), env_int("GSW_ATTN_PAIR", 1), env_int("GSW_ATTN_DMA", 1), env_int("GSW_ATTN_KVS", 1)};      // A/B switches for profiling
+    const AttnLaunch d = attn_decide(B, H, head_dim, Sq, Sk, Sk_valid, workspace_bytes, sw);
+    if (d.status != GSW_OK) return d.status;
     const int inner = H * head_dim;
-    if ((Sk & 7) || ldq < inner || ldk < inner || ldo < inner || ((ldq | ldk | ldo) & 7)) return GSW_ERR_UNSUPPORTED;
-    static const int qb_env = getenv("GSW_ATTN_QB") ? atoi(getenv("GSW_ATTN_QB")) : 2;      // A/B switch for profiling
-    const bool ragged = (Sq & 127) || (Sk & 63);
-    // 256-query workgroups once there are plenty of them (7-12 % faster from ~1000 workgroups up); below ~400 of them the 128-query form keeps more CUs
-    // busy (one image at 64 x 64: 62 vs 91 us; profiles/r03y_attention_query_tile_sweep.txt)
-    const int64_t wg256 = (int64_t)(Sq / 256) * B * H;
-    const int QB = ((Sq & 255) == 0 && Sq >= 512 && qb_env >= 2 && head_dim < 80 && !ragged && (wg256 > 400 || qb_env == 3)) ? 2 : 1;      // (GSW_ATTN_QB: 1 / 3 force a form)
-    const int64_t total = (int64_t)((Sq + 128 * QB - 1) / (128 * QB)) * B * H;
-    if (total > 0x7FFFFFFF) return GSW_ERR_UNSUPPORTED;
+    if (ldq < inner || ldk < inner || ldo < inner || ((ldq | ldk | ldo) & 7)) return GSW_ERR_UNSUPPORTED;
     AttnArgs a;
     a.q = q_dev; a.k = k_dev; a.vt = vt_dev; a.o = out_dev;
     a.H = H; a.Sq = Sq; a.Sk = Sk; a.ldq = ldq; a.ldk = ldk; a.ldo = ldo; a.Sk_valid = Sk_valid;
     a.scale_log2 = scale * 1.4426950408889634f;
-    a.nqt = (uint32_t)((Sq + 128 * QB - 1) / (128 * QB));
-    a.total = (uint32_t)total;
+    a.nqt = d.nqt;
+    a.total = d.total;
     a.ksplit = 1; a.part = nullptr;
-    float* const ws = workspace_bytes > 0 ? (float*)workspace_dev : nullptr;
-    const int rc = dtype == GSW_F16 ? launch_attn<_Float16>(a, head_dim, QB, (uint32_t)total, ragged, ws, workspace_bytes, (hipStream_t)stream)
-                                    : launch_attn<__bf16>(a, head_dim, QB, (uint32_t)total, ragged, ws, workspace_bytes, (hipStream_t)stream);
+    const int rc = dtype == GSW_F16 ? launch_attn<_Float16>(a, head_dim, d, (float*)workspace_dev, (hipStream_t)stream)
+                                    : launch_attn<__bf16>(a, head_dim, d, (float*)workspace_dev, (hipStream_t)stream);
     if (rc != GSW_OK) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { g_last_hip_error = (int)e; return GSW_ERR_HIP; }
@@ -782,7 +768,7 @@ __global__ __launch_bounds__(256) void gsw_softmax_rows_kernel(T* __restrict__ x
 }
 
 int gsw_softmax_rows(void* x_dev, int64_t rows, int cols, int64_t ld, float scale, int dtype, void* stream) {
-    if (!x_dev || rows < 0 || cols <= 0 || ld < cols) return GSW_ERR_BAD_ARG;
+    if (!x_dev || rows < 0 || cols <= 0 || ld < cols || !(scale > 0.f && scale <= FLT_MAX)) return GSW_ERR_BAD_ARG;      // (max(x) * scale is the maximum of the scaled row only for scale > 0)
     if (dtype != GSW_F16 && dtype != GSW_BF16) return GSW_ERR_BAD_ARG;
     if ((cols & 7) || (ld & 7) || rows > 0x7FFFFFFF) return GSW_ERR_UNSUPPORTED;
     if (rows == 0) return GSW_OK;

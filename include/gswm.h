@@ -307,7 +307,8 @@ int gsw_mm_config(int tile_rows, int split_mask);
 int gsw_mm_get_config(int* tile_rows, int* split_mask); /* the current values (either pointer may be NULL): what a captured launch sequence depends on */
 
 /* X1 / G1 tail -- diffusers AutoencoderKL mid-block attention (one head as wide as the block, 512): softmax over the rows of the score matrix
- * between the two engine products.  In place: x[r, 0:cols] <- softmax(scale * x[r, 0:cols]); rows `ld` elements apart; cols % 8 == 0. */
+ * between the two engine products.  In place: x[r, 0:cols] <- softmax(scale * x[r, 0:cols]); rows `ld` elements apart; cols % 8 == 0; a scale that is not
+ * finite and > 0 returns GSW_ERR_BAD_ARG. */
 int gsw_softmax_rows(void* x_dev, int64_t rows, int cols, int64_t ld, float scale, int dtype, void* stream);
 
 /* ---- The small-batch regime of the eps model (csrc/gswm_small.hip).  The reference inverts ONE latent per call (extract.py:112-117: 50 UNet
@@ -362,7 +363,7 @@ int gsw_conv_up2x_pf(const void* x_dev, const void* w4_dev, const void* bias_dev
  *   out : [B, Sq, >= H*head_dim] row stride ldo
  *   Sk_valid : keys in [Sk_valid, Sk) are padding and get zero weight (cross-attention: 77 context tokens padded to 128)
  * Any Sq; Sk % 8 == 0; strides % 8 == 0; else GSW_ERR_UNSUPPORTED (sequences off the 128-query / 64-key tiles run a variant with clamped
- * loads and masked keys). */
+ * loads and masked keys).  A scale that is not finite and > 0 returns GSW_ERR_BAD_ARG. */
 int gsw_attention(const void* q_dev, const void* k_dev, const void* vt_dev, void* out_dev, int B, int H, int head_dim, int Sq, int Sk,
                   int Sk_valid, int ldq, int ldk, int ldo, float scale, int dtype, void* stream);
 /* The same with a caller-owned scratch buffer (16-byte aligned device memory, free again when the launch's stream has run it): few query tiles against many

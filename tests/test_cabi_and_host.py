@@ -173,6 +173,13 @@ def test_argument_validation_of_eps_model_and_image_entry_points():
     assert lib.gsw_attention(p, p, p, p, 1, 5, 64, 256, 128, 129, 320, 320, 320, 0.125, 1, None) == BAD          # valid keys > keys
     assert lib.gsw_attention(p, p, p, p, 1, 5, 64, 256, 128, 77, 316, 320, 320, 0.125, 1, None) == UNS           # row stride < H * d
     assert lib.gsw_attention(p, p, p, p, 1, 5, 64, 256, 128, 77, 320, 320, 320, 0.125, 0, None) == BAD           # fp32
+    # a scale that is not finite and > 0: the kernels take max(s) * scale for the maximum of the scaled scores
+    for scale in (0.0, -0.125, -0.0, float("inf"), float("-inf"), float("nan")):
+        assert lib.gsw_attention(p, p, p, p, 1, 5, 64, 256, 256, 256, 320, 320, 320, scale, 1, None) == BAD, scale
+        assert lib.gsw_attention_ws(p, p, p, p, 1, 5, 64, 256, 256, 256, 320, 320, 320, scale, 1, None, 0, None) == BAD, scale
+        assert lib.gsw_attention_ws(p, p, p, p, 1, 5, 48, 256, 256, 256, 240, 240, 240, scale, 1, None, 0, None) == BAD, scale      # (a bad argument wins over an unsupported shape)
+        assert lib.gsw_softmax_rows(p, 4, 128, 128, scale, 1, None) == BAD, scale
+    assert lib.gsw_softmax_rows(p, 0, 128, 128, 1e-30, 1, None) == N.GSW_OK                                      # (tiny but > 0 is a scale)
     # convolutions on padded-flat activations
     assert lib.gsw_conv_pf(p, p, None, None, 0, None, p, 1, 8, 8, 60, 64, 3, 1, 60, 1, None) == UNS                 # C % 64
     assert lib.gsw_conv_pf(p, p, None, None, 0, None, p, 1, 8, 8, 64, 64, 5, 1, 64, 1, None) == BAD                 # 5x5
