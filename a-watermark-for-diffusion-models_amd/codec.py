@@ -681,6 +681,99 @@ def level_pack(z: torch.Tensor, thresholds: torch.Tensor) -> LevelRows:
     return LevelRows(signs, planes, wsum, wsq, flags)
 
 
+# ------------------------------------------------------------------------------------------------ soft-decision vote, multi-bit windows (l = 2, 4)
+def _multi_bit_window(l, twin: str) -> int:
+    """l as 2 or 4; l = 1 is refused with a pointer to the l = 1 function"""
+    l = check_window(l)
+    if l == 1:
+        raise ValueError(f"l = 1 has one cipher bit per element and no window bits: use `{twin}`")
+    return l
+
+
+def _window_table(thresholds: torch.Tensor, z: torch.Tensor, B: int, l: int) -> int:
+    """The checks `extract_soft_l` and `level_pack_l` share on the per-window-bit table -> levels"""
+    _need_gpu(thresholds, "thresholds")
+    _same_device(thresholds, z, "thresholds")
+    if (thresholds.dtype != torch.float32 or thresholds.dim() not in (2, 3) or thresholds.shape[-2] != l
+            or (thresholds.dim() == 3 and thresholds.shape[0] != B)):
+        raise ValueError(f"thresholds must be float32 [{l}, levels] or [{B}, {l}, levels]")
+    levels = thresholds.shape[-1]
+    if not 1 <= levels <= SOFT_MAX_LEVELS:
+        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
+    return levels
+
+
+def extract_soft_l(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresholds: torch.Tensor, l: int) -> SoftVote:
+    """The soft-decision vote at l = 2 or 4, every image under its OWN record, in one launch (gsw_extract_soft_l): each of the n l cipher
+    bits of an image votes for its decrypted value with an integer level, the distance of its element from the nearest quantiser boundary
+    at which that bit would have come out differently.
+
+    Element e holds z and the window y = (z >= quant_thresholds(l)).sum(); window bit w (0 = MSB of y, cipher position e l + w) has the
+    value s = 2**(l-1-w) in y, a = (y // s) s and c = a + s are the flip boundaries around z, and
+    level(e, w) = #{ i : (a == 0 or Z >= T_a + t_i) and (c == 2**l or Z <= T_c - t_i) }, t_i = thresholds[b][w][i], Z = z in float64, sums
+    and compares in float64 -- exact in every dtype; a NaN has level 0.
+
+    z: latents [B, ...] (fp16 / bf16 / fp32 / fp64), records: as `extract_records`, thresholds: float32 [l, levels] (one table for all
+    images) or [B, l, levels] on z's device, levels in 1..15 (`soft.window_thresholds`).  Returns a `SoftVote` whose score and wsum sum over
+    the copies of a message bit and whose wsq sums over all n l bits.  With one level at threshold 0 on NaN-free images the bits are
+    `extract_records(..., l=l)`'s bits and score = 2 counts - copies.  n must be a multiple of 8 and n l at most 1 048 576 (ValueError);
+    IndexError as `extract_records`.  l = 1 is refused: that is `extract_soft`."""
+    l = _multi_bit_window(l, "extract_soft")
+    B, stride, msg_bytes = _records_operand(records, msg_bytes)
+    _need_gpu(z, "z")
+    _same_device(records, z, "records")
+    if z.dim() < 2 or z.shape[0] != B:
+        raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
+    levels = _window_table(thresholds, z, B, l)
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 1 or n % 8 or n * l > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n} elements at l = {l} must be a multiple of 8 elements and hold at most {ROW_MAX_BITS} bits")
+    M = 8 * msg_bytes
+    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    matches = torch.empty((B,), dtype=torch.int32, device=z.device)
+    score = torch.empty((B, M), dtype=torch.int32, device=z.device)
+    wsum = torch.empty((B, M), dtype=torch.int32, device=z.device)
+    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
+    thresholds = thresholds.contiguous()
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_extract_soft_l(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, thresholds.data_ptr(),
+                                           l * levels if thresholds.dim() == 3 else 0, levels, l, bits.data_ptr(), score.data_ptr(),
+                                           wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), matches.data_ptr(), B, n, _stream_ptr()))
+    return SoftVote(bits, flags, matches, score, wsum, wsq)
+
+
+def level_pack_l(z: torch.Tensor, thresholds: torch.Tensor, l: int) -> LevelRows:
+    """`level_pack` at l = 2 or 4, in one launch (gsw_level_pack_l): the row of `quant_pack(z, l)` bit for bit, `extract_soft_l`'s level of
+    every cipher bit as P bit planes over the same n l bits, and the image's sum of levels and of squared levels -- the operands of
+    `trace_keyed_soft_topk` and `key_search_soft_topk` with n_bits = n l.  thresholds: float32 [l, levels] or [B, l, levels] on z's device.
+    n must be a multiple of 8 and n l at most 1 048 576; the searches refuse n l (1 + P) > 1 048 576.  l = 1 is refused: that is
+    `level_pack`."""
+    l = _multi_bit_window(l, "level_pack")
+    _need_gpu(z, "z")
+    if z.dim() < 2 or z.shape[0] < 1:
+        raise ValueError("z must be [B, ...] with at least one image")
+    B = z.shape[0]
+    levels = _window_table(thresholds, z, B, l)
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 8 or n % 8 or n * l > ROW_MAX_BITS:
+        raise ValueError(f"level_pack_l needs a lattice of a multiple of 8 elements per image and at most {ROW_MAX_BITS} bits (got {n} at l = {l})")
+    P = level_planes(levels)
+    nbytes = n * l // 8
+    signs = torch.empty((B, nbytes), dtype=torch.uint8, device=z.device)
+    planes = torch.empty((B, P, nbytes), dtype=torch.uint8, device=z.device)
+    wsum = torch.empty((B,), dtype=torch.int32, device=z.device)
+    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
+    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
+    thresholds = thresholds.contiguous()
+    with torch.cuda.device(z.device):
+        N.check(N.lib().gsw_level_pack_l(z.data_ptr(), dt, thresholds.data_ptr(), l * levels if thresholds.dim() == 3 else 0, levels, l,
+                                         signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
+    return LevelRows(signs, planes, wsum, wsq, flags)
+
+
 def _level_rows_checks(rows: "LevelRows", with_wsum: bool):
     """(planes_check, wsum_check) of a `LevelRows` operand for `_search_operands`' extras"""
     signs, planes, wsum = rows.signs, rows.planes, rows.wsum

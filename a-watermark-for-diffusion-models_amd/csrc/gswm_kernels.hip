@@ -1663,3 +1663,8 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
 // Soft-decision vote (every element weighted by an integer reliability level): gsw_extract_soft, kernel and entry point
 // ------------------------------------------------------------------------------------------------
 #include "gswm_codec_soft.inc"
+
+// ------------------------------------------------------------------------------------------------
+// Soft-decision vote for multi-bit windows (l = 2, 4; a level per cipher bit): gsw_extract_soft_l / gsw_level_pack_l, kernels and entry points
+// ------------------------------------------------------------------------------------------------
+#include "gswm_codec_soft_l.inc"

@@ -25,6 +25,10 @@ independent weighted Rademacher sums: `log10_p_blind_soft` computes their exact 
 Both at once (`detect_latents_aligned_soft`, `--align ... --align_reliability L`; l = 1): the level-weighted statistic over every (key, alignment) pair
 (`align.search_keys_soft`), the Chernoff bound given the image's levels under THAT alignment, Bonferroni over K A.  `detect_latents(reliability=, align=)` still
 refuses the combination; the new names leave every existing path as it was.
+
+Reliability levels at l = 2 and 4 (`detect_latents_soft_l`, `--window_reliability L --l 2|4`): every cipher BIT of an element votes with a level, its element's
+distance from the nearest quantiser boundary that would flip it (`codec.level_pack_l`); the search kernel and the Chernoff bound are the ones above over the n l
+bits.  Not with `--align`.
 """
 from __future__ import annotations
 
@@ -496,6 +500,47 @@ def _detect_latents_soft(latents, keyring: Keyring, message_length: int, k: int,
                               refuse=False)
 
 
+def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int, *, levels: int = 15, k: int = 1, fpr: float = 1e-6) -> List[DetectResult]:
+    """`detect_latents(reliability=levels)` for multi-bit windows (l = 2 or 4): every one of the n l cipher bits of an
+    image votes with a level 0..levels, the distance of its element from the nearest quantiser boundary at which that bit would have come out
+    differently.  `soft.window_thresholds`, one `codec.level_pack_l`, the unchanged `codec.key_search_soft_topk` with n_bits = n l, and the
+    message of the best key read by one `codec.extract_soft_l` launch with the same thresholds.  `KeyCandidate.stat` is the level-weighted
+    statistic; the bound under it is `log10_p_blind_soft` on the n l per-bit levels read back from the planes (given the levels, the decrypted
+    bits of a key-independent image are independent fair coins, per cipher bit), Bonferroni over the keyring.  n l (1 + P) may not exceed
+    1 048 576, P the bit length of `levels`: the search refuses beyond (ValueError).  l = 1 is refused: that is `detect_latents(reliability=)`."""
+    import torch
+    limit = T._log10_fpr(fpr)
+    mb = _message_bytes(message_length)
+    M = 8 * mb
+    l = codec.check_window(l)
+    if l == 1:
+        raise ValueError("l = 1 has no window bits: the level-weighted key search at l = 1 is detect_latents(reliability=) (--reliability)")
+    levels = _reliability_levels(levels)
+    if not levels:
+        raise ValueError(f"levels must be a number of levels in 1..{codec.SOFT_MAX_LEVELS}, got 0")
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    keyring.packed()                                               # (an empty keyring fails here)
+    z = latents.contiguous()
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    codec.vote_copies(n, M, l)                                     # (a lattice the message does not tile fails here, as extract_batch would)
+    keys_dev = keyring.to_device(z.device)
+    thr = S.window_thresholds(z, l, levels)
+    packed = codec.level_pack_l(z, thr, l)
+    idx, stat = codec.key_search_soft_topk(packed, n * l, keys_dev, mb, k=k)
+    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
+    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
+    bits = codec.extract_soft_l(z, rows, mb, thr, l).bits
+    idx_h, stat_h = T._pairs_to_host(idx, stat)
+    flags_h, bits_h, K = packed.flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
+    laws = [_SoftNullLaw(lv, M) for lv in levels_from_planes(packed.planes.cpu().numpy())]       # over the n l cipher bits, bit j on message position j mod M
+    return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(laws[b].log10_bound(s), K)),
+                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
+                              refuse=False)
+
+
 def _detect_latents_aligned(latents, keyring: Keyring, message_length: int, k: int, fpr: float, l: int, aligns) -> List[DetectResult]:
     """`detect_latents` with candidate alignments"""
     import torch
@@ -646,6 +691,10 @@ def build_parser():
     p.add_argument("--align_reliability", type=int, default=0, choices=range(0, 16), metavar="L",
                    help="with --align: rank every (key, alignment) pair by level-weighted margins, L (1..15) reliability levels per lattice element; the "
                         "p-value is a Chernoff bound given the levels under the alignment (--l 1, not with --reliability); 0: the sign statistic")
+    p.add_argument("--window_reliability", type=int, default=0, choices=range(0, 16), metavar="L",
+                   help="with --l 2 or 4: rank the keys by level-weighted margins, every cipher bit of a lattice element votes with one of L (1..15) "
+                        "levels taken from its distance to the quantiser boundaries that would flip it; the p-value is a Chernoff bound given the levels "
+                        "(not with --align, --reliability or --align_reliability); 0: the sign statistic")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -673,6 +722,8 @@ def _detect_files(files, args, keyring) -> list:
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
             if getattr(args, "align_reliability", 0):
                 return detect_latents_aligned_soft(latents, keyring, args.message_length, cands, levels=args.align_reliability, k=args.top, fpr=args.fpr)
+        if getattr(args, "window_reliability", 0):
+            return detect_latents_soft_l(latents, keyring, args.message_length, args.l, levels=args.window_reliability, k=args.top, fpr=args.fpr)
         return detect_latents(latents, keyring, args.message_length, k=args.top, fpr=args.fpr, l=args.l, align=cands, reliability=getattr(args, "reliability", 0))
 
     return T._trace_files(files, args, keyring, trace_batch=batch)
@@ -692,6 +743,8 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
             fields += [("reliability", args.reliability)]
         if getattr(args, "align_reliability", 0):
             fields += [("align_reliability", args.align_reliability)]
+        if getattr(args, "window_reliability", 0):
+            fields += [("window_reliability", args.window_reliability)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
@@ -712,6 +765,8 @@ def main(argv=None):
         raise SystemExit("--reliability needs --l 1 and cannot be combined with --align yet")
     if args.align_reliability and (args.align == "none" or args.l != 1 or args.reliability):
         raise SystemExit("--align_reliability needs --align flips or --align d4 and --l 1, and cannot be combined with --reliability")
+    if args.window_reliability and (args.l == 1 or args.align != "none" or args.reliability or args.align_reliability):
+        raise SystemExit("--window_reliability needs --l 2 or --l 4 and cannot be combined with --align, --reliability or --align_reliability")
     keyring = load_keyring(args.keyring)
     keyring.packed()
     synthetic = X._no_checkpoint(args.model_id)

@@ -51,6 +51,23 @@ def _soft_wanted(args, l: int) -> bool:
     return True
 
 
+def _window_soft_wanted(args, l: int) -> int:
+    """--window_soft L as a number of levels (0: not asked for); the combinations it does not exist for are refused by name"""
+    levels = int(getattr(args, "window_soft", 0) or 0)
+    if not levels:
+        return 0
+    if not 1 <= levels <= codec.SOFT_MAX_LEVELS:
+        raise ValueError(f"--window_soft takes a number of levels in 1..{codec.SOFT_MAX_LEVELS}, got {levels}")
+    for flag in ("soft", "robust"):
+        if int(getattr(args, flag, 0) or 0):
+            raise ValueError(f"--window_soft cannot be combined with --{flag} 1: it is a vote of its own")
+    if getattr(args, "align", None) not in (None, "none"):
+        raise ValueError("--window_soft cannot be combined with --align: the alignment search reads the reference's vote")
+    if l == 1:
+        raise ValueError("--window_soft needs --l 2 or --l 4: at --l 1 the level-weighted vote is --soft 1")
+    return levels
+
+
 class _AlignedBits(str):
     """A recovered bit string that also says under which alignment of the lattice it was read (--align)"""
     alignment = None
@@ -64,6 +81,8 @@ def _align_wanted(args) -> bool:
     for flag in ("soft", "robust"):
         if int(getattr(args, flag, 0) or 0):
             raise ValueError(f"--align cannot be combined with --{flag} 1: the alignment search reads the reference's vote")
+    if int(getattr(args, "window_soft", 0) or 0):
+        raise ValueError("--window_soft cannot be combined with --align: the alignment search reads the reference's vote")
     if getattr(args, "tamper_map", None):
         raise ValueError("--align cannot be combined with --tamper_map")
     return True
@@ -96,7 +115,13 @@ def _alignment_note(r) -> str:
 
 def _vote(z, args, m: int, l: int):
     """(bits, flags) of the reference's vote, with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations), with
-    --soft 1 of the level-weighted vote (soft.extract_soft, thresholds scaled to each image's RMS)"""
+    --soft 1 of the level-weighted vote (soft.extract_soft, thresholds scaled to each image's RMS), with --window_soft L at --l 2 / 4 of the
+    vote with a level per cipher bit (soft.extract_soft_l, soft.window_thresholds)"""
+    window_levels = _window_soft_wanted(args, l)
+    if window_levels:
+        from . import soft
+        res = soft.extract_soft_l(z, args.key, args.nonce, m, l, levels=window_levels, clip=float(getattr(args, "soft_clip", 2.5)))
+        return res.bits, res.flags
     if _soft_wanted(args, l):
         from . import soft
         res = soft.extract_soft(z, args.key, args.nonce, m, levels=int(getattr(args, "soft_levels", 15)), clip=float(getattr(args, "soft_clip", 2.5)))
@@ -660,6 +685,10 @@ def build_parser():
                 self.error("--soft 1 cannot be combined with --robust 1: level weights and tile weights are separate votes")
             if a.soft and a.l != 1:
                 self.error(f"--soft 1 cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
+            if a.window_soft and (a.soft or a.robust or a.align != "none"):
+                self.error("--window_soft cannot be combined with --soft 1, --robust 1 or --align: it is a vote of its own")
+            if a.window_soft and a.l == 1:
+                self.error("--window_soft needs --l 2 or --l 4: at --l 1 the level-weighted vote is --soft 1")
             if a.align != "none" and (a.soft or a.robust or a.tamper_map):
                 self.error("--align cannot be combined with --soft 1, --robust 1 or --tamper_map: the alignment search reads the reference's vote")
             if a.align_shift < 0 or (a.align == "none" and a.align_shift):
@@ -696,6 +725,10 @@ def build_parser():
     parser.add_argument("--soft", type=int, choices=[0, 1], default=0,
                         help="(not a reference flag) 1: decode with the soft-decision vote (soft.extract_soft): every lattice element votes with a "
                              "reliability level taken from its magnitude; 0: the reference's vote.  Not with --robust 1, --l 1 only")
+    parser.add_argument("--window_soft", type=int, default=0, choices=range(0, 16), metavar="L",
+                        help="(not a reference flag) with --l 2 or 4: decode with the soft-decision vote for multi-bit windows (soft.extract_soft_l), every "
+                             "cipher bit of a lattice element votes with one of L (1..15) levels taken from its distance to the quantiser boundaries that "
+                             "would flip it; 0: the reference's vote.  Not with --soft 1, --robust 1 or --align")
     parser.add_argument("--soft_levels", type=int, default=15, choices=range(1, 16), metavar="LEVELS", help="(not a reference flag) reliability levels of --soft 1 (1..15)")
     parser.add_argument("--soft_clip", type=float, default=2.5,
                         help="(not a reference flag) --soft 1: the top level starts at this many times the image's RMS")

@@ -58,14 +58,25 @@ class GaussianShadingPipeline:
 
     # X2 + X3-X5 + X6 against each image's own record
     def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False, soft: bool = False,
-                       levels: int = 15, clip: float = 2.5):
+                       levels: int = 15, clip: float = 2.5, window_levels: Optional[int] = None):
         """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`.
         soft=True: the `codec.SoftVote` (bits, flags, matches, score, wsum, wsq) of `codec.extract_soft` instead, every element weighted by
-        one of `levels` reliability levels with thresholds scaled to its image's RMS (`soft.uniform_thresholds(z, levels, clip)`); l = 1 only."""
+        one of `levels` reliability levels with thresholds scaled to its image's RMS (`soft.uniform_thresholds(z, levels, clip)`); l = 1 only.
+        window_levels=L at the pipeline's l = 2 or 4: the `codec.SoftVote` of `codec.extract_soft_l`, every cipher bit weighted by one of L
+        levels (`soft.window_thresholds(z, l, L, clip)`); not with soft=True, and not at l = 1 (that is soft=True)."""
         if soft and self.l != 1:
             raise ValueError(f"soft=True cannot be combined with l = {self.l}: reliability levels are defined for one cipher bit per element")
+        if window_levels is not None:
+            if soft:
+                raise ValueError("window_levels cannot be combined with soft=True: soft=True is the l = 1 form of the vote")
+            if self.l == 1:
+                raise ValueError("window_levels needs a pipeline with l = 2 or 4: at l = 1 the level-weighted vote is soft=True")
+            from . import soft as S
+            window_levels = S._check_table(window_levels, clip)[0]
         z = ddim_invert(self.eps_model, x0, self._uncond(x0.shape[0]), self.schedule)
-        if soft:
+        if window_levels is not None:
+            res = codec.extract_soft_l(z, records, msg_bytes, S.window_thresholds(z, self.l, window_levels, clip), self.l)
+        elif soft:
             from . import soft as S
             res = codec.extract_soft(z, records, msg_bytes, S.uniform_thresholds(z, levels, clip))
         else:

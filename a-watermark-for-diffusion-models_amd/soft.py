@@ -6,6 +6,10 @@ same.  `codec.extract_soft` (gsw_extract_soft, one launch) weights element j by 
 0..levels, so the result is exact in every dtype and independent of the order of summation.  This module holds the threshold tables
 (`uniform_thresholds`: scaled to the image's own RMS, needs no noise estimate; `llr_thresholds`: calibrated to a known noise level), the
 shared-key convenience `extract_soft` and the significance bound of a level-weighted score (`log10_p`).
+
+Multi-bit windows (l = 2, 4): `codec.extract_soft_l` gives every cipher BIT of an element a level, the element's distance from the
+nearest quantiser boundary at which that bit would have come out differently, counted against a table per window bit (`window_thresholds`);
+`extract_soft_l` is the shared-key convenience, and `log10_p` bounds its score as it stands (the coins are now per cipher bit).
 """
 from __future__ import annotations
 
@@ -42,6 +46,35 @@ def uniform_thresholds(z: torch.Tensor, levels: int = 15, clip: float = 2.5) -> 
     rms = torch.sqrt(sq / ok.sum(dim=1).clamp(min=1).to(torch.float32))
     steps = (torch.arange(1, levels + 1, dtype=torch.float32, device=zf.device) - 0.5) * (clip / levels)
     return (rms[:, None] * steps[None, :]).contiguous()
+
+
+def window_gaps(l: int) -> list:
+    """g_w for w = 0 .. l-1: the largest gap between neighbouring flip boundaries of window bit w, T_(i+s) - T_i over the boundaries
+    T_i = codec.quant_thresholds(l)[i-1] with s = 2**(l-1-w) dividing i; inf for w = 0, whose only flip boundary is the median."""
+    T = codec.quant_thresholds(l)
+    out = []
+    for w in range(l):
+        s = 1 << (l - 1 - w)
+        flips = [float(T[i - 1]) for i in range(s, 1 << l, s)]
+        out.append(max((b - a for a, b in zip(flips, flips[1:])), default=math.inf))
+    return out
+
+
+def window_thresholds(z: torch.Tensor, l: int, levels: int = 15, clip: float = 2.5) -> torch.Tensor:
+    """float32 [B, l, levels] on z's device, the table of `codec.extract_soft_l`: per image and window bit w,
+    t[w][i] = (i - 1/2) c_w / levels for i = 1..levels.  c_0 = clip rms (the first bit has one flip boundary, the median, and behaves as at
+    l = 1; rms as `uniform_thresholds`); for w > 0 c_w = min(clip rms, g_w / 2), g_w = `window_gaps(l)[w]`: an element cannot be further
+    than half the widest gap from both of its flip boundaries, so a wider table would leave its top levels to the two tails alone."""
+    levels, clip = _check_table(levels, clip)
+    l = codec.check_window(l)
+    span = uniform_thresholds(z, levels, clip)                       # [B, levels]: (i - 1/2) clip rms / levels
+    top = span[:, -1:] * (levels / (levels - 0.5))                    # clip rms
+    steps = (torch.arange(1, levels + 1, dtype=torch.float32, device=span.device) - 0.5) / levels
+    rows = [span]
+    for g in window_gaps(l)[1:]:
+        c = torch.clamp(top, max=g / 2.0)
+        rows.append(c * steps[None, :])
+    return torch.stack(rows, dim=1).contiguous()
 
 
 def _log_erfc(u: float) -> float:
@@ -109,6 +142,25 @@ def extract_soft(latents: torch.Tensor, key: bytes, nonce: bytes, message_length
         thresholds = thresholds.to(z.device)
     records = shared_records(key, nonce, M // 8, z.shape[0], z.device)
     return codec.extract_soft(z, records, M // 8, thresholds)._replace(matches=None)
+
+
+def extract_soft_l(latents: torch.Tensor, key: bytes, nonce: bytes, message_length: int, l: int, *, levels: int = 15, clip: float = 2.5,
+                   thresholds: Optional[torch.Tensor] = None) -> codec.SoftVote:
+    """`codec.extract_soft_l` for a batch under ONE key and nonce, as `extract_soft` is for l = 1 (to which l = 1 delegates, bit for bit).
+    thresholds: float32 [l, levels] or [B, l, levels]; None: `window_thresholds(latents, l, levels, clip)`."""
+    l = codec.check_window(l)
+    if l == 1:
+        return extract_soft(latents, key, nonce, message_length, levels=levels, clip=clip, thresholds=thresholds)
+    M = int(message_length)
+    if M < 8 or M % 8 or M > 8 * codec.N.GSW_MSG_INLINE_MAX:
+        raise ValueError(f"the soft vote needs a message_length that is a multiple of 8 in 8..{8 * codec.N.GSW_MSG_INLINE_MAX}, got {message_length!r}")
+    z = latents
+    if thresholds is None:
+        thresholds = window_thresholds(z, l, levels, clip)
+    else:
+        thresholds = thresholds.to(z.device)
+    records = shared_records(key, nonce, M // 8, z.shape[0], z.device)
+    return codec.extract_soft_l(z, records, M // 8, thresholds, l)._replace(matches=None)
 
 
 def log10_p(score_total, wsq) -> float:

@@ -40,6 +40,10 @@ by s = sum_j level_j (1 - 2 (h_j XOR e_j)) -- for records of one key the number 
 key-independent image under any key are fair coins, so the Hoeffding bound `soft.log10_p(s, sum level^2)` holds across keys as it does
 within one.
 
+The same at l = 2 and 4 (`trace_latents_keyed_soft_l`, `--per_record_keys --window_reliability T --l 2|4`): every cipher BIT of an element carries
+a level, its element's distance from the nearest quantiser boundary that would flip it (`codec.level_pack_l`); the search and the bound are the
+ones above over the n l bits.
+
 Where (`tamper_tile=`, `--tamper_map DIR`): an attributed image can also be asked WHERE it still carries the record's watermark --
 `TraceResult.tamper`, the per-tile agreement with the attributed record's codeword (`tamper.TamperMap`, one `codec.tile_agreement` launch more
 per batch).  The record comes from the registry, not from the image, so each tile's count has the exact binomial null as well.
@@ -807,6 +811,57 @@ def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 
     return out
 
 
+def trace_latents_keyed_soft_l(latents, registry: KeyedRegistry, l: int, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
+                               fpr: float = 1e-6) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed_soft` for multi-bit windows (l = 2 or 4): latents [B, ...] on the device -> one TraceResult
+    per image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
+
+    Every one of the n l cipher bits of an image votes with an integer level 0..levels, the distance of its element from the nearest
+    quantiser boundary at which that bit would have come out differently -- thresholds: float32 [l, levels] or [B, l, levels], None:
+    `soft.window_thresholds(latents, l, levels, clip)`.  One `codec.level_pack_l` launch, then the unchanged `codec.trace_keyed_soft_topk`
+    with n_bits = n l.  The p-value is the Hoeffding bound `soft.log10_p(score, wsq)`, Bonferroni over the records: given the levels, the
+    decrypted bits of a key-independent image are independent fair coins, now per cipher bit, so the bound holds as at l = 1.
+    `Candidate.agree` counts the bits of the soft vote under the candidate's own record: one `codec.extract_soft_l` launch over the
+    reported (image, candidate) pairs.  n l (1 + P) may not exceed 1 048 576, P the bit length of `levels`: the search refuses beyond
+    (ValueError).  l = 1 is refused: that is `trace_latents_keyed_soft`."""
+    import torch
+    from . import soft as S
+    l = codec.check_window(l)
+    if l == 1:
+        raise ValueError("l = 1 has no window bits: the level-weighted search across keys at l = 1 is trace_latents_keyed_soft (--keyed_reliability)")
+    limit = _log10_fpr(fpr)
+    z = latents.contiguous()
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    M, mb = registry.message_bits, registry.message_bytes
+    codec.vote_copies(n, M, l)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    nb = n * l
+    if thresholds is None:
+        thr = S.window_thresholds(z, l, levels, clip)
+    else:
+        thr = thresholds.to(device=z.device, dtype=torch.float32).contiguous()
+    rec_dev = registry.to_device(z.device)
+    rows = codec.level_pack_l(z, thr, l)
+    idx, score = codec.trace_keyed_soft_topk(rows, nb, rec_dev, mb, k=k)
+    idx_h, score_h = _pairs_to_host(idx, score)
+    flags_h, wsq_h, U = rows.flags.cpu().numpy(), rows.wsq.cpu().numpy(), len(registry)
+    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+
+    def candidate(b, j, i, s):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U))
+        reported.append((b, c))
+        return c
+
+    out = _candidate_lists(idx_h, score_h, flags_h, limit, candidate, _trace_result)
+    if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
+        img = torch.tensor([b for b, _ in reported], device=z.device)
+        rec = torch.tensor([c.index for _, c in reported], device=z.device)
+        vote = codec.extract_soft_l(z.reshape(B, -1)[img].contiguous(), rec_dev[rec].contiguous(), mb, thr if thr.dim() == 2 else thr[img].contiguous(), l)
+        for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
+            c.agree = int(a)
+    return out
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result, message_length: int) -> str:
     """One line of trace.txt / stdout"""
@@ -839,6 +894,17 @@ def build_parser():
                     self.error("--keyed_reliability cannot be combined with --reliability: --reliability is the shared-key form of the same statistic")
                 if a.l != 1:
                     self.error(f"--keyed_reliability cannot be combined with --l {a.l}: reliability levels are defined for one cipher bit per element (--l 1)")
+            if a.window_reliability is not None:
+                if not a.per_record_keys:
+                    self.error("--window_reliability requires --per_record_keys: it ranks a registry whose records carry their own keys")
+                if a.l == 1:
+                    self.error("--window_reliability needs --l 2 or --l 4: at --l 1 the level-weighted search across keys is --keyed_reliability")
+                if a.hard:
+                    self.error("--window_reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
+                if a.reliability is not None or a.keyed_reliability is not None:
+                    self.error("--window_reliability cannot be combined with --reliability or --keyed_reliability: those are the --l 1 forms of the statistic")
+                if a.tamper_map:
+                    self.error("--window_reliability cannot be combined with --tamper_map")
             if a.reliability is not None:
                 if a.hard:
                     self.error("--reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
@@ -879,6 +945,10 @@ def build_parser():
     p.add_argument("--keyed_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
                    help="with --per_record_keys: rank by level-weighted margins across keys, LEVELS (1..15) reliability levels per lattice element, "
                         "the p-value is a Hoeffding bound (--l 1, not with --hard or --reliability)")
+    p.add_argument("--window_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
+                   help="with --per_record_keys and --l 2 or 4: rank by level-weighted margins across keys, every cipher bit of a lattice element "
+                        "votes with one of LEVELS (1..15) levels taken from its distance to the quantiser boundaries that would flip it, the p-value is "
+                        "a Hoeffding bound (not with --hard, --reliability, --keyed_reliability or --tamper_map)")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -916,6 +986,8 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
         if trace_batch is not None:
             return trace_batch(latents)
         tile = args.tile if getattr(args, "tamper_map", None) else None
+        if args.per_record_keys and getattr(args, "window_reliability", None) is not None:
+            return trace_latents_keyed_soft_l(latents, registry, args.l, levels=args.window_reliability, k=args.top, fpr=args.fpr)
         if args.per_record_keys and getattr(args, "keyed_reliability", None) is not None:
             return trace_latents_keyed_soft(latents, registry, levels=args.keyed_reliability, k=args.top, fpr=args.fpr, tamper_tile=tile)
         if args.per_record_keys:
@@ -951,6 +1023,8 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
 def _statistic_name(args) -> str:
     """the `statistic` field of trace.txt's header"""
     levels = args.reliability if args.reliability is not None else getattr(args, "keyed_reliability", None)
+    if levels is None and getattr(args, "window_reliability", None) is not None:
+        return f"soft, {args.window_reliability} reliability levels per window bit"
     return "hard" if args.hard else "soft" if levels is None else f"soft, {levels} reliability levels"
 
 

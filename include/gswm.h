@@ -698,6 +698,48 @@ int gsw_trace_keyed_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_de
                               int32_t* score_dev, void* workspace_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Soft-decision vote for multi-bit windows, l = 2 or 4: every CIPHER BIT of a lattice element votes with an
+ * integer reliability level, its distance from the nearest quantiser boundary at which that bit would have come out differently.
+ * Additive: gsw_version() stays 500.
+ *
+ *   Element e of image b holds z (Z = z widened exactly to fp64) and y = #{ j : z >= T_j }, gsw_extract_l's window (T_1 .. T_(2^l - 1)
+ *   the quantiser's fp64 thresholds; NaN: 0 + GSW_FLAG_NAN, z >= the saturation point: all ones + GSW_FLAG_SATURATED).  Window bit w
+ *   (0 = first = MSB of y, cipher position e l + w) has the value s = 2^(l-1-w) in y and flips exactly at the boundaries T_i with s | i.
+ *   a = (y / s) s is the nearest flip boundary at or below z (none if a == 0), c = a + s the nearest above (none if c == 2^l).
+ *   thr_dev     : float [B, thr_stride] (thr_stride >= l levels, in floats) or, with thr_stride == 0, one table for all images; a table is
+ *                 [l][levels], row w for window bit w; levels is 1..15.  With t_i = (double)thr[b][w][i]:
+ *   level(e, w) = #{ i < levels : (a == 0 or Z >= fl64(T_a + t_i)) and (c == 2^l or Z <= fl64(T_c - t_i)) }, sums and differences formed
+ *                 in fp64 (round to nearest), compares in fp64: an exact function of the stored bits in every dtype.  NaN z gives level
+ *                 0, a NaN threshold never counts, +-inf gives `levels` for finite thresholds; the order of a row does not matter.
+ *   p           = (bit w of y) ^ keystream bit (e l + w) of record b (gsw_extract_keyed's rows and keystream), t = (e l + w) mod M, M = 8 msg_bytes
+ *   score_dev   : int32 [B, M] (NULL ok), score[b, t] = sum of level (2 p - 1)         wsum_dev : int32 [B, M] (NULL ok), the same sum of level
+ *   wsq_dev     : int32 [B] (NULL ok), sum of level^2 over all n_elems l bits
+ *   bits_dev, matches_dev, flags_dev : as gsw_extract_soft (MSB first, bit t = (score > 0), a tie or no weight gives 0)
+ * With levels = 1 and thr = 0 every bit of a non-NaN element has level 1: on NaN-free images score = 2 counts - copies of
+ * gsw_extract_keyed at that l and the bits are its bits.
+ *
+ * gsw_level_pack_l: the same levels without a key, the operands of gsw_trace_keyed_soft_topk and gsw_key_search_soft_topk with
+ * n_bits = Nb = n_elems l.  P = bit length of levels (1 .. 4).
+ *   signs_dev  : uint8 [B, Nb / 8], bit for bit gsw_quant_pack's row
+ *   planes_dev : uint8 [B, P, Nb / 8], bit e l + w of plane k = bit k of level(e, w), packed MSB first
+ *   wsum_dev   : int32 [B], sum of the levels over the image's Nb bits          wsq_dev : int32 [B], sum of their squares
+ *   flags_dev  : uint32 [B], as gsw_quant_pack
+ * Both: one launch, one workgroup per image; every output element is written, no atomics, no workspace, nothing to zero first; the results
+ * are exact integers and do not depend on the launch geometry.
+ * GSW_ERR_BAD_ARG: l other than 2 or 4, null pointer (score_dev, wsum_dev, wsq_dev, matches_dev of gsw_extract_soft_l excepted), B < 1,
+ * msg_bytes outside 1..256, a bad stride or alignment of records_dev, z_dev not 16-byte aligned, thr_dev not 4-byte aligned, thr_stride
+ * neither 0 nor >= l levels, levels outside 1..15, unknown dtype, n_elems < 1.
+ * GSW_ERR_UNSUPPORTED: n_elems % 8 != 0 or n_elems l > 1 048 576 (one image's keystream is staged in 128 KiB of LDS).
+ * GSW_ERR_RAGGED (gsw_extract_soft_l): n_elems l % (8 msg_bytes) != 0. */
+int gsw_extract_soft_l(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes,
+                       const float* thr_dev, int64_t thr_stride /* floats; 0: one table for all images */, int levels, int l,
+                       uint8_t* bits_dev, int32_t* score_dev /* NULL ok */, int32_t* wsum_dev /* NULL ok */, int32_t* wsq_dev /* NULL ok */,
+                       uint32_t* flags_dev, uint32_t* matches_dev /* NULL ok */, int B, int64_t n_elems, void* stream);
+int gsw_level_pack_l(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride /* floats; 0: one table for all images */, int levels,
+                     int l, uint8_t* signs_dev, uint8_t* planes_dev, int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int B,
+                     int64_t n_elems, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Blind key search: which keys of a keyring does an image carry a watermark under, whatever the message.
  * Additive: gsw_version() stays 500.
  *
