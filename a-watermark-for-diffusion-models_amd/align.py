@@ -186,40 +186,52 @@ def _device_table(aligns: Sequence[Alignment], shape, device) -> torch.Tensor:
     return t
 
 
+def _search_chunks(B: int, per_image: int, table: torch.Tensor, keys_dev: torch.Tensor, k: int, budget_bytes: Optional[int], take, search, **merge_best):
+    """The cuts and the merge of the two searches.  per_image: bytes of ONE aligned image; merge_best: `_merge_best`'s stat_bits where its default (the sign statistic's) is too few; table: the int32 [A, 3] alignments on the
+    device; take(b0, b1) -> the packed operand of images b0:b1; search(operand, table[a0:a1]) -> (idx, stat) int32 [nb (a1 - a0), k] of `codec.key_search_topk` /
+    `codec.key_search_soft_topk` on that operand's aligned rows, image-major."""
+    A = table.shape[0]
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise ValueError("k must be in 1..8")
+    budget = int(ROWS_BUDGET_BYTES if budget_bytes is None else budget_bytes)
+    a_step = max(1, min(A, SEARCH_MAX_ROWS, budget // per_image))                          # alignments per launch (all of them unless one image's rows pass the budget)
+    b_step = max(1, min(B, SEARCH_MAX_ROWS // a_step, budget // (a_step * per_image)))     # images per launch
+    join = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, 1)
+    outs = []
+    for b0 in range(0, B, b_step):
+        nb = min(b_step, B - b0)
+        operand = take(b0, b0 + nb)
+        keys, stats = [], []
+        for a0 in range(0, A, a_step):
+            na = min(a_step, A - a0)
+            idx, stat = search(operand, table[a0:a0 + na])
+            keys.append(idx.view(nb, na * k))
+            stats.append(stat.view(nb, na * k))
+        best = _merge_best(join(keys), join(stats), keys_dev.shape[0], **merge_best) if k == 1 else None
+        if best is None:
+            als = torch.arange(A, dtype=torch.int32, device=table.device).repeat_interleave(k).expand(nb, A * k)
+            best = _merge(join(keys), join(stats), als, k)
+        outs.append(best)
+    return outs[0] if len(outs) == 1 else tuple(torch.cat([o[i] for o in outs]) for i in range(3))
+
+
 def _search_packed(packed: torch.Tensor, shape, l: int, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], k: int,
                    budget_bytes: Optional[int] = None):
     """`search_keys` from the packed rows on: packed uint8 [B, rowbytes] of a [C, H, W] lattice at l bits per element"""
     shape = tuple(int(s) for s in shape)
     table = _device_table(aligns, shape, packed.device)
-    A = table.shape[0]
     B, rowbytes = packed.shape
-    n_bits = rowbytes * 8
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("k must be in 1..8")
-    budget = int(ROWS_BUDGET_BYTES if budget_bytes is None else budget_bytes)
-    a_step = max(1, min(A, SEARCH_MAX_ROWS, budget // rowbytes))                           # alignments per launch (all of them unless one image's rows pass the budget)
-    b_step = max(1, min(B, SEARCH_MAX_ROWS // a_step, budget // (a_step * rowbytes)))      # images per launch
-    join = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, 1)
-    outs = []
-    for b0 in range(0, B, b_step):
-        rows_b = packed[b0:b0 + b_step]
-        if rows_b.data_ptr() % 16:
-            rows_b = rows_b.clone()
-        nb = rows_b.shape[0]
-        keys, stats = [], []
-        for a0 in range(0, A, a_step):
-            na = min(a_step, A - a0)
-            rows = codec._rows_align_launch(rows_b, shape, l, table[a0:a0 + na])
-            idx, stat = codec.key_search_topk(rows.view(nb * na, rowbytes), n_bits, keys_dev, msg_bytes, k=k)
-            keys.append(idx.view(nb, na * k))
-            stats.append(stat.view(nb, na * k))
-        best = _merge_best(join(keys), join(stats), keys_dev.shape[0]) if k == 1 else None
-        if best is None:
-            als = torch.arange(A, dtype=torch.int32, device=packed.device).repeat_interleave(k).expand(nb, A * k)
-            best = _merge(join(keys), join(stats), als, k)
-        outs.append(best)
-    return outs[0] if len(outs) == 1 else tuple(torch.cat([o[i] for o in outs]) for i in range(3))
+
+    def take(b0, b1):
+        rows_b = packed[b0:b1]
+        return rows_b.clone() if rows_b.data_ptr() % 16 else rows_b
+
+    def search(rows_b, aligns_dev):
+        rows = codec._rows_align_launch(rows_b, shape, l, aligns_dev)
+        return codec.key_search_topk(rows.view(-1, rowbytes), rowbytes * 8, keys_dev, msg_bytes, k=int(k))
+
+    return _search_chunks(B, rowbytes, table, keys_dev, k, budget_bytes, take, search)
 
 
 def search_keys(latents: torch.Tensor, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], *, l: int = 1, k: int = 1,
@@ -247,36 +259,16 @@ def _search_level_rows(rows: "codec.LevelRows", shape, keys_dev: torch.Tensor, m
     """`search_keys_soft` from `codec.level_pack`'s rows on: `_search_packed` with 1 + P rows per aligned image"""
     shape = tuple(int(s) for s in shape)
     table = _device_table(aligns, shape, rows.signs.device)
-    A = table.shape[0]
     B, rowbytes = rows.signs.shape
     P = rows.planes.shape[1]
-    n_bits = rowbytes * 8
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("k must be in 1..8")
-    budget = int(ROWS_BUDGET_BYTES if budget_bytes is None else budget_bytes)
-    per_row = (1 + P) * rowbytes                                                            # an aligned image: its sign row and its P planes
-    a_step = max(1, min(A, SEARCH_MAX_ROWS, budget // per_row))                             # alignments per launch (all of them unless one image's rows pass the budget)
-    b_step = max(1, min(B, SEARCH_MAX_ROWS // a_step, budget // (a_step * per_row)))        # images per launch
-    join = lambda ts: ts[0] if len(ts) == 1 else torch.cat(ts, 1)
-    outs = []
-    for b0 in range(0, B, b_step):
-        rows_b = codec.LevelRows(*(t[b0:b0 + b_step] for t in rows))
-        nb = rows_b.signs.shape[0]
-        keys, stats = [], []
-        for a0 in range(0, A, a_step):
-            na = min(a_step, A - a0)
-            signs, planes = codec._level_rows_align_launch(rows_b, shape, table[a0:a0 + na])
-            al = codec.LevelRows(signs.view(nb * na, rowbytes), planes.view(nb * na, P, rowbytes), rows_b.wsum, rows_b.wsq, rows_b.flags)   # (the search reads signs and planes alone)
-            idx, stat = codec.key_search_soft_topk(al, n_bits, keys_dev, msg_bytes, k=k)
-            keys.append(idx.view(nb, na * k))
-            stats.append(stat.view(nb, na * k))
-        best = _merge_best(join(keys), join(stats), keys_dev.shape[0], SOFT_STAT_BITS) if k == 1 else None
-        if best is None:
-            als = torch.arange(A, dtype=torch.int32, device=rows.signs.device).repeat_interleave(k).expand(nb, A * k)
-            best = _merge(join(keys), join(stats), als, k)
-        outs.append(best)
-    return outs[0] if len(outs) == 1 else tuple(torch.cat([o[i] for o in outs]) for i in range(3))
+
+    def search(rows_b, aligns_dev):
+        signs, planes = codec._level_rows_align_launch(rows_b, shape, aligns_dev)
+        al = codec.LevelRows(signs.view(-1, rowbytes), planes.view(-1, P, rowbytes), rows_b.wsum, rows_b.wsq, rows_b.flags)   # (the search reads signs and planes alone)
+        return codec.key_search_soft_topk(al, rowbytes * 8, keys_dev, msg_bytes, k=int(k))
+
+    return _search_chunks(B, (1 + P) * rowbytes, table, keys_dev, k, budget_bytes,
+                          lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in rows)), search, stat_bits=SOFT_STAT_BITS)         # an aligned image: its sign row and its P planes
 
 
 def search_keys_soft(latents: torch.Tensor, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], *, levels: int = 15,

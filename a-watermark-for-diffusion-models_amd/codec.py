@@ -580,7 +580,7 @@ def extract_records(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, l
     return (bits, flags, matches, counts) if return_counts else (bits, flags, matches)
 
 
-# ------------------------------------------------------------------------------------------------ soft-decision vote (reliability levels)
+# ------------------------------------------------------------------------------------------------ soft-decision vote and level rows (reliability levels; l = 1, 2, 4)
 SOFT_MAX_LEVELS = 15
 
 
@@ -594,45 +594,6 @@ class SoftVote(NamedTuple):
     wsq: torch.Tensor       # int32 [B], sum of level^2 over the image
 
 
-def extract_soft(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresholds: torch.Tensor) -> SoftVote:
-    """The soft-decision vote of every image under its OWN record, in one launch (gsw_extract_soft, l = 1): element j votes for its
-    decrypted bit with the integer weight level_j = #{ i : |z_j| >= thresholds[b][i] }.
-
-    z: latents [B, ...] (fp16 / bf16 / fp32 / fp64), records: as `extract_records`, thresholds: float32 [levels] (one table for all images)
-    or [B, levels] on z's device, levels in 1..15 (`soft.uniform_thresholds`, `soft.llr_thresholds`).  The comparison is exact in every
-    dtype (fp32 after an exact widening; fp64 against the thresholds widened to fp64); a NaN has level 0.  With thresholds = [0] on
-    NaN-free images the bits are `extract_records`' bits and score = 2 counts - copies.  Lattice limits and IndexError as `extract_records`."""
-    B, stride, msg_bytes = _records_operand(records, msg_bytes)
-    _need_gpu(z, "z")
-    _same_device(records, z, "records")
-    if z.dim() < 2 or z.shape[0] != B:
-        raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
-    _need_gpu(thresholds, "thresholds")
-    _same_device(thresholds, z, "thresholds")
-    if thresholds.dtype != torch.float32 or thresholds.dim() not in (1, 2) or (thresholds.dim() == 2 and thresholds.shape[0] != B):
-        raise ValueError(f"thresholds must be float32 [levels] or [{B}, levels]")
-    levels = thresholds.shape[-1]
-    if not 1 <= levels <= SOFT_MAX_LEVELS:
-        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
-    dt = _dt(z.dtype)
-    n = z.numel() // B
-    if n < 1 or n % 8 or n > ROW_MAX_BITS:
-        raise ValueError(f"a lattice of {n} elements must fill whole bytes and hold at most {ROW_MAX_BITS} bits")
-    M = 8 * msg_bytes
-    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
-    matches = torch.empty((B,), dtype=torch.int32, device=z.device)
-    score = torch.empty((B, M), dtype=torch.int32, device=z.device)
-    wsum = torch.empty((B, M), dtype=torch.int32, device=z.device)
-    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
-    with torch.cuda.device(z.device):
-        N.check(N.lib().gsw_extract_soft(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, thresholds.data_ptr(),
-                                         levels if thresholds.dim() == 2 else 0, levels, bits.data_ptr(), score.data_ptr(), wsum.data_ptr(),
-                                         wsq.data_ptr(), flags.data_ptr(), matches.data_ptr(), B, n, _stream_ptr()))
-    return SoftVote(bits, flags, matches, score, wsum, wsq)
-
-
-# ------------------------------------------------------------------------------------------------ level-weighted keyed search
 class LevelRows(NamedTuple):
     """What `level_pack` returns, all on z's device: the operands of `trace_keyed_soft_topk`"""
     signs: torch.Tensor     # uint8 [B, n/8], `sign_pack`'s row
@@ -649,58 +610,101 @@ def level_planes(levels: int) -> int:
     return int(levels).bit_length()
 
 
+def _level_table(thresholds: torch.Tensor, z: torch.Tensor, B: int, l: int) -> Tuple[int, int]:
+    """The checks the votes and the packers share on the threshold table -> (levels, the stride between the images' tables in floats, 0 for one table for all).
+    l = 1: [levels] or [B, levels]; l = 2, 4: a row per window bit, [l, levels] or [B, l, levels]."""
+    _need_gpu(thresholds, "thresholds")
+    _same_device(thresholds, z, "thresholds")
+    own = thresholds.dim() - (2 if l > 1 else 1)                    # 0: one table for all, 1: a table per image
+    if (thresholds.dtype != torch.float32 or own not in (0, 1) or (l > 1 and thresholds.shape[-2] != l) or (own == 1 and thresholds.shape[0] != B)):
+        rows = "levels" if l == 1 else f"{l}, levels"
+        raise ValueError(f"thresholds must be float32 [{rows}] or [{B}, {rows}]")
+    levels = thresholds.shape[-1]
+    if not 1 <= levels <= SOFT_MAX_LEVELS:
+        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
+    return levels, own * l * levels
+
+
+def _soft_vote(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresholds: torch.Tensor, l: int) -> SoftVote:
+    """`extract_soft` (l = 1) and `extract_soft_l` (l = 2, 4): the operand checks, the outputs and the launch"""
+    B, stride, msg_bytes = _records_operand(records, msg_bytes)
+    _need_gpu(z, "z")
+    _same_device(records, z, "records")
+    if z.dim() < 2 or z.shape[0] != B:
+        raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
+    levels, thr_stride = _level_table(thresholds, z, B, l)
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 1 or n % 8 or n * l > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {n} elements must fill whole bytes and hold at most {ROW_MAX_BITS} bits" if l == 1 else
+                         f"a lattice of {n} elements at l = {l} must be a multiple of 8 elements and hold at most {ROW_MAX_BITS} bits")
+    M, dev = 8 * msg_bytes, z.device                                # (z.device builds an object per read)
+    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    matches = torch.empty((B,), dtype=torch.int32, device=dev)
+    score = torch.empty((B, M), dtype=torch.int32, device=dev)
+    wsum = torch.empty((B, M), dtype=torch.int32, device=dev)
+    wsq = torch.empty((B,), dtype=torch.int32, device=dev)
+    window = () if l == 1 else (l,)                                 # gsw_extract_soft_l takes l after levels, gsw_extract_soft has no such argument
+    with torch.cuda.device(dev):
+        launch = N.lib().gsw_extract_soft if l == 1 else N.lib().gsw_extract_soft_l
+        N.check(launch(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, thresholds.data_ptr(), thr_stride, levels, *window, bits.data_ptr(),
+                       score.data_ptr(), wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), matches.data_ptr(), B, n, _stream_ptr()))
+    return SoftVote(bits, flags, matches, score, wsum, wsq)
+
+
+def _level_rows(z: torch.Tensor, thresholds: torch.Tensor, l: int) -> LevelRows:
+    """`level_pack` (l = 1) and `level_pack_l` (l = 2, 4): the operand checks, the outputs and the launch"""
+    _need_gpu(z, "z")
+    if z.dim() < 2 or z.shape[0] < 1:
+        raise ValueError("z must be [B, ...] with at least one image")
+    B = z.shape[0]
+    levels, thr_stride = _level_table(thresholds, z, B, l)
+    dt = _dt(z.dtype)
+    n = z.numel() // B
+    if n < 8 or n % 8 or n * l > ROW_MAX_BITS:
+        raise ValueError(f"level_pack needs a lattice of a multiple of 8 elements per image, at most {ROW_MAX_BITS} (got {n})" if l == 1 else
+                         f"level_pack_l needs a lattice of a multiple of 8 elements per image and at most {ROW_MAX_BITS} bits (got {n} at l = {l})")
+    P = level_planes(levels)
+    nbytes, dev = n * l // 8, z.device
+    signs = torch.empty((B, nbytes), dtype=torch.uint8, device=dev)
+    planes = torch.empty((B, P, nbytes), dtype=torch.uint8, device=dev)
+    wsum = torch.empty((B,), dtype=torch.int32, device=dev)
+    wsq = torch.empty((B,), dtype=torch.int32, device=dev)
+    flags = torch.empty((B,), dtype=torch.int32, device=dev)
+    window = () if l == 1 else (l,)
+    with torch.cuda.device(dev):
+        launch = N.lib().gsw_level_pack if l == 1 else N.lib().gsw_level_pack_l
+        N.check(launch(z.data_ptr(), dt, thresholds.data_ptr(), thr_stride, levels, *window, signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(),
+                       wsq.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
+    return LevelRows(signs, planes, wsum, wsq, flags)
+
+
+def extract_soft(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresholds: torch.Tensor) -> SoftVote:
+    """The soft-decision vote of every image under its OWN record, in one launch (gsw_extract_soft, l = 1): element j votes for its
+    decrypted bit with the integer weight level_j = #{ i : |z_j| >= thresholds[b][i] }.
+
+    z: latents [B, ...] (fp16 / bf16 / fp32 / fp64), records: as `extract_records`, thresholds: float32 [levels] (one table for all images)
+    or [B, levels] on z's device, levels in 1..15 (`soft.uniform_thresholds`, `soft.llr_thresholds`).  The comparison is exact in every
+    dtype (fp32 after an exact widening; fp64 against the thresholds widened to fp64); a NaN has level 0.  With thresholds = [0] on
+    NaN-free images the bits are `extract_records`' bits and score = 2 counts - copies.  Lattice limits and IndexError as `extract_records`."""
+    return _soft_vote(z, records, msg_bytes, thresholds, 1)
+
+
 def level_pack(z: torch.Tensor, thresholds: torch.Tensor) -> LevelRows:
     """Quantise and pack latents z [B, ...] (fp16/bf16/fp32/fp64) once for the level-weighted keyed search, in one launch (gsw_level_pack):
     the sign row of `sign_pack` bit for bit, the reliability level of every element -- `extract_soft`'s level_j = #{ i : |z_j| >=
     thresholds[b][i] }, same exact comparison, NaN -> 0 -- as P bit planes, and the image's sum of levels and of squared levels.
     thresholds: float32 [levels] or [B, levels] on z's device, levels in 1..15.  n must be a multiple of 8 and at most 1 048 576."""
-    _need_gpu(z, "z")
-    if z.dim() < 2 or z.shape[0] < 1:
-        raise ValueError("z must be [B, ...] with at least one image")
-    B = z.shape[0]
-    _need_gpu(thresholds, "thresholds")
-    _same_device(thresholds, z, "thresholds")
-    if thresholds.dtype != torch.float32 or thresholds.dim() not in (1, 2) or (thresholds.dim() == 2 and thresholds.shape[0] != B):
-        raise ValueError(f"thresholds must be float32 [levels] or [{B}, levels]")
-    levels = thresholds.shape[-1]
-    if not 1 <= levels <= SOFT_MAX_LEVELS:
-        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
-    dt = _dt(z.dtype)
-    n = z.numel() // B
-    if n < 8 or n % 8 or n > ROW_MAX_BITS:
-        raise ValueError(f"level_pack needs a lattice of a multiple of 8 elements per image, at most {ROW_MAX_BITS} (got {n})")
-    P = level_planes(levels)
-    signs = torch.empty((B, n // 8), dtype=torch.uint8, device=z.device)
-    planes = torch.empty((B, P, n // 8), dtype=torch.uint8, device=z.device)
-    wsum = torch.empty((B,), dtype=torch.int32, device=z.device)
-    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
-    with torch.cuda.device(z.device):
-        N.check(N.lib().gsw_level_pack(z.data_ptr(), dt, thresholds.data_ptr(), levels if thresholds.dim() == 2 else 0, levels, signs.data_ptr(),
-                                       planes.data_ptr(), wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
-    return LevelRows(signs, planes, wsum, wsq, flags)
+    return _level_rows(z, thresholds, 1)
 
 
-# ------------------------------------------------------------------------------------------------ soft-decision vote, multi-bit windows (l = 2, 4)
 def _multi_bit_window(l, twin: str) -> int:
     """l as 2 or 4; l = 1 is refused with a pointer to the l = 1 function"""
     l = check_window(l)
     if l == 1:
         raise ValueError(f"l = 1 has one cipher bit per element and no window bits: use `{twin}`")
     return l
-
-
-def _window_table(thresholds: torch.Tensor, z: torch.Tensor, B: int, l: int) -> int:
-    """The checks `extract_soft_l` and `level_pack_l` share on the per-window-bit table -> levels"""
-    _need_gpu(thresholds, "thresholds")
-    _same_device(thresholds, z, "thresholds")
-    if (thresholds.dtype != torch.float32 or thresholds.dim() not in (2, 3) or thresholds.shape[-2] != l
-            or (thresholds.dim() == 3 and thresholds.shape[0] != B)):
-        raise ValueError(f"thresholds must be float32 [{l}, levels] or [{B}, {l}, levels]")
-    levels = thresholds.shape[-1]
-    if not 1 <= levels <= SOFT_MAX_LEVELS:
-        raise ValueError(f"thresholds holds {levels} levels, supported are 1..{SOFT_MAX_LEVELS}")
-    return levels
 
 
 def extract_soft_l(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thresholds: torch.Tensor, l: int) -> SoftVote:
@@ -719,29 +723,7 @@ def extract_soft_l(z: torch.Tensor, records: torch.Tensor, msg_bytes: int, thres
     `extract_records(..., l=l)`'s bits and score = 2 counts - copies.  n must be a multiple of 8 and n l at most 1 048 576 (ValueError);
     IndexError as `extract_records`.  l = 1 is refused: that is `extract_soft`."""
     l = _multi_bit_window(l, "extract_soft")
-    B, stride, msg_bytes = _records_operand(records, msg_bytes)
-    _need_gpu(z, "z")
-    _same_device(records, z, "records")
-    if z.dim() < 2 or z.shape[0] != B:
-        raise ValueError(f"z holds {z.shape[0] if z.dim() else 0} images, records {B} rows")
-    levels = _window_table(thresholds, z, B, l)
-    dt = _dt(z.dtype)
-    n = z.numel() // B
-    if n < 1 or n % 8 or n * l > ROW_MAX_BITS:
-        raise ValueError(f"a lattice of {n} elements at l = {l} must be a multiple of 8 elements and hold at most {ROW_MAX_BITS} bits")
-    M = 8 * msg_bytes
-    bits = torch.empty((B, msg_bytes), dtype=torch.uint8, device=z.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
-    matches = torch.empty((B,), dtype=torch.int32, device=z.device)
-    score = torch.empty((B, M), dtype=torch.int32, device=z.device)
-    wsum = torch.empty((B, M), dtype=torch.int32, device=z.device)
-    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
-    thresholds = thresholds.contiguous()
-    with torch.cuda.device(z.device):
-        N.check(N.lib().gsw_extract_soft_l(z.data_ptr(), dt, records.data_ptr(), stride, msg_bytes, thresholds.data_ptr(),
-                                           l * levels if thresholds.dim() == 3 else 0, levels, l, bits.data_ptr(), score.data_ptr(),
-                                           wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), matches.data_ptr(), B, n, _stream_ptr()))
-    return SoftVote(bits, flags, matches, score, wsum, wsq)
+    return _soft_vote(z, records, msg_bytes, thresholds, l)
 
 
 def level_pack_l(z: torch.Tensor, thresholds: torch.Tensor, l: int) -> LevelRows:
@@ -751,27 +733,7 @@ def level_pack_l(z: torch.Tensor, thresholds: torch.Tensor, l: int) -> LevelRows
     n must be a multiple of 8 and n l at most 1 048 576; the searches refuse n l (1 + P) > 1 048 576.  l = 1 is refused: that is
     `level_pack`."""
     l = _multi_bit_window(l, "level_pack")
-    _need_gpu(z, "z")
-    if z.dim() < 2 or z.shape[0] < 1:
-        raise ValueError("z must be [B, ...] with at least one image")
-    B = z.shape[0]
-    levels = _window_table(thresholds, z, B, l)
-    dt = _dt(z.dtype)
-    n = z.numel() // B
-    if n < 8 or n % 8 or n * l > ROW_MAX_BITS:
-        raise ValueError(f"level_pack_l needs a lattice of a multiple of 8 elements per image and at most {ROW_MAX_BITS} bits (got {n} at l = {l})")
-    P = level_planes(levels)
-    nbytes = n * l // 8
-    signs = torch.empty((B, nbytes), dtype=torch.uint8, device=z.device)
-    planes = torch.empty((B, P, nbytes), dtype=torch.uint8, device=z.device)
-    wsum = torch.empty((B,), dtype=torch.int32, device=z.device)
-    wsq = torch.empty((B,), dtype=torch.int32, device=z.device)
-    flags = torch.empty((B,), dtype=torch.int32, device=z.device)
-    thresholds = thresholds.contiguous()
-    with torch.cuda.device(z.device):
-        N.check(N.lib().gsw_level_pack_l(z.data_ptr(), dt, thresholds.data_ptr(), l * levels if thresholds.dim() == 3 else 0, levels, l,
-                                         signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(), wsq.data_ptr(), flags.data_ptr(), B, n, _stream_ptr()))
-    return LevelRows(signs, planes, wsum, wsq, flags)
+    return _level_rows(z, thresholds, l)
 
 
 def _level_rows_checks(rows: "LevelRows", with_wsum: bool):

@@ -1,7 +1,8 @@
 // gswm_codec_soft.inc -- the soft-decision vote: every lattice element votes with an integer reliability level taken from its magnitude,
 // B images under their own records in one launch (gfx950).  Included at the end of gswm_kernels.hip, after gswm_codec_keyed.inc: records,
 // keystream, its LDS staging and the end of the vote are gsw_extract_keyed's own (gswm_record.h), the hard bit q_j is gsw_extract's
-// quantiser (quantise8 / quantise8d), l = 1 only.
+// quantiser (quantise8 / quantise8d).  The kernels here are l = 1; the host side at the end of the namespace (one argument struct per operation, level_check /
+// vote_check, vote_args / pack_args, launch_vote / launch_pack, with_dtype / with_steps) also serves the l = 2, 4 entry points of gswm_codec_soft_l.inc.
 //
 // Definition, image b with thresholds thr[b][0 .. levels) (fp32; row b * thr_stride of thr_dev, thr_stride == 0: one row for all), M = 8 msg_bytes:
 //   p_j     = q_j ^ ks_j                                  the decrypted bit of element j
@@ -37,10 +38,11 @@ namespace codec_soft {
 
 constexpr int SOFT_MAX_LEVELS = 15;
 
+// the arguments of both vote kernels: gsw_extract_soft_kernel below and gsw_extract_soft_l_kernel (gswm_codec_soft_l.inc); filled by vote_args
 struct ExtractSoftArgs {
     const void* z;          // [B][N]
     const uint8_t* records; // [B][stride]
-    const float* thr;       // [B][thr_stride] or one row
+    const float* thr;       // [B][thr_stride] or one table: a row (l = 1), [L][levels] (l = 2, 4)
     uint8_t* bits;          // [B][msg_bytes]
     int32_t* score;         // [B][msg_bits] or nullptr
     int32_t* wsum;          // [B][msg_bits] or nullptr
@@ -50,11 +52,12 @@ struct ExtractSoftArgs {
     int64_t thr_stride;     // floats
     uint32_t stride;
     uint32_t n_elems;       // N
-    uint32_t msg_bytes;
+    uint32_t msg_bytes;     // P
     uint32_t nblk;          // ChaCha blocks that cover the staged row
     uint32_t levels;
-    uint32_t reps;          // R: threads per octet
-    Thr q;                  // gsw_extract's quantiser
+    uint32_t q;             // Q = P / gcd(P, l): the groups after which a thread's message bytes repeat (l = 1: P)
+    uint32_t reps;          // R = 256 / Q: threads per octet (l = 1), per owner (l = 2, 4)
+    Thr quant;              // gsw_extract's quantiser (read at l = 1; the windows of l = 2, 4 are quantised against constants)
 };
 
 // eight elements as the type they are compared in (fp32, fp64 for fp64 inputs), their cipher byte and flags by gsw_extract's quantiser
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
     if (tid < step) {
         for (uint32_t g = tid; g < (N >> 3); g += step) {            // N % 8 == 0: whole, 16-byte aligned groups
             cmp_t v[8];
-            const uint32_t c = Group8<T>::ld(z + ((size_t)g << 3), p.q, v, flags) ^ (uint32_t)row[g];
+            const uint32_t c = Group8<T>::ld(z + ((size_t)g << 3), p.quant, v, flags) ^ (uint32_t)row[g];
             uint32_t lv[8];
             levels8<STEPS>(v, s_thr, lv);
 #pragma unroll
@@ -171,39 +174,23 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_kernel(ExtractSoftArg
     if (tid == 0 && p.wsq) p.wsq[b] = (int32_t)(s_wsq[0] + s_wsq[1] + s_wsq[2] + s_wsq[3]);
 }
 
-template <typename T, int STEPS>
-static int launch_soft_steps(const ExtractSoftArgs& a, int B, hipStream_t st) {
-    const uint32_t lds = a.nblk * 64u;
-    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_soft_kernel<T, STEPS>, lds, 32u * 1024u));   // next to 17.1 KiB of static LDS
-    hipLaunchKernelGGL((gsw_extract_soft_kernel<T, STEPS>), dim3((uint32_t)B), dim3(GSW_WG), lds, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
-}
-
-template <typename T>
-static int launch_soft(const ExtractSoftArgs& a, int B, hipStream_t st) {
-    if (a.levels < 2u) return launch_soft_steps<T, 1>(a, B, st);    // the bit length of `levels`: 2^STEPS - 1 >= levels
-    if (a.levels < 4u) return launch_soft_steps<T, 2>(a, B, st);
-    if (a.levels < 8u) return launch_soft_steps<T, 3>(a, B, st);
-    return launch_soft_steps<T, 4>(a, B, st);
-}
-
 // ---- gsw_level_pack: the operands of the level-weighted keyed search (gswm_keyed_soft.inc) -- the sign row of gsw_sign_pack, the bits of the
 // levels as P = STEPS packed planes, and the two sums of the levels.  [B] workgroups of 256; thread tid walks the groups of eight elements tid,
 // tid + 256, ... and writes one byte of the sign row and of every plane per group (adjacent lanes adjacent bytes).  The quantiser is the vote's
 // (Group8), the level search is levels8 above.  Integer sums, reduced by shuffles and one LDS round: no atomics, no workspace, nothing to zero.
+// the arguments of both pack kernels: gsw_level_pack_kernel below and gsw_level_pack_l_kernel (gswm_codec_soft_l.inc); filled by pack_args
 struct LevelPackArgs {
     const void* z;          // [B][N]
-    const float* thr;       // [B][thr_stride] or one row
-    uint8_t* signs;         // [B][N / 8]
-    uint8_t* planes;        // [B][STEPS][N / 8], plane k = bit k of the levels
+    const float* thr;       // [B][thr_stride] or one table: a row (l = 1), [L][levels] (l = 2, 4)
+    uint8_t* signs;         // [B][N l / 8]
+    uint8_t* planes;        // [B][STEPS][N l / 8], plane k = bit k of the levels
     int32_t* wsum;          // [B]
     int32_t* wsq;           // [B]
     uint32_t* flags;        // [B]
     int64_t thr_stride;     // floats
     uint32_t n_elems;       // N
     uint32_t levels;
-    Thr q;                  // gsw_extract's quantiser
+    Thr quant;              // gsw_extract's quantiser (read at l = 1)
 };
 
 template <typename T, int STEPS>
@@ -223,7 +210,7 @@ __global__ __launch_bounds__(GSW_WG) void gsw_level_pack_kernel(LevelPackArgs p)
     uint32_t flags = 0, wsum = 0, wsq = 0;
     for (uint32_t g = tid; g < nbytes; g += GSW_WG) {               // N % 8 == 0: whole, 16-byte aligned groups
         cmp_t v[8];
-        signs[g] = (uint8_t)Group8<T>::ld(z + ((size_t)g << 3), p.q, v, flags);
+        signs[g] = (uint8_t)Group8<T>::ld(z + ((size_t)g << 3), p.quant, v, flags);
         uint32_t lv[8];
         levels8<STEPS>(v, s_thr, lv);
         uint32_t pl[STEPS];
@@ -249,64 +236,55 @@ __global__ __launch_bounds__(GSW_WG) void gsw_level_pack_kernel(LevelPackArgs p)
     }
 }
 
-template <typename T>
-static int launch_level_pack(const LevelPackArgs& a, int B, hipStream_t st) {
-    const dim3 grid((uint32_t)B), wg(GSW_WG);
-    if (a.levels < 2u) hipLaunchKernelGGL((gsw_level_pack_kernel<T, 1>), grid, wg, 0, st, a);   // the bit length of `levels`, as launch_soft
-    else if (a.levels < 4u) hipLaunchKernelGGL((gsw_level_pack_kernel<T, 2>), grid, wg, 0, st, a);
-    else if (a.levels < 8u) hipLaunchKernelGGL((gsw_level_pack_kernel<T, 3>), grid, wg, 0, st, a);
-    else hipLaunchKernelGGL((gsw_level_pack_kernel<T, 4>), grid, wg, 0, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
-}
+// ---- the host side of the four entry points (l = 1 here, l = 2 and 4 in gswm_codec_soft_l.inc): one check, one filling function per struct, one launch each.
 
-}  // namespace codec_soft
-
-int gsw_level_pack(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, uint8_t* signs_dev, uint8_t* planes_dev,
-                   int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int B, int64_t n_elems, void* stream) {
-    if (!z_dev || !thr_dev || !signs_dev || !planes_dev || !wsum_dev || !wsq_dev || !flags_dev || B < 1 || n_elems < 1) return GSW_ERR_BAD_ARG;
-    if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
-    if ((uintptr_t)z_dev & 15u) return GSW_ERR_BAD_ARG;                                      // 16-byte loads
-    if ((uintptr_t)thr_dev & 3u) return GSW_ERR_BAD_ARG;
-    if (levels < 1 || levels > codec_soft::SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
-    if (thr_stride != 0 && thr_stride < levels) return GSW_ERR_BAD_ARG;
-    if (n_elems % 8 || n_elems > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;                // (15^2 n fits int32 far beyond this)
-    codec_soft::LevelPackArgs a;
-    memset(&a, 0, sizeof(a));
-    a.z = z_dev;
-    a.thr = thr_dev;
-    a.signs = signs_dev;
-    a.planes = planes_dev;
-    a.wsum = wsum_dev;
-    a.wsq = wsq_dev;
-    a.flags = flags_dev;
-    a.thr_stride = thr_stride;
-    a.n_elems = (uint32_t)n_elems;
-    a.levels = (uint32_t)levels;
-    a.q = make_thr(z_dtype);
-    hipStream_t st = (hipStream_t)stream;
+// f(TypeTag<the element type of z_dtype>{}); z_dtype was checked
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F> static int with_dtype(int z_dtype, F&& f) {
     switch (z_dtype) {
-        case GSW_F32: return codec_soft::launch_level_pack<float>(a, B, st);
-        case GSW_F16: return codec_soft::launch_level_pack<__half>(a, B, st);
-        case GSW_BF16: return codec_soft::launch_level_pack<__hip_bfloat16>(a, B, st);
-        default: return codec_soft::launch_level_pack<double>(a, B, st);
+        case GSW_F32: return f(TypeTag<float>{});
+        case GSW_F16: return f(TypeTag<__half>{});
+        case GSW_BF16: return f(TypeTag<__hip_bfloat16>{});
+        default: return f(TypeTag<double>{});
     }
 }
 
-int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
-                     int64_t thr_stride, int levels, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,
-                     uint32_t* flags_dev, uint32_t* matches_dev, int B, int64_t n_elems, void* stream) {
-    const int rc = records_check32(records_dev, record_stride, msg_bytes, B);
-    if (rc != GSW_OK) return rc;
-    if (!z_dev || !thr_dev || !bits_dev || !flags_dev || n_elems <= 0) return GSW_ERR_BAD_ARG;
+// f(std::integral_constant<int, STEPS>{}), STEPS = the bit length of `levels`: 2^STEPS - 1 >= levels
+template <typename F> static int with_steps(uint32_t levels, F&& f) {
+    if (levels < 2u) return f(std::integral_constant<int, 1>{});
+    if (levels < 4u) return f(std::integral_constant<int, 2>{});
+    if (levels < 8u) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 4>{});
+}
+
+// what the entry points ask of z, the table and the lattice, l in {1, 2, 4} (the l entries refuse l = 1 themselves)
+static int level_check(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, int l, int64_t n_elems) {
+    if (!z_dev || !thr_dev || n_elems < 1) return GSW_ERR_BAD_ARG;
+    if (l != 1 && l != 2 && l != 4) return GSW_ERR_BAD_ARG;
     if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
     if ((uintptr_t)z_dev & 15u) return GSW_ERR_BAD_ARG;                                      // 16-byte loads
     if ((uintptr_t)thr_dev & 3u) return GSW_ERR_BAD_ARG;
-    if (levels < 1 || levels > codec_soft::SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
-    if (thr_stride != 0 && thr_stride < levels) return GSW_ERR_BAD_ARG;
-    if (n_elems % 8 || n_elems > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;
-    if (n_elems % ((int64_t)msg_bytes * 8)) return GSW_ERR_RAGGED;
-    codec_soft::ExtractSoftArgs a;
+    if (levels < 1 || levels > SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
+    if (thr_stride != 0 && thr_stride < (int64_t)l * levels) return GSW_ERR_BAD_ARG;
+    if (n_elems % 8 || n_elems * l > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;           // (15^2 n l fits int32 far beyond this)
+    return GSW_OK;
+}
+
+// the vote's check: the records first, then the outputs that must be there, level_check, and whole copies of the message in the n l bits
+static int vote_check(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev, int64_t thr_stride,
+                      int levels, int l, const uint8_t* bits_dev, const uint32_t* flags_dev, int B, int64_t n_elems) {
+    const int rc = records_check32(records_dev, record_stride, msg_bytes, B);
+    if (rc != GSW_OK) return rc;
+    if (!bits_dev || !flags_dev) return GSW_ERR_BAD_ARG;
+    const int lc = level_check(z_dev, z_dtype, thr_dev, thr_stride, levels, l, n_elems);
+    if (lc != GSW_OK) return lc;
+    return (n_elems * l) % ((int64_t)msg_bytes * 8) ? GSW_ERR_RAGGED : GSW_OK;
+}
+
+static ExtractSoftArgs vote_args(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
+                                 int64_t thr_stride, int levels, int l, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,
+                                 uint32_t* flags_dev, uint32_t* matches_dev, int64_t n_elems) {
+    ExtractSoftArgs a;
     memset(&a, 0, sizeof(a));
     a.z = z_dev;
     a.records = records_dev;
@@ -321,15 +299,76 @@ int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev,
     a.stride = (uint32_t)record_stride;
     a.n_elems = (uint32_t)n_elems;
     a.msg_bytes = (uint32_t)msg_bytes;
-    a.nblk = (uint32_t)((n_elems / 8 + 63) / 64);
+    a.nblk = (uint32_t)((n_elems / 8 * l + 63) / 64);
     a.levels = (uint32_t)levels;
-    a.reps = (uint32_t)GSW_WG / (uint32_t)msg_bytes;               // msg_bytes <= 256 = GSW_WG: at least 1
-    a.q = make_thr(z_dtype);
-    hipStream_t st = (hipStream_t)stream;
-    switch (z_dtype) {
-        case GSW_F32: return codec_soft::launch_soft<float>(a, B, st);
-        case GSW_F16: return codec_soft::launch_soft<__half>(a, B, st);
-        case GSW_BF16: return codec_soft::launch_soft<__hip_bfloat16>(a, B, st);
-        default: return codec_soft::launch_soft<double>(a, B, st);
-    }
+    uint32_t gcd = (uint32_t)l;                                      // l is 1, 2 or 4
+    while ((uint32_t)msg_bytes % gcd) gcd >>= 1;
+    a.q = (uint32_t)msg_bytes / gcd;                                 // <= 256 = GSW_WG: reps is at least 1
+    a.reps = (uint32_t)GSW_WG / a.q;
+    a.quant = make_thr(z_dtype);
+    return a;
+}
+
+static LevelPackArgs pack_args(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, uint8_t* signs_dev, uint8_t* planes_dev,
+                               int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int64_t n_elems) {
+    LevelPackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.z = z_dev;
+    a.thr = thr_dev;
+    a.signs = signs_dev;
+    a.planes = planes_dev;
+    a.wsum = wsum_dev;
+    a.wsq = wsq_dev;
+    a.flags = flags_dev;
+    a.thr_stride = thr_stride;
+    a.n_elems = (uint32_t)n_elems;
+    a.levels = (uint32_t)levels;
+    a.quant = make_thr(z_dtype);
+    return a;
+}
+
+// [B] workgroups of 256 with the image's keystream in dynamic LDS; lds_threshold: from where on the kernel must be allowed that much next to its static LDS
+static int launch_vote(void (*kernel)(ExtractSoftArgs), uint32_t lds_threshold, const ExtractSoftArgs& a, int B, hipStream_t st) {
+    const uint32_t lds = a.nblk * 64u;
+    GSW_HIP(allow_dynamic_lds((const void*)kernel, lds, lds_threshold));
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)B), dim3(GSW_WG), lds, st, a);
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
+static int launch_pack(void (*kernel)(LevelPackArgs), const LevelPackArgs& a, int B, hipStream_t st) {
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)B), dim3(GSW_WG), 0, st, a);
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
+}  // namespace codec_soft
+
+int gsw_level_pack(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, uint8_t* signs_dev, uint8_t* planes_dev,
+                   int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int B, int64_t n_elems, void* stream) {
+    using namespace codec_soft;
+    if (!signs_dev || !planes_dev || !wsum_dev || !wsq_dev || !flags_dev || B < 1) return GSW_ERR_BAD_ARG;
+    const int rc = level_check(z_dev, z_dtype, thr_dev, thr_stride, levels, 1, n_elems);
+    if (rc != GSW_OK) return rc;
+    const LevelPackArgs a = pack_args(z_dev, z_dtype, thr_dev, thr_stride, levels, signs_dev, planes_dev, wsum_dev, wsq_dev, flags_dev, n_elems);
+    return with_dtype(z_dtype, [&](auto t) {
+        return with_steps(a.levels, [&](auto steps) {
+            return launch_pack(gsw_level_pack_kernel<typename decltype(t)::type, decltype(steps)::value>, a, B, (hipStream_t)stream);
+        });
+    });
+}
+
+int gsw_extract_soft(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
+                     int64_t thr_stride, int levels, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,
+                     uint32_t* flags_dev, uint32_t* matches_dev, int B, int64_t n_elems, void* stream) {
+    using namespace codec_soft;
+    const int rc = vote_check(z_dev, z_dtype, records_dev, record_stride, msg_bytes, thr_dev, thr_stride, levels, 1, bits_dev, flags_dev, B, n_elems);
+    if (rc != GSW_OK) return rc;
+    const ExtractSoftArgs a = vote_args(z_dev, z_dtype, records_dev, record_stride, msg_bytes, thr_dev, thr_stride, levels, 1, bits_dev, score_dev, wsum_dev, wsq_dev,
+                                        flags_dev, matches_dev, n_elems);
+    return with_dtype(z_dtype, [&](auto t) {
+        return with_steps(a.levels, [&](auto steps) {                  // 32 KiB: next to 17.1 KiB of static LDS
+            return launch_vote(gsw_extract_soft_kernel<typename decltype(t)::type, decltype(steps)::value>, 32u * 1024u, a, B, (hipStream_t)stream);
+        });
+    });
 }

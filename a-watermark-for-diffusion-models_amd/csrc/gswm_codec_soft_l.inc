@@ -1,7 +1,8 @@
 // gswm_codec_soft_l.inc -- the soft-decision vote for multi-bit windows (l = 2, 4): every CIPHER BIT of a lattice element votes with an
 // integer reliability level, B images under their own records in one launch (gfx950).  Included at the end of gswm_kernels.hip, after
 // gswm_codec_soft.inc: records, keystream staging and the end of the vote are gswm_record.h's, the hard window y is gswm_codec_l.inc's
-// quantiser (quant1), the ranking of a threshold row is gswm_codec_soft.inc's (rank_thresholds).  DESIGN.md section 4.23.
+// quantiser (quant1), the ranking of a threshold row is gswm_codec_soft.inc's (rank_thresholds), and so are the argument structs (ExtractSoftArgs,
+// LevelPackArgs) and the whole host side of the two entry points at the end of this file.  DESIGN.md section 4.23.
 //
 // Definition, image b, element e with stored value z (Z = z widened exactly to fp64), y = #{ j : z >= T_j } its window, T = quant_thresholds:
 //   window bit w (0 = first = MSB of y, cipher position e l + w) has the value s = 2^(l-1-w) in y and flips exactly at the boundaries T_i, s | i
@@ -122,32 +123,15 @@ __device__ __forceinline__ void levels_group(const F (&v)[8], const uint32_t (&y
     }
 }
 
-struct ExtractSoftLArgs {
-    const void* z;          // [B][N]
-    const uint8_t* records; // [B][stride]
-    const float* thr;       // [B][thr_stride] or one table, [L][levels]
-    uint8_t* bits;          // [B][msg_bytes]
-    int32_t* score;         // [B][msg_bits] or nullptr
-    int32_t* wsum;          // [B][msg_bits] or nullptr
-    int32_t* wsq;           // [B] or nullptr
-    uint32_t* flags;        // [B]
-    uint32_t* matches;      // [B] or nullptr
-    int64_t thr_stride;     // floats
-    uint32_t stride;
-    uint32_t n_elems;       // N
-    uint32_t msg_bytes;     // P
-    uint32_t nblk;          // ChaCha blocks that cover the staged row
-    uint32_t levels;
-    uint32_t q;             // Q = P / gcd(P, L)
-    uint32_t reps;          // R = 256 / Q
-};
+using codec_soft::ExtractSoftArgs;
+using codec_soft::LevelPackArgs;
 
 constexpr uint32_t NO_OWNER = 0xFFFFu;
 static_assert(GSW_MSG_INLINE_MAX == GSW_WG, "s_own is initialised one column per thread");
 constexpr int SOFT_L_TRIPS = GSW_MSG_INLINE_MAX * 8 / GSW_WG;        // message bits per thread at the longest message
 
 template <typename T, int L, int STEPS>
-__global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_l_kernel(ExtractSoftLArgs p) {
+__global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_l_kernel(ExtractSoftArgs p) {
     typedef typename codec_l::QLoad<T>::F F;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // the keystream of the image, p.nblk * 16 words
     __shared__ int32_t s_part[16][GSW_WG];                           // one round: [k] score, [8 + k] wsum of every thread's byte i
@@ -242,46 +226,6 @@ __global__ __launch_bounds__(GSW_WG) void gsw_extract_soft_l_kernel(ExtractSoftL
     if (tid == 0 && p.wsq) p.wsq[b] = (int32_t)(s_wsq[0] + s_wsq[1] + s_wsq[2] + s_wsq[3]);
 }
 
-template <typename T, int L, int STEPS>
-static int launch_soft_l_steps(const ExtractSoftLArgs& a, int B, hipStream_t st) {
-    const uint32_t lds = a.nblk * 64u;
-    GSW_HIP(allow_dynamic_lds((const void*)gsw_extract_soft_l_kernel<T, L, STEPS>, lds, 16u * 1024u));   // next to up to 26.8 KiB of static LDS
-    hipLaunchKernelGGL((gsw_extract_soft_l_kernel<T, L, STEPS>), dim3((uint32_t)B), dim3(GSW_WG), lds, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
-}
-
-template <typename T, int L>
-static int launch_soft_l(const ExtractSoftLArgs& a, int B, hipStream_t st) {
-    if (a.levels < 2u) return launch_soft_l_steps<T, L, 1>(a, B, st);   // the bit length of `levels`, as launch_soft
-    if (a.levels < 4u) return launch_soft_l_steps<T, L, 2>(a, B, st);
-    if (a.levels < 8u) return launch_soft_l_steps<T, L, 3>(a, B, st);
-    return launch_soft_l_steps<T, L, 4>(a, B, st);
-}
-
-template <int L>
-static int launch_soft_l_dtype(const ExtractSoftLArgs& a, int dtype, int B, hipStream_t st) {
-    switch (dtype) {
-        case GSW_F32: return launch_soft_l<float, L>(a, B, st);
-        case GSW_F16: return launch_soft_l<__half, L>(a, B, st);
-        case GSW_BF16: return launch_soft_l<__hip_bfloat16, L>(a, B, st);
-        default: return launch_soft_l<double, L>(a, B, st);
-    }
-}
-
-struct LevelPackLArgs {
-    const void* z;          // [B][N]
-    const float* thr;       // [B][thr_stride] or one table, [L][levels]
-    uint8_t* signs;         // [B][N L / 8]
-    uint8_t* planes;        // [B][STEPS][N L / 8], plane k = bit k of the levels
-    int32_t* wsum;          // [B]
-    int32_t* wsq;           // [B]
-    uint32_t* flags;        // [B]
-    int64_t thr_stride;     // floats
-    uint32_t n_elems;       // N
-    uint32_t levels;
-};
-
 // the 8 L bits of group g (first bit on top) as L bytes at row[g L ..], first byte at the lower address; one store where the row allows it
 template <int L>
 __device__ __forceinline__ void store_group(uint8_t* row, uint32_t g, uint32_t bits, bool aligned) {
@@ -295,7 +239,7 @@ __device__ __forceinline__ void store_group(uint8_t* row, uint32_t g, uint32_t b
 }
 
 template <typename T, int L, int STEPS>
-__global__ __launch_bounds__(GSW_WG) void gsw_level_pack_l_kernel(LevelPackLArgs p) {
+__global__ __launch_bounds__(GSW_WG) void gsw_level_pack_l_kernel(LevelPackArgs p) {
     typedef typename codec_l::QLoad<T>::F F;
     __shared__ float s_thr[L][SOFT_MAX_LEVELS + 1];
     __shared__ typename EdgePair<F>::V s_edge[SOFT_MAX_LEVELS + 1][Geo<L>::ROWS];
@@ -341,93 +285,46 @@ __global__ __launch_bounds__(GSW_WG) void gsw_level_pack_l_kernel(LevelPackLArgs
     }
 }
 
-template <typename T, int L>
-static int launch_level_pack_l(const LevelPackLArgs& a, int B, hipStream_t st) {
-    const dim3 grid((uint32_t)B), wg(GSW_WG);
-    if (a.levels < 2u) hipLaunchKernelGGL((gsw_level_pack_l_kernel<T, L, 1>), grid, wg, 0, st, a);   // the bit length of `levels`
-    else if (a.levels < 4u) hipLaunchKernelGGL((gsw_level_pack_l_kernel<T, L, 2>), grid, wg, 0, st, a);
-    else if (a.levels < 8u) hipLaunchKernelGGL((gsw_level_pack_l_kernel<T, L, 3>), grid, wg, 0, st, a);
-    else hipLaunchKernelGGL((gsw_level_pack_l_kernel<T, L, 4>), grid, wg, 0, st, a);
-    GSW_HIP(hipGetLastError());
-    return GSW_OK;
-}
-
-template <int L>
-static int launch_level_pack_l_dtype(const LevelPackLArgs& a, int dtype, int B, hipStream_t st) {
-    switch (dtype) {
-        case GSW_F32: return launch_level_pack_l<float, L>(a, B, st);
-        case GSW_F16: return launch_level_pack_l<__half, L>(a, B, st);
-        case GSW_BF16: return launch_level_pack_l<__hip_bfloat16, L>(a, B, st);
-        default: return launch_level_pack_l<double, L>(a, B, st);
-    }
-}
-
-// what both entry points ask of z, the table and the lattice
-static int soft_l_check(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, int l, int64_t n_elems) {
-    if (!z_dev || !thr_dev || n_elems < 1) return GSW_ERR_BAD_ARG;
-    if (l != 2 && l != 4) return GSW_ERR_BAD_ARG;
-    if (z_dtype < GSW_F32 || z_dtype > GSW_F64) return GSW_ERR_BAD_ARG;
-    if ((uintptr_t)z_dev & 15u) return GSW_ERR_BAD_ARG;                                      // 16-byte loads
-    if ((uintptr_t)thr_dev & 3u) return GSW_ERR_BAD_ARG;
-    if (levels < 1 || levels > SOFT_MAX_LEVELS) return GSW_ERR_BAD_ARG;
-    if (thr_stride != 0 && thr_stride < (int64_t)l * levels) return GSW_ERR_BAD_ARG;
-    if (n_elems % 8 || n_elems * l > GSW_ROW_MAX_BITS) return GSW_ERR_UNSUPPORTED;           // (15^2 n l fits int32 far beyond this)
-    return GSW_OK;
+// f(std::integral_constant<int, L>{}); l is 2 or 4
+template <typename F> static int with_window(int l, F&& f) {
+    return l == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 4>{});
 }
 
 }  // namespace codec_soft_l
 
+// The host side is gswm_codec_soft.inc's with l = 2 or 4: level_check / vote_check, pack_args / vote_args, launch_pack / launch_vote.
 int gsw_level_pack_l(const void* z_dev, int z_dtype, const float* thr_dev, int64_t thr_stride, int levels, int l, uint8_t* signs_dev,
                      uint8_t* planes_dev, int32_t* wsum_dev, int32_t* wsq_dev, uint32_t* flags_dev, int B, int64_t n_elems, void* stream) {
-    if (!signs_dev || !planes_dev || !wsum_dev || !wsq_dev || !flags_dev || B < 1) return GSW_ERR_BAD_ARG;
-    const int rc = codec_soft_l::soft_l_check(z_dev, z_dtype, thr_dev, thr_stride, levels, l, n_elems);
+    using namespace codec_soft;
+    if (!signs_dev || !planes_dev || !wsum_dev || !wsq_dev || !flags_dev || B < 1 || l == 1) return GSW_ERR_BAD_ARG;
+    const int rc = level_check(z_dev, z_dtype, thr_dev, thr_stride, levels, l, n_elems);
     if (rc != GSW_OK) return rc;
-    codec_soft_l::LevelPackLArgs a;
-    memset(&a, 0, sizeof(a));
-    a.z = z_dev;
-    a.thr = thr_dev;
-    a.signs = signs_dev;
-    a.planes = planes_dev;
-    a.wsum = wsum_dev;
-    a.wsq = wsq_dev;
-    a.flags = flags_dev;
-    a.thr_stride = thr_stride;
-    a.n_elems = (uint32_t)n_elems;
-    a.levels = (uint32_t)levels;
-    hipStream_t st = (hipStream_t)stream;
-    return l == 2 ? codec_soft_l::launch_level_pack_l_dtype<2>(a, z_dtype, B, st) : codec_soft_l::launch_level_pack_l_dtype<4>(a, z_dtype, B, st);
+    const LevelPackArgs a = pack_args(z_dev, z_dtype, thr_dev, thr_stride, levels, signs_dev, planes_dev, wsum_dev, wsq_dev, flags_dev, n_elems);
+    return with_dtype(z_dtype, [&](auto t) {
+        return codec_soft_l::with_window(l, [&](auto w) {
+            return with_steps(a.levels, [&](auto steps) {
+                return launch_pack(codec_soft_l::gsw_level_pack_l_kernel<typename decltype(t)::type, decltype(w)::value, decltype(steps)::value>, a, B,
+                                   (hipStream_t)stream);
+            });
+        });
+    });
 }
 
 int gsw_extract_soft_l(const void* z_dev, int z_dtype, const uint8_t* records_dev, int64_t record_stride, int msg_bytes, const float* thr_dev,
                        int64_t thr_stride, int levels, int l, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* wsq_dev,
                        uint32_t* flags_dev, uint32_t* matches_dev, int B, int64_t n_elems, void* stream) {
-    const int rc = records_check32(records_dev, record_stride, msg_bytes, B);
+    using namespace codec_soft;
+    if (l == 1) return GSW_ERR_BAD_ARG;                              // that is gsw_extract_soft; every refusal before GSW_ERR_UNSUPPORTED is GSW_ERR_BAD_ARG
+    const int rc = vote_check(z_dev, z_dtype, records_dev, record_stride, msg_bytes, thr_dev, thr_stride, levels, l, bits_dev, flags_dev, B, n_elems);
     if (rc != GSW_OK) return rc;
-    if (!bits_dev || !flags_dev) return GSW_ERR_BAD_ARG;
-    const int sc = codec_soft_l::soft_l_check(z_dev, z_dtype, thr_dev, thr_stride, levels, l, n_elems);
-    if (sc != GSW_OK) return sc;
-    if ((n_elems * l) % ((int64_t)msg_bytes * 8)) return GSW_ERR_RAGGED;
-    codec_soft_l::ExtractSoftLArgs a;
-    memset(&a, 0, sizeof(a));
-    a.z = z_dev;
-    a.records = records_dev;
-    a.thr = thr_dev;
-    a.bits = bits_dev;
-    a.score = score_dev;
-    a.wsum = wsum_dev;
-    a.wsq = wsq_dev;
-    a.flags = flags_dev;
-    a.matches = matches_dev;
-    a.thr_stride = thr_stride;
-    a.stride = (uint32_t)record_stride;
-    a.n_elems = (uint32_t)n_elems;
-    a.msg_bytes = (uint32_t)msg_bytes;
-    a.nblk = (uint32_t)((n_elems / 8 * l + 63) / 64);
-    a.levels = (uint32_t)levels;
-    uint32_t gcd = (uint32_t)l;                                      // l is 2 or 4
-    while ((uint32_t)msg_bytes % gcd) gcd >>= 1;
-    a.q = (uint32_t)msg_bytes / gcd;                                 // <= 256 = GSW_WG: reps is at least 1
-    a.reps = (uint32_t)GSW_WG / a.q;
-    hipStream_t st = (hipStream_t)stream;
-    return l == 2 ? codec_soft_l::launch_soft_l_dtype<2>(a, z_dtype, B, st) : codec_soft_l::launch_soft_l_dtype<4>(a, z_dtype, B, st);
+    const ExtractSoftArgs a = vote_args(z_dev, z_dtype, records_dev, record_stride, msg_bytes, thr_dev, thr_stride, levels, l, bits_dev, score_dev, wsum_dev, wsq_dev,
+                                        flags_dev, matches_dev, n_elems);
+    return with_dtype(z_dtype, [&](auto t) {
+        return codec_soft_l::with_window(l, [&](auto w) {
+            return with_steps(a.levels, [&](auto steps) {              // 16 KiB: next to up to 26.8 KiB of static LDS
+                return launch_vote(codec_soft_l::gsw_extract_soft_l_kernel<typename decltype(t)::type, decltype(w)::value, decltype(steps)::value>, 16u * 1024u, a,
+                                   B, (hipStream_t)stream);
+            });
+        });
+    });
 }

@@ -423,38 +423,14 @@ def detect_latents(latents, keyring: Keyring, message_length: int, *, k: int = 1
     `codec.key_search_soft_topk` in place of the sign search, and the message of the best key read by one `codec.extract_soft` launch with the same
     thresholds.  `KeyCandidate.stat` is then the level-weighted statistic and the bound under it `log10_p_blind_soft` -- a Chernoff bound given the image's
     levels, which the host reads from the planes already on the device.  One cipher bit per element only (l = 1), and not with `align` yet (ValueError)."""
-    import torch
     reliability = _reliability_levels(reliability)
-    if reliability:
-        if align is not None:
-            raise ValueError("reliability cannot be combined with align yet: the level planes are not carried through the alignment search")
-        return _detect_latents_soft(latents, keyring, message_length, k, fpr, l, reliability)
-    if align is not None:
-        return _detect_latents_aligned(latents, keyring, message_length, k, fpr, l, align)
-    limit = T._log10_fpr(fpr)
-    mb = _message_bytes(message_length)
-    M = 8 * mb
+    if reliability and align is not None:
+        raise ValueError("reliability cannot be combined with align yet: the level planes are not carried through the alignment search")
+    limit, mb = _rate_and_bytes(fpr, message_length)
     l = codec.check_window(l)
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("k must be in 1..8")
-    keys_host = keyring.packed()                                   # (an empty keyring fails here)
-    z = latents.contiguous()
-    B = z.shape[0]
-    n = z.numel() // max(B, 1)
-    V = codec.vote_copies(n, M, l)                                 # (a lattice the message does not tile fails here, as extract_batch would)
-    nb = n * l
-    keys_dev = keyring.to_device(z.device) if z.is_cuda else torch.from_numpy(keys_host)
-    packed, flags = codec.quant_pack(z, l)
-    idx, stat = codec.key_search_topk(packed, nb, keys_dev, mb, k=k)
-    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
-    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
-    bits, _, _ = codec.extract_records(z, rows, mb, l=l)
-    idx_h, stat_h = T._pairs_to_host(idx, stat)
-    flags_h, bits_h, K = flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
-    return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), K)),
-                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
-                              refuse=False)
+    if reliability and l != 1:
+        raise ValueError(f"reliability cannot be combined with l = {l}: reliability levels are defined for one cipher bit per element")
+    return _detect(latents, keyring, mb, k, limit, l=l, levels=reliability, aligns=align)[0]
 
 
 def _reliability_levels(reliability) -> int:
@@ -469,35 +445,132 @@ def levels_from_planes(planes: np.ndarray) -> np.ndarray:
     return sum(bits[:, p] << p for p in range(planes.shape[1]))
 
 
-def _detect_latents_soft(latents, keyring: Keyring, message_length: int, k: int, fpr: float, l: int, levels: int) -> List[DetectResult]:
-    """`detect_latents` ranked by `levels` reliability levels"""
+def _rate_and_bytes(fpr, message_length) -> Tuple[float, int]:
+    """What every detection checks first, in this order -> (log10 fpr, message bytes)"""
+    return T._log10_fpr(fpr), _message_bytes(message_length)
+
+
+# The four steps of a detection, each in the forms a decoder chooses from.  pack(z, l, levels) -> (packed operand, flags, threshold table or None);
+# search(packed, shape, l, keys_dev, mb, table, k) -> (idx, stat, alignment index or None), int32 [B, k] on the device; read(z, rows, mb, l, thr) -> voted bytes;
+# law(packed, M, V, shape, table) -> bound(b, a, s), log10 of the null tail of statistic s of image b under alignment index a (None: as it stands).
+def _pack_signs(z, l, levels):
+    packed, flags = codec.quant_pack(z, l)
+    return packed, flags, None
+
+
+def _pack_levels(z, l, levels):
+    thr = S._default_table(z, l, levels)                           # once, on the un-aligned latents: the search, the bound and the vote share it
+    packed = codec.level_pack(z, thr) if l == 1 else codec.level_pack_l(z, thr, l)
+    return packed, packed.flags, thr
+
+
+def _search_signs(packed, shape, l, keys_dev, mb, table, k):
+    return codec.key_search_topk(packed, packed.shape[1] * 8, keys_dev, mb, k=k) + (None,)
+
+
+def _search_levels(packed, shape, l, keys_dev, mb, table, k):
+    return codec.key_search_soft_topk(packed, packed.signs.shape[1] * 8, keys_dev, mb, k=k) + (None,)
+
+
+def _search_signs_aligned(packed, shape, l, keys_dev, mb, table, k):
+    from . import align as AL
+    idx, aidx, stat = AL._search_packed(packed, shape, l, keys_dev, mb, table, k)
+    return idx, stat, aidx
+
+
+def _search_levels_aligned(packed, shape, l, keys_dev, mb, table, k):
+    from . import align as AL
+    codec._level_rows_align_checks(packed, shape)
+    idx, aidx, stat = AL._search_level_rows(packed, shape, keys_dev, mb, table, k)
+    return idx, stat, aidx
+
+
+def _read_signs(z, rows, mb, l, thr):
+    return codec.extract_records(z, rows, mb, l=l)[0]
+
+
+def _read_levels(z, rows, mb, l, thr):
+    return (codec.extract_soft(z, rows, mb, thr) if l == 1 else codec.extract_soft_l(z, rows, mb, thr, l)).bits
+
+
+def _law_signs(packed, M, V, shape, table):
+    return lambda b, a, s: log10_p_blind(s, M, V)                  # exact, and the same under every alignment: a permutation keeps the copies per position
+
+
+def _law_levels(packed, M, V, shape, table):
+    """One dynamic programme per distinct (image, alignment) among the reported candidates: an alignment moves elements between message positions, so the W_t
+    and with them the null law differ from one alignment to the next"""
     import torch
-    limit = T._log10_fpr(fpr)
-    mb = _message_bytes(message_length)
+    from . import align as AL
+    lv = levels_from_planes(packed.planes.cpu().numpy())           # over the n l cipher bits, bit j on message position j mod M
+    laws: Dict[Tuple[int, Optional[int]], _SoftNullLaw] = {}
+
+    def bound(b: int, a: Optional[int], s: int) -> float:
+        t = laws.get((b, a))
+        if t is None:
+            row = lv[b] if a is None else AL.apply(torch.from_numpy(lv[b].reshape(shape)), table[a]).reshape(-1).numpy()
+            t = laws[(b, a)] = _SoftNullLaw(row, M)
+        return t.log10_bound(s)
+
+    return bound
+
+
+_DECODERS = {  # (level-weighted, with alignments) -> (pack, search, read, law); the next decoder is one more row
+    (False, False): (_pack_signs, _search_signs, _read_signs, _law_signs),
+    (True, False): (_pack_levels, _search_levels, _read_levels, _law_levels),
+    (False, True): (_pack_signs, _search_signs_aligned, _read_signs, _law_signs),
+    (True, True): (_pack_levels, _search_levels_aligned, _read_levels, _law_levels),
+}
+
+
+def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int, levels: int, aligns):
+    """The one flow behind `detect_latents`, `detect_latents_soft_l` and `detect_latents_aligned_soft`, after the checks that are each entry's own: pack the
+    images, search the keyring, read every image under its best key, bound every reported statistic, build the candidate lists
+    -> (results, the best candidate's alignment index int [B] or None, the bytes voted under the best key uint8 [B, mb]).
+
+    levels: 0 -- the sign statistic; 1..15 -- the level-weighted statistic.  aligns: None, or the candidate alignments: the search then runs over every
+    (key, alignment) pair and the image is read with its best alignment applied.  `_DECODERS` holds the four steps of each combination."""
+    import torch
+    from . import align as AL
+    if levels and aligns is not None and l != 1:
+        raise ValueError(f"reliability levels cannot be combined with alignments at l = {l}: the level-weighted alignment search is defined for one cipher bit per element")
+    pack, search, read, law = _DECODERS[(bool(levels), aligns is not None)]
     M = 8 * mb
-    if codec.check_window(l) != 1:
-        raise ValueError(f"reliability cannot be combined with l = {l}: reliability levels are defined for one cipher bit per element")
     k = int(k)
     if not 1 <= k <= 8:
         raise ValueError("k must be in 1..8")
-    keyring.packed()                                               # (an empty keyring fails here)
+    keys_host = keyring.packed()                                   # (an empty keyring fails here)
+    if aligns is not None and latents.dim() != 4:
+        raise ValueError(f"align needs latents [B, C, H, W], got {tuple(latents.shape)}")
     z = latents.contiguous()
-    B = z.shape[0]
-    n = z.numel() // max(B, 1)
-    codec.vote_copies(n, M, 1)                                     # (a lattice the message does not tile fails here, as extract_batch would)
-    keys_dev = keyring.to_device(z.device)
-    thr = S.uniform_thresholds(z, levels)
-    packed = codec.level_pack(z, thr)
-    idx, stat = codec.key_search_soft_topk(packed, n, keys_dev, mb, k=k)
+    B, shape = z.shape[0], tuple(z.shape[1:])
+    table = None if aligns is None else AL._as_list(aligns, shape[1], shape[2])
+    V = codec.vote_copies(z.numel() // max(B, 1), M, l)            # (a lattice the message does not tile fails here, as extract_batch would)
+    keys_dev = keyring.to_device(z.device) if z.is_cuda else torch.from_numpy(keys_host)
+    packed, flags, thr = pack(z, l, levels)
+    idx, stat, aidx = search(packed, shape, l, keys_dev, mb, table, k)
     rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
-    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
-    bits = codec.extract_soft(z, rows, mb, thr).bits
-    idx_h, stat_h = T._pairs_to_host(idx, stat)
-    flags_h, bits_h, K = packed.flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
-    laws = [_SoftNullLaw(lv, M) for lv in levels_from_planes(packed.planes.cpu().numpy())]       # one dynamic programme per image, shared by its candidates
-    return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(laws[b].log10_bound(s), K)),
-                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
-                              refuse=False)
+    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]      # every image under its own best key, a zero message: `matches` is not read
+    if aidx is None:
+        bits = read(z, rows, mb, l, thr)
+        idx_h, stat_h = T._pairs_to_host(idx, stat)
+        aidx_h = None
+    else:                                                          # the read needs the best alignment on the host first
+        idx_h, aidx_h, stat_h = torch.stack([idx, aidx, stat]).cpu().numpy()
+        bits = read(AL.unalign(z, table, aidx_h[:, 0]), rows, mb, l, thr)
+    flags_h, bits_h = flags.cpu().numpy(), bits.cpu().numpy()
+    pairs = len(keyring) * (1 if table is None else len(table))    # Bonferroni: over the keys, or over the (key, alignment) pairs
+    bound = law(packed, M, V, shape, table)
+
+    def candidate(b, j, i, s):
+        a = None if aidx_h is None else int(aidx_h[b, j])
+        return KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(bound(b, a, s), pairs), None if a is None else table[a])
+
+    out = T._candidate_lists(idx_h, stat_h, flags_h, limit, candidate,
+                             lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b]),
+                                                              c[0].alignment if named else None),
+                             refuse=False)
+    return out, None if aidx_h is None else aidx_h[:, 0], bits_h
 
 
 def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int, *, levels: int = 15, k: int = 1, fpr: float = 1e-6) -> List[DetectResult]:
@@ -508,120 +581,23 @@ def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int
     statistic; the bound under it is `log10_p_blind_soft` on the n l per-bit levels read back from the planes (given the levels, the decrypted
     bits of a key-independent image are independent fair coins, per cipher bit), Bonferroni over the keyring.  n l (1 + P) may not exceed
     1 048 576, P the bit length of `levels`: the search refuses beyond (ValueError).  l = 1 is refused: that is `detect_latents(reliability=)`."""
-    import torch
-    limit = T._log10_fpr(fpr)
-    mb = _message_bytes(message_length)
-    M = 8 * mb
+    limit, mb = _rate_and_bytes(fpr, message_length)
     l = codec.check_window(l)
     if l == 1:
         raise ValueError("l = 1 has no window bits: the level-weighted key search at l = 1 is detect_latents(reliability=) (--reliability)")
     levels = _reliability_levels(levels)
     if not levels:
         raise ValueError(f"levels must be a number of levels in 1..{codec.SOFT_MAX_LEVELS}, got 0")
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("k must be in 1..8")
-    keyring.packed()                                               # (an empty keyring fails here)
-    z = latents.contiguous()
-    B = z.shape[0]
-    n = z.numel() // max(B, 1)
-    codec.vote_copies(n, M, l)                                     # (a lattice the message does not tile fails here, as extract_batch would)
-    keys_dev = keyring.to_device(z.device)
-    thr = S.window_thresholds(z, l, levels)
-    packed = codec.level_pack_l(z, thr, l)
-    idx, stat = codec.key_search_soft_topk(packed, n * l, keys_dev, mb, k=k)
-    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
-    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
-    bits = codec.extract_soft_l(z, rows, mb, thr, l).bits
-    idx_h, stat_h = T._pairs_to_host(idx, stat)
-    flags_h, bits_h, K = packed.flags.cpu().numpy(), bits.cpu().numpy(), len(keyring)
-    laws = [_SoftNullLaw(lv, M) for lv in levels_from_planes(packed.planes.cpu().numpy())]       # over the n l cipher bits, bit j on message position j mod M
-    return T._candidate_lists(idx_h, stat_h, flags_h, limit, lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(laws[b].log10_bound(s), K)),
-                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b])),
-                              refuse=False)
-
-
-def _detect_latents_aligned(latents, keyring: Keyring, message_length: int, k: int, fpr: float, l: int, aligns) -> List[DetectResult]:
-    """`detect_latents` with candidate alignments"""
-    import torch
-    from . import align as AL
-    limit = T._log10_fpr(fpr)
-    mb = _message_bytes(message_length)
-    M = 8 * mb
-    l = codec.check_window(l)
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("k must be in 1..8")
-    keyring.packed()                                               # (an empty keyring fails here)
-    if latents.dim() != 4:
-        raise ValueError(f"align needs latents [B, C, H, W], got {tuple(latents.shape)}")
-    z = latents.contiguous()
-    B = z.shape[0]
-    table = AL._as_list(aligns, z.shape[2], z.shape[3])
-    V = codec.vote_copies(z.numel() // max(B, 1), M, l)
-    keys_dev = keyring.to_device(z.device)
-    packed, flags = codec.quant_pack(z, l)
-    idx, aidx, stat = AL._search_packed(packed, z.shape[1:], l, keys_dev, mb, table, k)
-    host = torch.stack([idx, aidx, stat]).cpu().numpy()
-    idx_h, aidx_h, stat_h = host[0], host[1], host[2]
-    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
-    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
-    bits, _, _ = codec.extract_records(AL.unalign(z, table, aidx_h[:, 0]), rows, mb, l=l)
-    flags_h, bits_h, pairs = flags.cpu().numpy(), bits.cpu().numpy(), len(keyring) * len(table)
-    return T._candidate_lists(idx_h, stat_h, flags_h, limit,
-                              lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(log10_p_blind(s, M, V), pairs), table[int(aidx_h[b, j])]),
-                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b]),
-                                                               c[0].alignment if named else None),
-                              refuse=False)
+    return _detect(latents, keyring, mb, k, limit, l=l, levels=levels, aligns=None)[0]
 
 
 def _aligned_soft(latents, keyring: Keyring, message_length: int, aligns, levels: int, k: int, fpr: float):
     """`detect_latents_aligned_soft` -> (results, the best candidate's alignment index int [B], the bytes voted under it uint8 [B, msg_bytes])"""
-    import torch
-    from . import align as AL
-    limit = T._log10_fpr(fpr)
-    mb = _message_bytes(message_length)
-    M = 8 * mb
+    limit, mb = _rate_and_bytes(fpr, message_length)
     levels = _reliability_levels(levels)
     if not levels:
         raise ValueError(f"levels must be in 1..{codec.SOFT_MAX_LEVELS}: a search without levels is detect_latents(align=...)")
-    k = int(k)
-    if not 1 <= k <= 8:
-        raise ValueError("k must be in 1..8")
-    keyring.packed()                                               # (an empty keyring fails here)
-    if latents.dim() != 4:
-        raise ValueError(f"align needs latents [B, C, H, W], got {tuple(latents.shape)}")
-    z = latents.contiguous()
-    B, shape = z.shape[0], tuple(z.shape[1:])
-    table = AL._as_list(aligns, shape[1], shape[2])
-    codec.vote_copies(z.numel() // max(B, 1), M, 1)                # (a lattice the message does not tile fails here, as extract_batch would)
-    keys_dev = keyring.to_device(z.device)
-    thr = S.uniform_thresholds(z, levels)                          # once, on the un-aligned latents: the search, the bound and the vote share it
-    packed = codec.level_pack(z, thr)
-    codec._level_rows_align_checks(packed, shape)
-    idx, aidx, stat = AL._search_level_rows(packed, shape, keys_dev, mb, table, k)
-    host = torch.stack([idx, aidx, stat]).cpu().numpy()
-    idx_h, aidx_h, stat_h = host[0], host[1], host[2]
-    rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
-    rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]
-    bits = codec.extract_soft(AL.unalign(z, table, aidx_h[:, 0]), rows, mb, thr).bits
-    flags_h, bits_h, pairs = packed.flags.cpu().numpy(), bits.cpu().numpy(), len(keyring) * len(table)
-    lv = levels_from_planes(packed.planes.cpu().numpy()).reshape(B, *shape)
-    laws: Dict[Tuple[int, int], _SoftNullLaw] = {}                 # one dynamic programme per distinct (image, alignment) among the reported candidates
-
-    def law(b: int, a: int) -> _SoftNullLaw:
-        t = laws.get((b, a))
-        if t is None:                                              # W_t depends on the alignment: it moves elements between message positions
-            t = laws[(b, a)] = _SoftNullLaw(AL.apply(torch.from_numpy(lv[b]), table[a]).reshape(-1).numpy(), M)
-        return t
-
-    out = T._candidate_lists(idx_h, stat_h, flags_h, limit,
-                             lambda b, j, i, s: KeyCandidate(keyring.key_at(i), i, s, T.log10_p_any(law(b, int(aidx_h[b, j])).log10_bound(s), pairs),
-                                                             table[int(aidx_h[b, j])]),
-                             lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b]),
-                                                              c[0].alignment if named else None),
-                             refuse=False)
-    return out, aidx_h[:, 0], bits_h
+    return _detect(latents, keyring, mb, k, limit, l=1, levels=levels, aligns=aligns)
 
 
 def detect_latents_aligned_soft(latents, keyring: Keyring, message_length: int, aligns, *, levels: int = 15, k: int = 1,

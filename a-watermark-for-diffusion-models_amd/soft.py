@@ -127,21 +127,28 @@ def shared_records(key: bytes, nonce: bytes, msg_bytes: int, batch: int, device)
     return torch.from_numpy(row).to(device).expand(int(batch), -1).contiguous()
 
 
+def _default_table(z: torch.Tensor, l: int, levels: int, clip: float = 2.5) -> torch.Tensor:
+    """The table a decoder uses when it is given none: `uniform_thresholds` at l = 1, `window_thresholds` at l = 2 and 4"""
+    return uniform_thresholds(z, levels, clip) if l == 1 else window_thresholds(z, l, levels, clip)
+
+
+def _extract_shared_key(z: torch.Tensor, key: bytes, nonce: bytes, message_length: int, l: int, levels: int, clip: float, thresholds) -> codec.SoftVote:
+    """`extract_soft` (l = 1) and `extract_soft_l` (l = 2, 4)"""
+    M = int(message_length)
+    if M < 8 or M % 8 or M > 8 * codec.N.GSW_MSG_INLINE_MAX:
+        raise ValueError(f"the soft vote needs a message_length that is a multiple of 8 in 8..{8 * codec.N.GSW_MSG_INLINE_MAX}, got {message_length!r}")
+    thresholds = _default_table(z, l, levels, clip) if thresholds is None else thresholds.to(z.device)
+    records = shared_records(key, nonce, M // 8, z.shape[0], z.device)
+    vote = codec.extract_soft(z, records, M // 8, thresholds) if l == 1 else codec.extract_soft_l(z, records, M // 8, thresholds, l)
+    return vote._replace(matches=None)
+
+
 def extract_soft(latents: torch.Tensor, key: bytes, nonce: bytes, message_length: int, *, levels: int = 15, clip: float = 2.5,
                  thresholds: Optional[torch.Tensor] = None) -> codec.SoftVote:
     """`codec.extract_soft` for a batch under ONE key and nonce: latents [B, ...] on the device -> `codec.SoftVote` with matches = None (there
     is no message to compare with).  thresholds: float32 [levels] or [B, levels]; None: `uniform_thresholds(latents, levels, clip)`.
     message_length: a multiple of 8 up to 2048 bits; one cipher bit per element (l = 1)."""
-    M = int(message_length)
-    if M < 8 or M % 8 or M > 8 * codec.N.GSW_MSG_INLINE_MAX:
-        raise ValueError(f"the soft vote needs a message_length that is a multiple of 8 in 8..{8 * codec.N.GSW_MSG_INLINE_MAX}, got {message_length!r}")
-    z = latents
-    if thresholds is None:
-        thresholds = uniform_thresholds(z, levels, clip)
-    else:
-        thresholds = thresholds.to(z.device)
-    records = shared_records(key, nonce, M // 8, z.shape[0], z.device)
-    return codec.extract_soft(z, records, M // 8, thresholds)._replace(matches=None)
+    return _extract_shared_key(latents, key, nonce, message_length, 1, levels, clip, thresholds)
 
 
 def extract_soft_l(latents: torch.Tensor, key: bytes, nonce: bytes, message_length: int, l: int, *, levels: int = 15, clip: float = 2.5,
@@ -151,16 +158,7 @@ def extract_soft_l(latents: torch.Tensor, key: bytes, nonce: bytes, message_leng
     l = codec.check_window(l)
     if l == 1:
         return extract_soft(latents, key, nonce, message_length, levels=levels, clip=clip, thresholds=thresholds)
-    M = int(message_length)
-    if M < 8 or M % 8 or M > 8 * codec.N.GSW_MSG_INLINE_MAX:
-        raise ValueError(f"the soft vote needs a message_length that is a multiple of 8 in 8..{8 * codec.N.GSW_MSG_INLINE_MAX}, got {message_length!r}")
-    z = latents
-    if thresholds is None:
-        thresholds = window_thresholds(z, l, levels, clip)
-    else:
-        thresholds = thresholds.to(z.device)
-    records = shared_records(key, nonce, M // 8, z.shape[0], z.device)
-    return codec.extract_soft_l(z, records, M // 8, thresholds, l)._replace(matches=None)
+    return _extract_shared_key(latents, key, nonce, message_length, l, levels, clip, thresholds)
 
 
 def log10_p(score_total, wsq) -> float:

@@ -762,19 +762,10 @@ def trace_latents_keyed(latents, registry: KeyedRegistry, *, k: int = 1, fpr: fl
     return out
 
 
-def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
-                             fpr: float = 1e-6, tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
-    """`trace_latents_keyed` ranked by reliability-weighted margins (one cipher bit per element): latents [B, ...] on the device -> one
-    TraceResult per image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
-
-    Every lattice element votes with an integer level 0..levels taken from its magnitude -- thresholds: float32 [levels] or [B, levels],
-    None: `soft.uniform_thresholds(latents, levels, clip)`, scaled to each image's RMS.  One `codec.level_pack` launch, one search launch
-    (`codec.trace_keyed_soft_topk`); a candidate's score is sum_j level_j (1 - 2 (sign_j ^ codeword_j)), for records of one key the number
-    `trace_latents(..., reliability=levels)` ranks by.  The p-value is the Hoeffding bound `soft.log10_p(score, wsq)`, Bonferroni over the
-    records: given the levels, the bits of a key-independent image under ANY key are fair coins, so the bound is as valid across keys as
-    within one -- a bound, not the exact binomial tail of `trace_latents_keyed`.  `Candidate.agree` counts the bits of the soft vote under
-    the candidate's own record: one `codec.extract_soft` launch over the reported (image, candidate) pairs.
-    tamper_tile: as in `trace_latents_keyed`, on the packed sign row.  n (1 + P) may not exceed 1 048 576, P the bit length of `levels`."""
+def _trace_keyed_soft(latents, registry: KeyedRegistry, l: int, levels: int, clip: float, thresholds, k: int, fpr: float,
+                      tamper_tile: Optional[int]) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed_soft` (l = 1) and `trace_latents_keyed_soft_l` (l = 2, 4): one level packer, one search over the n l bits, the candidate lists,
+    and one soft vote over the reported (image, candidate) pairs for `Candidate.agree`"""
     import torch
     from . import soft as S
     limit = _log10_fpr(fpr)
@@ -782,14 +773,15 @@ def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 
     B = z.shape[0]
     n = z.numel() // max(B, 1)
     M, mb = registry.message_bits, registry.message_bytes
-    codec.vote_copies(n, M, 1)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    codec.vote_copies(n, M, l)                           # (a lattice the messages do not tile fails here, as extract_batch would)
     if thresholds is None:
-        thr = S.uniform_thresholds(z, levels, clip)
+        thr = S._default_table(z, l, levels, clip)
     else:
         thr = thresholds.to(device=z.device, dtype=torch.float32).contiguous()
+    shared = thr.dim() == (1 if l == 1 else 2)          # one table for all images
     rec_dev = registry.to_device(z.device)
-    rows = codec.level_pack(z, thr)
-    idx, score = codec.trace_keyed_soft_topk(rows, n, rec_dev, mb, k=k)
+    rows = codec.level_pack(z, thr) if l == 1 else codec.level_pack_l(z, thr, l)
+    idx, score = codec.trace_keyed_soft_topk(rows, n * l, rec_dev, mb, k=k)
     idx_h, score_h = _pairs_to_host(idx, score)
     flags_h, wsq_h, U = rows.flags.cpu().numpy(), rows.wsq.cpu().numpy(), len(registry)
     reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
@@ -803,12 +795,29 @@ def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 
     if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
         img = torch.tensor([b for b, _ in reported], device=z.device)
         rec = torch.tensor([c.index for _, c in reported], device=z.device)
-        vote = codec.extract_soft(z.reshape(B, -1)[img].contiguous(), rec_dev[rec].contiguous(), mb, thr if thr.dim() == 1 else thr[img].contiguous())
+        pairs = (z.reshape(B, -1)[img].contiguous(), rec_dev[rec].contiguous(), mb, thr if shared else thr[img].contiguous())
+        vote = codec.extract_soft(*pairs) if l == 1 else codec.extract_soft_l(*pairs, l)
         for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
             c.agree = int(a)
     if tamper_tile is not None:
-        _attach_tamper_maps(out, z, rows.signs, _best_records(out, registry.record_at), M, 1, tamper_tile, fpr)
+        _attach_tamper_maps(out, z, rows.signs, _best_records(out, registry.record_at), M, l, tamper_tile, fpr)
     return out
+
+
+def trace_latents_keyed_soft(latents, registry: KeyedRegistry, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
+                             fpr: float = 1e-6, tamper_tile: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed` ranked by reliability-weighted margins (one cipher bit per element): latents [B, ...] on the device -> one
+    TraceResult per image (best candidate first), or the ValueError the reference raises for that image (a saturated / NaN latent).
+
+    Every lattice element votes with an integer level 0..levels taken from its magnitude -- thresholds: float32 [levels] or [B, levels],
+    None: `soft.uniform_thresholds(latents, levels, clip)`, scaled to each image's RMS.  One `codec.level_pack` launch, one search launch
+    (`codec.trace_keyed_soft_topk`); a candidate's score is sum_j level_j (1 - 2 (sign_j ^ codeword_j)), for records of one key the number
+    `trace_latents(..., reliability=levels)` ranks by.  The p-value is the Hoeffding bound `soft.log10_p(score, wsq)`, Bonferroni over the
+    records: given the levels, the bits of a key-independent image under ANY key are fair coins, so the bound is as valid across keys as
+    within one -- a bound, not the exact binomial tail of `trace_latents_keyed`.  `Candidate.agree` counts the bits of the soft vote under
+    the candidate's own record: one `codec.extract_soft` launch over the reported (image, candidate) pairs.
+    tamper_tile: as in `trace_latents_keyed`, on the packed sign row.  n (1 + P) may not exceed 1 048 576, P the bit length of `levels`."""
+    return _trace_keyed_soft(latents, registry, 1, levels, clip, thresholds, k, fpr, tamper_tile)
 
 
 def trace_latents_keyed_soft_l(latents, registry: KeyedRegistry, l: int, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
@@ -824,42 +833,10 @@ def trace_latents_keyed_soft_l(latents, registry: KeyedRegistry, l: int, *, leve
     `Candidate.agree` counts the bits of the soft vote under the candidate's own record: one `codec.extract_soft_l` launch over the
     reported (image, candidate) pairs.  n l (1 + P) may not exceed 1 048 576, P the bit length of `levels`: the search refuses beyond
     (ValueError).  l = 1 is refused: that is `trace_latents_keyed_soft`."""
-    import torch
-    from . import soft as S
     l = codec.check_window(l)
     if l == 1:
         raise ValueError("l = 1 has no window bits: the level-weighted search across keys at l = 1 is trace_latents_keyed_soft (--keyed_reliability)")
-    limit = _log10_fpr(fpr)
-    z = latents.contiguous()
-    B = z.shape[0]
-    n = z.numel() // max(B, 1)
-    M, mb = registry.message_bits, registry.message_bytes
-    codec.vote_copies(n, M, l)                           # (a lattice the messages do not tile fails here, as extract_batch would)
-    nb = n * l
-    if thresholds is None:
-        thr = S.window_thresholds(z, l, levels, clip)
-    else:
-        thr = thresholds.to(device=z.device, dtype=torch.float32).contiguous()
-    rec_dev = registry.to_device(z.device)
-    rows = codec.level_pack_l(z, thr, l)
-    idx, score = codec.trace_keyed_soft_topk(rows, nb, rec_dev, mb, k=k)
-    idx_h, score_h = _pairs_to_host(idx, score)
-    flags_h, wsq_h, U = rows.flags.cpu().numpy(), rows.wsq.cpu().numpy(), len(registry)
-    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
-
-    def candidate(b, j, i, s):
-        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U))
-        reported.append((b, c))
-        return c
-
-    out = _candidate_lists(idx_h, score_h, flags_h, limit, candidate, _trace_result)
-    if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
-        img = torch.tensor([b for b, _ in reported], device=z.device)
-        rec = torch.tensor([c.index for _, c in reported], device=z.device)
-        vote = codec.extract_soft_l(z.reshape(B, -1)[img].contiguous(), rec_dev[rec].contiguous(), mb, thr if thr.dim() == 2 else thr[img].contiguous(), l)
-        for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
-            c.agree = int(a)
-    return out
+    return _trace_keyed_soft(latents, registry, l, levels, clip, thresholds, k, fpr, None)
 
 
 # ===================================================================================================================== front end
