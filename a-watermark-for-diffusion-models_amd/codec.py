@@ -937,6 +937,88 @@ def vote_tiled(packed: torch.Tensor, keys: torch.Tensor, weights: torch.Tensor, 
     return bits, score, wsum
 
 
+# ------------------------------------------------------------------------------------------------ robust decode in one launch (tile weights times reliability levels)
+ROBUST_MAX_ITERS = 8
+ROBUST_LDS_CAP = 131072         # bytes of LDS one image's decode may take (csrc/gswm_robust_plan.h)
+
+
+class RobustVote(NamedTuple):
+    """What `decode_robust` returns, all on the rows' device: the last round of the decode"""
+    bits: torch.Tensor      # uint8 [B, msg_bits / 8], MSB first, bit t = (score > 0)
+    score: torch.Tensor     # int32 [B, msg_bits], sum of level weight (2 p - 1) over the copies of a message bit
+    wsum: torch.Tensor      # int32 [B, msg_bits], the same sum of level weight alone
+    excess: torch.Tensor    # int32 [B, th, tw], level-weighted agreement minus disagreement of a tile with the returned bits
+    wsq: torch.Tensor       # int32 [B, th, tw], sum of level^2 over a tile
+    weights: torch.Tensor   # int32 [B, th, tw], the tile weights the last vote used (ones when iters = 0)
+
+
+def robust_lds_bytes(n_bits: int, P: int, tiles: int, msg_bits: int, level_rounds: bool) -> int:
+    """The LDS one image's decode takes: the row padded to whole 64-byte blocks, P planes, the int32 tile weights (and the tiles' sums of levels
+    and of squared levels when a round votes with the levels), the message bytes padded to a dword -- csrc/gswm_robust_plan.h's layout"""
+    rowbytes = n_bits // 8
+    return 64 * ((rowbytes + 63) // 64) + P * rowbytes + 4 * tiles * (3 if level_rounds else 1) + (msg_bits // 8 + 3) // 4 * 4
+
+
+def _small_int(v, name: str, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{name} must be an int in {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
+def decode_robust(signs: torch.Tensor, planes: Optional[torch.Tensor], keys: torch.Tensor, msg_bits: int, shape: Sequence[int], l: int = 1, tile: int = 8,
+                  iters: int = 2, sign_rounds: int = 0) -> RobustVote:
+    """The robust decode of every image under its OWN key in ONE launch (gsw_decode_robust): `iters` + 1 rounds of vote, map and weights, every
+    cipher bit voting with its reliability level times the weight of its tile.
+
+    signs: uint8 [B, n l / 8] (`quant_pack` / `level_pack[_l]`), planes: uint8 [B, P, n l / 8] with P in 1..4 (`LevelRows.planes`) or None for
+    unit levels, keys: uint8 [B, 48] as `vote_tiled`, shape: the (C, h, w) of the lattice.  With p_j the decrypted bit, lev_j the level the
+    planes hold and L_j = 1 in round r < sign_rounds, lev_j after, the weights start at 1 and round r = 0 .. iters computes
+    score[t] = sum over j = t (mod msg_bits) of L_j weight[tile of j // l] (2 p_j - 1), wsum[t] the same sum without the sign, bit t = score[t] > 0
+    (a tie, or no weight at all, gives 0), excess[tile] = sum over the tile's bits of L_j (+1 where p_j agrees with its message bit, -1 where not),
+    wsq[tile] = sum of L_j^2, and the next weights max(0, excess - isqrt(wsq)).  Returns the `RobustVote` of the last round.
+    planes = None: bits, score and wsum of `tamper.extract_robust(..., iters=iters)` and excess = 2 agree - n_t.  iters = 0, sign_rounds = 0: the
+    vote of `extract_soft[_l]`; iters = 0, sign_rounds = 1: the plain vote.
+    Raises IndexError when n l is not a multiple of msg_bits, ValueError for what `vote_tiled` refuses, for P outside 0..4, iters outside 0..8,
+    sign_rounds outside (0, 1), n l (1 + P) > 1 048 576, copies Lmax^2 n_t > 2^31 - 1 (Lmax = max(1, 2^P - 1), n_t = C tile^2 l, copies = n l /
+    msg_bits: a score would not fit int32) and an LDS footprint above 131 072 bytes; RuntimeError for host tensors (there is no CPU fallback).
+    All of it before any launch."""
+    iters = _small_int(iters, "iters", 0, ROBUST_MAX_ITERS)
+    sign_rounds = _small_int(sign_rounds, "sign_rounds", 0, 1)
+    B, C, h, w, l, tile, M, th, tw = _tiled_operands(signs, keys, msg_bits, shape, l, tile)
+    P = 0
+    if planes is not None:
+        _need_gpu(planes, "planes")
+        if planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != signs.shape[1] or not 1 <= planes.shape[1] <= 4:
+            raise ValueError(f"planes must be uint8 [{B}, P, {signs.shape[1]}] with P in 1..4 (`level_pack`), or None for unit levels")
+        _same_device(planes, signs, "planes")
+        P = planes.shape[1]
+    nb = C * h * w * l
+    if nb > ROW_MAX_BITS or nb * (1 + P) > ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {nb} bits with {P} level planes is beyond the decode's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
+    if nb % M:
+        raise IndexError("string index out of range")
+    lmax, n_t, copies = max(1, (1 << P) - 1), C * tile * tile * l, nb // M
+    if copies * lmax * lmax * n_t > 2**31 - 1:
+        raise ValueError(f"copies Lmax^2 n_t = {copies} x {lmax}^2 x {n_t} = {copies * lmax * lmax * n_t} does not fit int32: a bit's vote is at most "
+                         f"Lmax = max(1, 2^P - 1) times a weight of at most Lmax n_t, n_t = C tile^2 l, summed over copies = n_bits / msg_bits")
+    lds = robust_lds_bytes(nb, P, th * tw, M, P > 0 and iters >= sign_rounds)
+    if lds > ROBUST_LDS_CAP:
+        raise ValueError(f"the decode would take {lds} bytes of LDS (64 ceil(n_bits / 512) + P n_bits / 8 + 4 tiles (3 with levels, else 1) + msg_bits / 8), "
+                         f"the cap is {ROBUST_LDS_CAP}")
+    dev = signs.device
+    bits = torch.empty((B, M // 8), dtype=torch.uint8, device=dev)
+    score = torch.empty((B, M), dtype=torch.int32, device=dev)
+    wsum = torch.empty((B, M), dtype=torch.int32, device=dev)
+    excess = torch.empty((B, th, tw), dtype=torch.int32, device=dev)
+    wsq = torch.empty((B, th, tw), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, th, tw), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().gsw_decode_robust(signs.data_ptr(), planes.data_ptr() if planes is not None else None, P, B, C, h, w, l, tile, keys.data_ptr(), M, iters,
+                                          sign_rounds, bits.data_ptr(), score.data_ptr(), wsum.data_ptr(), excess.data_ptr(), wsq.data_ptr(), weights.data_ptr(),
+                                          _stream_ptr()))
+    return RobustVote(bits, score, wsum, excess, wsq, weights)
+
+
 # ------------------------------------------------------------------------------------------------ X2 / G1 elementwise
 def ddim_step(x: torch.Tensor, model_out: torch.Tensor, a: float, b: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = a*x + b*model_out (fp32 math, one rounding). out may be x (in place)."""

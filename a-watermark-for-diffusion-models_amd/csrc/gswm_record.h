@@ -1,7 +1,7 @@
 // gswm_record.h -- "an image under its own record", the decisions every kernel family of that kind shares (gswm_codec_keyed.inc,
 // gswm_codec_soft.inc, gswm_keyed.hip, gswm_tamper.hip): the record layout and its operand check, the message repeated over a row, the
 // record's keystream in LDS, and the tail of a per-image vote.  The block function and the counter rule are gswm_chacha.h's.
-// Include after <hip/hip_runtime.h> and include/gswm.h.  A host compiler (gswm_search_plan.h's table program) sees the layout and the operand check only.
+// Include after <hip/hip_runtime.h> and include/gswm.h.  A host compiler (gswm_search_plan.h's table program, gswm_robust_plan.h's sweep) sees the layout, the operand check and vote_log2s only.
 #pragma once
 #include <stdint.h>
 
@@ -25,6 +25,14 @@ static inline int records_check(const uint8_t* records_dev, int64_t record_strid
 static inline int records_check32(const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records) {
     if (record_stride > (int64_t)0x7FFFFFF0) return GSW_ERR_BAD_ARG;
     return records_check(records_dev, record_stride, msg_bytes, n_records);
+}
+
+// Lanes per message bit of a per-image vote (its tail is below): enough to fill the workgroup for short messages, at most 8 (a wave then
+// still owns whole bytes) and at most the copies.  Host arithmetic: gswm_robust_plan.h decides with it.
+static inline int vote_log2s(int64_t msg_bits, int64_t copies, int wg) {
+    int log2s = 0;
+    while (log2s < 3 && (msg_bits << log2s) < wg && ((int64_t)2 << log2s) <= copies) ++log2s;
+    return log2s;
 }
 
 #ifdef __HIPCC__      // device code from here on
@@ -60,14 +68,6 @@ __device__ __forceinline__ void record_keystream_to_lds(const uint8_t* __restric
 }
 
 // ---- the tail of a per-image vote: S = 1 << log2s adjacent lanes per message bit, the message byte from the wave's ballot
-
-// Lanes per message bit: enough to fill the workgroup for short messages, at most 8 (a wave then still owns whole bytes) and at most
-// the copies.
-static inline int vote_log2s(int64_t msg_bits, int64_t copies, int wg) {
-    int log2s = 0;
-    while (log2s < 3 && (msg_bits << log2s) < wg && ((int64_t)2 << log2s) <= copies) ++log2s;
-    return log2s;
-}
 
 // Bit (i S) of the wave's ballot above lane `lane` is message bit (t of that lane) + i: the byte that starts at the lane's bit, MSB first.
 __device__ __forceinline__ uint32_t ballot_byte(uint64_t ball, uint32_t lane, uint32_t log2s) {

@@ -30,6 +30,7 @@
 // Kernels
 //   gsw_tile_agree_kernel : [B] workgroups of 256
 //   gsw_vote_tiled_kernel : [B] workgroups of 256
+//   gsw_decode_robust_kernel (gswm_tamper_soft.inc) : the vote, the map and the weights of every round in one launch, with reliability levels
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -240,3 +241,5 @@ int gsw_vote_tiled(const uint8_t* packed_dev, int B, int C, int h, int w, int l,
 }
 
 }  // extern "C"
+
+#include "gswm_tamper_soft.inc"   // gsw_decode_robust: the rounds of the robust decode in one launch, tile weights times reliability levels

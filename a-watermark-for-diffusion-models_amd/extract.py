@@ -68,6 +68,23 @@ def _window_soft_wanted(args, l: int) -> int:
     return levels
 
 
+def _robust_soft_wanted(args) -> int:
+    """--robust_soft L as a number of levels (0: not asked for); it is a decoder of its own and is refused, by name, next to every other one"""
+    levels = getattr(args, "robust_soft", 0) or 0
+    if not levels:
+        return 0
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= int(levels) <= codec.SOFT_MAX_LEVELS:
+        raise ValueError(f"--robust_soft takes a number of levels in 1..{codec.SOFT_MAX_LEVELS}, got {levels!r}")
+    for flag in ("soft", "robust"):
+        if int(getattr(args, flag, 0) or 0):
+            raise ValueError(f"--robust_soft cannot be combined with --{flag} 1: it weights by levels AND tiles, in a decoder of its own")
+    if int(getattr(args, "window_soft", 0) or 0):
+        raise ValueError("--robust_soft cannot be combined with --window_soft: it weights by levels AND tiles, in a decoder of its own")
+    if getattr(args, "align", None) not in (None, "none"):
+        raise ValueError("--robust_soft cannot be combined with --align: the alignment search reads the reference's vote")
+    return int(levels)
+
+
 class _AlignedBits(str):
     """A recovered bit string that also says under which alignment of the lattice it was read (--align)"""
     alignment = None
@@ -116,7 +133,14 @@ def _alignment_note(r) -> str:
 def _vote(z, args, m: int, l: int):
     """(bits, flags) of the reference's vote, with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations), with
     --soft 1 of the level-weighted vote (soft.extract_soft, thresholds scaled to each image's RMS), with --window_soft L at --l 2 / 4 of the
-    vote with a level per cipher bit (soft.extract_soft_l, soft.window_thresholds)"""
+    vote with a level per cipher bit (soft.extract_soft_l, soft.window_thresholds), with --robust_soft L of the robust decode with levels
+    (tamper.extract_robust_soft: --tile, --iters, --sign_rounds, at any --l)"""
+    robust_levels = _robust_soft_wanted(args)
+    if robust_levels:
+        from . import tamper
+        res = tamper.extract_robust_soft(z, args.key, args.nonce, m, l=l, tile=int(getattr(args, "tile", 8)), iters=int(getattr(args, "iters", 2)),
+                                         levels=robust_levels, clip=float(getattr(args, "soft_clip", 2.5)), sign_rounds=int(getattr(args, "sign_rounds", 1)))
+        return res.bits, res.flags
     window_levels = _window_soft_wanted(args, l)
     if window_levels:
         from . import soft
@@ -152,6 +176,7 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     l = _window(args)
     z = _to_device_latents(reversed_latents, device)
     m = int(args.message_length)
+    robust_soft = _robust_soft_wanted(args)
     if _align_wanted(args):                                  # the alignments act on the lattice: the search needs the image's [C, h, w]
         shape = tuple(int(d) for d in np.shape(reversed_latents))
         if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
@@ -160,10 +185,10 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
         if isinstance(r, Exception):
             raise r
         return r
-    if int(getattr(args, "robust", 0) or 0):                 # the tiles are cut from the lattice: the weighted vote needs the image's [C, h, w]
+    if robust_soft or int(getattr(args, "robust", 0) or 0):  # the tiles are cut from the lattice: the weighted vote needs the image's [C, h, w]
         shape = tuple(int(d) for d in np.shape(reversed_latents))
         if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
-            raise ValueError(f"--robust 1 needs the latents of ONE image as [..., C, h, w] (got {shape})")
+            raise ValueError(f"{'--robust_soft' if robust_soft else '--robust 1'} needs the latents of ONE image as [..., C, h, w] (got {shape})")
         z = z.view(1, *shape[-3:])
     bits, flags = _vote(z, args, m, l)
     f = int(flags[0].item())
@@ -179,6 +204,7 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
     Mirrors the per-image try/except of extract.py:148-155."""
     l = _window(args)
     m = int(args.message_length)
+    _robust_soft_wanted(args)
     if _align_wanted(args):
         return _vote_aligned(latents.contiguous(), args, m, l)
     bits, flags = _vote(latents.contiguous(), args, m, l)
@@ -681,6 +707,10 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.robust_soft:
+                for flag, on in (("--soft 1", a.soft), ("--robust 1", a.robust), ("--window_soft", a.window_soft), ("--align", a.align != "none")):
+                    if on:
+                        self.error(f"--robust_soft cannot be combined with {flag}: it weights by levels AND tiles, in a decoder of its own")
             if a.soft and a.robust:
                 self.error("--soft 1 cannot be combined with --robust 1: level weights and tile weights are separate votes")
             if a.soft and a.l != 1:
@@ -729,6 +759,15 @@ def build_parser():
                         help="(not a reference flag) with --l 2 or 4: decode with the soft-decision vote for multi-bit windows (soft.extract_soft_l), every "
                              "cipher bit of a lattice element votes with one of L (1..15) levels taken from its distance to the quantiser boundaries that "
                              "would flip it; 0: the reference's vote.  Not with --soft 1, --robust 1 or --align")
+    parser.add_argument("--robust_soft", type=int, default=0, choices=range(0, 16), metavar="L",
+                        help="(not a reference flag) decode with the robust decode with levels (tamper.extract_robust_soft): every cipher bit votes with one "
+                             "of L (1..15) reliability levels times the weight of its tile, the tiles re-weighted by their agreement with the decoded message "
+                             "--iters times, in one launch; --tile, --iters, --sign_rounds, at any --l; 0: the reference's vote.  Not with --soft 1, --robust 1, "
+                             "--window_soft or --align")
+    parser.add_argument("--iters", type=int, default=2, choices=range(0, 9), metavar="I", help="(not a reference flag) --robust_soft: re-weighting rounds after the first vote (0..8)")
+    parser.add_argument("--sign_rounds", type=int, default=1, choices=[0, 1],
+                        help="(not a reference flag) --robust_soft: 1 takes the first vote at unit levels (safe against a pasted region louder than the image), "
+                             "0 lets the levels count from the start (stronger where the damage is quiet)")
     parser.add_argument("--soft_levels", type=int, default=15, choices=range(1, 16), metavar="LEVELS", help="(not a reference flag) reliability levels of --soft 1 (1..15)")
     parser.add_argument("--soft_clip", type=float, default=2.5,
                         help="(not a reference flag) --soft 1: the top level starts at this many times the image's RMS")

@@ -8,7 +8,7 @@ built once, a batch of independent images moves through the loops together, and 
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -16,6 +16,18 @@ from . import codec
 from .ddim import DDIMSchedule, DPMSolverSchedule, ddim_invert_extract, ddim_sample, ddim_invert, dpms_sample
 
 SAMPLERS = ("ddim", "dpmpp_2m", "dpmpp_2m_karras")
+
+
+class RobustRecordsVote(NamedTuple):
+    """What `verify_records(..., robust_levels=L)` returns: (bits, flags, matches) as the other forms, then `codec.RobustVote`'s fields of the last round"""
+    bits: torch.Tensor      # uint8 [B, msg_bytes]
+    flags: torch.Tensor     # int32 [B]
+    matches: torch.Tensor   # int32 [B], recovered bits equal to the record's message
+    score: torch.Tensor     # int32 [B, 8 msg_bytes]
+    wsum: torch.Tensor      # int32 [B, 8 msg_bytes]
+    excess: torch.Tensor    # int32 [B, th, tw]
+    wsq: torch.Tensor       # int32 [B, th, tw]
+    weights: torch.Tensor   # int32 [B, th, tw]
 
 
 class GaussianShadingPipeline:
@@ -58,12 +70,31 @@ class GaussianShadingPipeline:
 
     # X2 + X3-X5 + X6 against each image's own record
     def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False, soft: bool = False,
-                       levels: int = 15, clip: float = 2.5, window_levels: Optional[int] = None):
+                       levels: int = 15, clip: float = 2.5, window_levels: Optional[int] = None, robust_levels: Optional[int] = None, tile: int = 8,
+                       iters: int = 2, sign_rounds: int = 1):
         """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`.
         soft=True: the `codec.SoftVote` (bits, flags, matches, score, wsum, wsq) of `codec.extract_soft` instead, every element weighted by
         one of `levels` reliability levels with thresholds scaled to its image's RMS (`soft.uniform_thresholds(z, levels, clip)`); l = 1 only.
         window_levels=L at the pipeline's l = 2 or 4: the `codec.SoftVote` of `codec.extract_soft_l`, every cipher bit weighted by one of L
-        levels (`soft.window_thresholds(z, l, L, clip)`); not with soft=True, and not at l = 1 (that is soft=True)."""
+        levels (`soft.window_thresholds(z, l, L, clip)`); not with soft=True, and not at l = 1 (that is soft=True).
+        robust_levels=L in 1..15, at the pipeline's l: the `RobustRecordsVote` of the one-launch robust decode (`codec.level_pack[_l]` with the
+        default table of L levels for this l, then `codec.decode_robust` under each record's own key with `tile`, `iters` and `sign_rounds`;
+        matches from `codec.bit_matches` against each record's message); not with soft=True or window_levels."""
+        if robust_levels is not None:
+            if soft:
+                raise ValueError("robust_levels cannot be combined with soft=True: the robust decode weights by levels AND tiles, in a launch of its own")
+            if window_levels is not None:
+                raise ValueError("robust_levels cannot be combined with window_levels: the robust decode weights by levels AND tiles, in a launch of its own")
+            from . import soft as S
+            robust_levels = S._check_table(robust_levels, clip)[0]
+            iters = codec._small_int(iters, "iters", 0, codec.ROBUST_MAX_ITERS)
+            sign_rounds = codec._small_int(sign_rounds, "sign_rounds", 0, 1)
+            if isinstance(tile, bool) or tile not in codec.TILES:
+                raise ValueError(f"tile must be one of {codec.TILES} (lattice elements per tile edge), got {tile!r}")
+            B, _, msg_bytes = codec._records_operand(records, msg_bytes)
+            z = ddim_invert(self.eps_model, x0, self._uncond(x0.shape[0]), self.schedule)
+            res = self._robust_records(z, records, B, msg_bytes, robust_levels, clip, tile, iters, sign_rounds)
+            return (*res, z) if return_latents else res
         if soft and self.l != 1:
             raise ValueError(f"soft=True cannot be combined with l = {self.l}: reliability levels are defined for one cipher bit per element")
         if window_levels is not None:
@@ -82,6 +113,21 @@ class GaussianShadingPipeline:
         else:
             res = codec.extract_records(z, records, msg_bytes, l=self.l)
         return (*res, z) if return_latents else res
+
+    def _robust_records(self, z: torch.Tensor, records: torch.Tensor, B: int, msg_bytes: int, levels: int, clip: float, tile: int, iters: int,
+                        sign_rounds: int) -> RobustRecordsVote:
+        """`verify_records(robust_levels=...)` after the inversion: one pack launch, one decode launch, the matches per record"""
+        from . import soft as S
+        if z.dim() != 4 or z.shape[0] != B:
+            raise ValueError(f"z must be [{B}, C, h, w] latents, one image per record (got {tuple(z.shape)})")
+        z = z.contiguous()
+        table = S._default_table(z, self.l, levels, clip)
+        rows = codec.level_pack(z, table) if self.l == 1 else codec.level_pack_l(z, table, self.l)
+        keys = records[:, :codec.KEYED_RECORD_HEAD].contiguous()
+        v = codec.decode_robust(rows.signs, rows.planes, keys, 8 * msg_bytes, tuple(int(s) for s in z.shape[1:]), self.l, tile, iters, sign_rounds)
+        msgs = records[:, codec.KEYED_RECORD_HEAD:codec.KEYED_RECORD_HEAD + msg_bytes].cpu().numpy()
+        matches = torch.cat([codec.bit_matches(v.bits[b:b + 1].clone(), 8 * msg_bytes, msgs[b].tobytes()) for b in range(B)])
+        return RobustRecordsVote(v.bits, rows.flags, matches, v.score, v.wsum, v.excess, v.wsq, v.weights)
 
     # G1
     def _uncond(self, batch: int) -> torch.Tensor:

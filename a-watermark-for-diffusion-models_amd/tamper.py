@@ -16,6 +16,10 @@ standard deviation of the null, an exact integer that needs no threshold -- and 
 decoded message, weights, weighted vote.  The weighted score is selected on the data and is NOT a test statistic: attribution
 (`trace`) keeps the unweighted p-values.
 
+With levels (`extract_robust_soft`).  The same alternation with every cipher bit voting at its reliability level (`soft`) times the weight of its tile,
+all rounds in ONE launch (`codec.decode_robust`, csrc/gswm_tamper_soft.inc): a tile's weight is `soft_weights` = max(0, excess - isqrt(wsq)), its
+level-weighted excess agreement over one standard deviation of its null, which is `default_weights` at unit levels.  DESIGN.md section 4.24.
+
 Everything that runs per lattice bit is a HIP kernel (csrc/gswm_tamper.hip); the host sees [th, tw] counts.  DESIGN.md section 4.14.
 """
 from __future__ import annotations
@@ -24,7 +28,7 @@ import math
 import os
 from dataclasses import dataclass
 from fractions import Fraction
-from typing import List, Optional, Tuple, Union
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 
@@ -194,6 +198,75 @@ def extract_robust(latents, key: bytes, nonce: bytes, message_length: int, *, l:
         bits, score, wsum = codec.vote_tiled(packed, keys, default_weights(agree, n_t), M, shape, l, tile)
         agree = codec.tile_agreement(packed, keys, bits, M, shape, l, tile)
     return bits, flags, score, wsum, agree
+
+
+def soft_weights(excess, wsq):
+    """max(0, excess - isqrt(wsq)) as int32: the weight rule of `codec.decode_robust`, a tile's level-weighted excess agreement over one
+    standard deviation of its null, for torch tensors (stays on their device) or anything NumPy reads.  With unit levels excess = 2 agree - n_t
+    and wsq = n_t: `default_weights(agree, n_t)`.  wsq must be in 0..2^31 - 1; the square root is the exact floor."""
+    try:
+        import torch
+    except ImportError:                                      # pragma: no cover
+        torch = None
+    if torch is not None and isinstance(excess, torch.Tensor):
+        q = torch.as_tensor(wsq, device=excess.device).to(torch.int64)
+        if bool(((q < 0) | (q > 2**31 - 1)).any()):
+            raise ValueError("wsq must be in 0..2^31 - 1")
+        r = q.to(torch.float64).sqrt().to(torch.int64)       # exact below 2^52; the two corrections keep it so whatever sqrt rounds to
+        r = r - (r * r > q).to(torch.int64)
+        r = r + ((r + 1) * (r + 1) <= q).to(torch.int64)
+        return (excess.to(torch.int64) - r).clamp_(min=0).to(torch.int32)
+    q = np.asarray(wsq).astype(np.int64)
+    if ((q < 0) | (q > 2**31 - 1)).any():
+        raise ValueError("wsq must be in 0..2^31 - 1")
+    r = np.sqrt(q.astype(np.float64)).astype(np.int64)
+    r = r - (r * r > q)
+    r = r + ((r + 1) * (r + 1) <= q)
+    return np.maximum(np.asarray(excess).astype(np.int64) - r, 0).astype(np.int32)
+
+
+class RobustSoftVote(NamedTuple):
+    """What `extract_robust_soft` returns, all on the latents' device: `codec.RobustVote`'s fields of the last round, and the packer's flags"""
+    bits: "torch.Tensor"      # uint8 [B, M / 8]
+    score: "torch.Tensor"     # int32 [B, M]
+    wsum: "torch.Tensor"      # int32 [B, M]
+    excess: "torch.Tensor"    # int32 [B, th, tw]
+    wsq: "torch.Tensor"       # int32 [B, th, tw]
+    weights: "torch.Tensor"   # int32 [B, th, tw]
+    flags: "torch.Tensor"     # int32 [B], GSW_FLAG_*, as `extract_batch`
+
+
+def extract_robust_soft(latents, key: bytes, nonce: bytes, message_length: int, *, l: int = 1, tile: int = 8, iters: int = 2, levels: int = 15,
+                        clip: float = 2.5, thresholds=None, sign_rounds: int = 1) -> RobustSoftVote:
+    """Decode latents [B, C, h, w] with tile weights AND reliability levels, in two launches: `codec.level_pack` / `level_pack_l` (the row and the
+    level planes; the table `soft`'s default for this l when `thresholds` is None) and `codec.decode_robust` (all `iters` + 1 rounds).
+    sign_rounds = 1 (default) takes the first round at unit levels: a pasted region louder than the watermarked rest gets the top levels and
+    would wreck a first vote that listens to them; sign_rounds = 0 lets the levels count from the start, which is stronger where the damage is
+    quiet.  levels = 0 packs with `codec.quant_pack` and passes no planes: the two-launch form of `extract_robust`.
+    thresholds: float32 [levels] / [B, levels] (l = 1) or [l, levels] / [B, l, levels] on the latents' device; its own width replaces `levels`."""
+    from . import soft
+    shape = _lattice(latents)
+    codec._check_key_nonce(key, nonce)
+    l = codec.check_window(l)
+    M = int(message_length)
+    codec.vote_copies(shape[0] * shape[1] * shape[2], M, l)
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= int(levels) <= codec.SOFT_MAX_LEVELS:
+        raise ValueError(f"levels must be an int in 0..{codec.SOFT_MAX_LEVELS} (0: unit levels), got {levels!r}")
+    iters = codec._small_int(iters, "iters", 0, codec.ROBUST_MAX_ITERS)
+    sign_rounds = codec._small_int(sign_rounds, "sign_rounds", 0, 1)
+    if int(levels) == 0 and thresholds is not None:
+        raise ValueError("levels = 0 votes at unit levels and takes no thresholds")
+    z = latents.contiguous()
+    keys = keys_tensor([(key, nonce)] * z.shape[0], z.device)
+    if int(levels) == 0:
+        signs, flags = codec.quant_pack(z, l)
+        planes = None
+    else:
+        table = soft._default_table(z, l, int(levels), clip) if thresholds is None else thresholds.to(z.device)
+        rows = codec.level_pack(z, table) if l == 1 else codec.level_pack_l(z, table, l)
+        signs, planes, flags = rows.signs, rows.planes, rows.flags
+    v = codec.decode_robust(signs, planes, keys, M, shape, l, tile, iters, sign_rounds)
+    return RobustSoftVote(v.bits, v.score, v.wsum, v.excess, v.wsq, v.weights, flags)
 
 
 # ===================================================================================================================== files

@@ -824,6 +824,35 @@ int gsw_key_search_soft_topk(const uint8_t* signs_dev, const uint8_t* planes_dev
 int gsw_level_rows_align(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int B, int C, int H, int W, const int32_t* aligns_dev, int A,
                          uint8_t* out_signs_dev, uint8_t* out_planes_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Robust decode in one launch, tile weights times reliability levels: the rounds of the tile-weighted vote
+ * (gsw_vote_tiled, gsw_tile_agree and the weight rule between them) with every cipher bit voting at its reliability level.
+ * Additive: gsw_version() stays 500.
+ *
+ *   signs_dev  : [B, Nb / 8], gsw_quant_pack's / gsw_level_pack[_l]'s row for the [C, h, w] lattice at window l, Nb = C h w l; 4-byte aligned
+ *   planes_dev : [B, P, Nb / 8], gsw_level_pack[_l]'s planes over the same Nb bits, plane k = bit k of the level; 4-byte aligned; P in 0 .. 4,
+ *                with P = 0 the pointer is not read and every level is 1
+ *   keys_dev   : [B, 48], key[32] | nonce16[16] PER IMAGE, 4-byte aligned, as gsw_vote_tiled
+ *   iters      : I in 0 .. 8, the rounds after the first;  sign_rounds : W in {0, 1}, the rounds that vote at unit levels before the levels count
+ * With p_j = q_j ^ ks_j, lev_j = sum_k 2^k plane_k[j], L_j = 1 in round r < W and lev_j after, wgt = 1 in round 0, for r = 0 .. I:
+ *   score[t]    = sum over j = t (mod msg_bits) of L_j wgt[tile(j / l)] (2 p_j - 1),  wsum[t] = the same sum without the sign,
+ *   bit_t       = score[t] > 0 (a tie or no weight at all gives 0),
+ *   excess[tau] = sum over j in tile tau of L_j (1 - 2 (p_j ^ bit_(j mod msg_bits))),  wsq[tau] = sum over j in tau of L_j^2,
+ *   wgt[tau]   <- max(0, excess[tau] - isqrt(wsq[tau])), isqrt the exact floor square root.
+ * Outputs of round I: bits_dev uint8 [B, msg_bits / 8] MSB first, score_dev and wsum_dev int32 [B, msg_bits], excess_dev, wsq_dev and weights_dev
+ * int32 [B, h / T, w / T]; weights is what the last vote used (ones when I = 0).  Every element of every output is written; the results are exact
+ * integers and do not depend on the launch geometry.  One workgroup per image; nothing visits global memory between the rounds.
+ * With P = 0, bits / score / wsum are those of I rounds of gsw_vote_tiled under max(0, 2 agree - n_t - isqrt(n_t)) and (excess + n_t) / 2 is
+ * gsw_tile_agree's count against the returned bits; with I = 0, W = 0 they are gsw_extract_soft[_l]'s; with I = 0, W = 1 the plain vote's.
+ * GSW_ERR_BAD_ARG: as gsw_vote_tiled, and P outside 0..4, iters outside 0..8, sign_rounds outside {0, 1}, planes_dev null or misaligned with P > 0.
+ * GSW_ERR_UNSUPPORTED: as gsw_vote_tiled's lattice checks, and Nb (1 + P) > 1 048 576, (Nb / msg_bits) Lmax^2 n_t > INT32_MAX with
+ * Lmax = max(1, 2^P - 1) and n_t = C T T l (a bit's vote is at most Lmax times a weight of at most Lmax n_t), or an LDS footprint
+ * 64 ceil(Nb / 512) + P Nb / 8 + 4 tiles (1 or 3) + msg_bits / 8 above 131 072 bytes.  GSW_ERR_RAGGED: Nb % msg_bits != 0.  Every refusal
+ * happens before any launch. */
+int gsw_decode_robust(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int B, int C, int h, int w, int l, int tile, const uint8_t* keys_dev,
+                      int msg_bits, int iters, int sign_rounds, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* excess_dev,
+                      int32_t* wsq_dev, int32_t* weights_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
