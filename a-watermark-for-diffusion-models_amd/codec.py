@@ -939,7 +939,7 @@ def vote_tiled(packed: torch.Tensor, keys: torch.Tensor, weights: torch.Tensor, 
 
 # ------------------------------------------------------------------------------------------------ robust decode in one launch (tile weights times reliability levels)
 ROBUST_MAX_ITERS = 8
-ROBUST_LDS_CAP = 131072         # bytes of LDS one image's decode may take (csrc/gswm_robust_plan.h)
+ROBUST_LDS_CAP = 131072         # bytes of LDS one image's decode may take (csrc/gswm_tamper_plan.h)
 
 
 class RobustVote(NamedTuple):
@@ -954,7 +954,7 @@ class RobustVote(NamedTuple):
 
 def robust_lds_bytes(n_bits: int, P: int, tiles: int, msg_bits: int, level_rounds: bool) -> int:
     """The LDS one image's decode takes: the row padded to whole 64-byte blocks, P planes, the int32 tile weights (and the tiles' sums of levels
-    and of squared levels when a round votes with the levels), the message bytes padded to a dword -- csrc/gswm_robust_plan.h's layout"""
+    and of squared levels when a round votes with the levels), the message bytes padded to a dword -- csrc/gswm_tamper_plan.h's layout"""
     rowbytes = n_bits // 8
     return 64 * ((rowbytes + 63) // 64) + P * rowbytes + 4 * tiles * (3 if level_rounds else 1) + (msg_bits // 8 + 3) // 4 * 4
 

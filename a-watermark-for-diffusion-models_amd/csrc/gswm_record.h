@@ -1,7 +1,7 @@
 // gswm_record.h -- "an image under its own record", the decisions every kernel family of that kind shares (gswm_codec_keyed.inc,
 // gswm_codec_soft.inc, gswm_keyed.hip, gswm_tamper.hip): the record layout and its operand check, the message repeated over a row, the
 // record's keystream in LDS, and the tail of a per-image vote.  The block function and the counter rule are gswm_chacha.h's.
-// Include after <hip/hip_runtime.h> and include/gswm.h.  A host compiler (gswm_search_plan.h's table program, gswm_robust_plan.h's sweep) sees the layout, the operand check and vote_log2s only.
+// Include after <hip/hip_runtime.h> and include/gswm.h.  A host compiler (gswm_search_plan.h's table program, gswm_tamper_plan.h's sweep) sees the layout, the operand check and vote_log2s only.
 #pragma once
 #include <stdint.h>
 
@@ -28,7 +28,7 @@ static inline int records_check32(const uint8_t* records_dev, int64_t record_str
 }
 
 // Lanes per message bit of a per-image vote (its tail is below): enough to fill the workgroup for short messages, at most 8 (a wave then
-// still owns whole bytes) and at most the copies.  Host arithmetic: gswm_robust_plan.h decides with it.
+// still owns whole bytes) and at most the copies.  Host arithmetic: gswm_tamper_plan.h decides with it.
 static inline int vote_log2s(int64_t msg_bits, int64_t copies, int wg) {
     int log2s = 0;
     while (log2s < 3 && (msg_bits << log2s) < wg && ((int64_t)2 << log2s) <= copies) ++log2s;

@@ -17,7 +17,7 @@ decoded message, weights, weighted vote.  The weighted score is selected on the 
 (`trace`) keeps the unweighted p-values.
 
 With levels (`extract_robust_soft`).  The same alternation with every cipher bit voting at its reliability level (`soft`) times the weight of its tile,
-all rounds in ONE launch (`codec.decode_robust`, csrc/gswm_tamper_soft.inc): a tile's weight is `soft_weights` = max(0, excess - isqrt(wsq)), its
+all rounds in ONE launch (`codec.decode_robust`, csrc/gswm_tamper.hip): a tile's weight is `soft_weights` = max(0, excess - isqrt(wsq)), its
 level-weighted excess agreement over one standard deviation of its null, which is `default_weights` at unit levels.  DESIGN.md section 4.24.
 
 Everything that runs per lattice bit is a HIP kernel (csrc/gswm_tamper.hip); the host sees [th, tw] counts.  DESIGN.md section 4.14.

@@ -96,6 +96,38 @@ def test_single_image_under_a_carrying_counter(G):
     assert np.array_equal(score[0].cpu().numpy(), ws) and np.array_equal(wsum[0].cpu().numpy(), ww) and np.array_equal(bits[0].cpu().numpy(), np.packbits(wb))
 
 
+FULL_ROWS = [((4, 512, 512), 1, 32, 4096),         # 256 tiles of 4096 bits; dword segments, 256 copies (x 65535 fits int32)
+             ((1, 512, 512), 4, 8, 1024)]          # 4096 tiles: the tile loop runs 128 passes; 4-byte segments, 1024 copies
+
+
+@pytest.mark.parametrize("shape,l,tile,M", FULL_ROWS)
+def test_the_row_that_fills_lds(G, shape, l, tile, M):
+    """Nb = 2^20, the edge of both kernels' domain: the row alone is the 131 072 bytes of LDS a launch may take, so neither kernel has a byte beside it"""
+    codec, tamper, T = G
+    rng, nb, packed, recs = _operands(31 + l, 1, shape, l, M)
+    assert nb == 1 << 20 and nb % M == 0
+    th, tw = shape[1] // tile, shape[2] // tile
+    weights = rng.choice(np.array([0, 1, 65535], dtype=np.uint16), size=(1, th, tw))
+    key, nonce, msg = recs[0]
+    q, ks = np.unpackbits(packed[0]), O.keystream_bits(key, nonce, nb)
+    want_agree = R.tile_agree(q, R.message_codeword(np.unpackbits(np.frombuffer(msg, dtype=np.uint8)), ks), shape, l, tile)
+    wb, ws, ww = R.vote(q, ks, weights[0], M, shape, l, tile)
+    assert int(ww.max()) < 2 ** 31
+    p, k, m = _dev(codec, tamper, packed, recs)
+    assert np.array_equal(codec.tile_agreement(p, k, m, M, shape, l, tile)[0].cpu().numpy(), want_agree)
+    bits, score, wsum = codec.vote_tiled(p, k, torch.from_numpy(weights.copy()).cuda(), M, shape, l, tile)
+    assert np.array_equal(score[0].cpu().numpy(), ws) and np.array_equal(wsum[0].cpu().numpy(), ww) and np.array_equal(bits[0].cpu().numpy(), np.packbits(wb))
+
+
+def test_decode_robust_refuses_the_row_that_fills_lds(G):
+    """the two families differ there on purpose: the robust decode keeps weights and message beside the row"""
+    codec, tamper, T = G
+    shape, l, tile, M = FULL_ROWS[0]
+    p, k = torch.zeros((1, 1 << 17), dtype=torch.uint8).cuda(), torch.zeros((1, 48), dtype=torch.uint8).cuda()
+    with pytest.raises(ValueError, match="bytes of LDS"):
+        codec.decode_robust(p, None, k, M, shape, l, tile)
+
+
 @pytest.mark.parametrize("l", [1, 2, 4])
 def test_unit_weights_are_the_plain_vote_and_the_map_sums_to_the_keyed_score(G, l):
     codec, tamper, T = G
