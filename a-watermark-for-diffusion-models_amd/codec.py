@@ -517,6 +517,65 @@ def rows_align(packed: torch.Tensor, shape: Sequence[int], l: int, aligns) -> to
     return _rows_align_launch(packed, shape, l, aligns_dev)
 
 
+COUNTS_ALIGN_MAX_BITS = 524288  # lattice bits of one image in `counts_align`: the row AND its keystream are staged in LDS (csrc/gswm_counts_align_plan.h)
+
+
+def _counts_align_launch(packed: torch.Tensor, shape: Tuple[int, int, int], l: int, aligns_dev: torch.Tensor, key: bytes, nonce: bytes, msg_bits: int) -> torch.Tensor:
+    """`counts_align` after its checks: packed uint8 [B, rowbytes], an `align_table` on packed's device, a checked key and nonce and a message length the lattice tiles"""
+    B = packed.shape[0]
+    A = aligns_dev.shape[0]
+    counts = torch.empty((B, A, int(msg_bits)), dtype=torch.int32, device=packed.device)
+    with torch.cuda.device(packed.device):
+        N.check(N.lib().gsw_counts_align(packed.data_ptr(), B, shape[0], shape[1], shape[2], l, aligns_dev.data_ptr(), A, key, nonce, int(msg_bits),
+                                         counts.data_ptr(), _stream_ptr()))
+    return counts
+
+
+def _counts_align_message(shape: Tuple[int, int, int], l: int, msg_bits) -> int:
+    """msg_bits as `counts_align` takes it for a [C, H, W] lattice at l bits per element, or the refusal: ValueError (the 524 288-bit limit, a length outside
+    8..2048 or not whole bytes), IndexError where `vote_copies` raises it"""
+    if isinstance(msg_bits, bool) or not isinstance(msg_bits, (int, np.integer)) or not 8 <= int(msg_bits) <= 2048 or int(msg_bits) % 8:
+        raise ValueError(f"msg_bits {msg_bits!r} must be a multiple of 8 in 8..2048")
+    n_bits = shape[0] * shape[1] * shape[2] * l
+    if n_bits > COUNTS_ALIGN_MAX_BITS:
+        raise ValueError(f"a lattice of {shape} at l = {l} holds {n_bits} bits, more than the {COUNTS_ALIGN_MAX_BITS} that counts_align stages with their keystream")
+    vote_copies(n_bits // l, int(msg_bits), l)
+    return int(msg_bits)
+
+
+def counts_align(packed: torch.Tensor, shape: Sequence[int], l: int, aligns, key: bytes, nonce: bytes, msg_bits: int) -> torch.Tensor:
+    """The vote counts of every candidate alignment of packed quantised rows under one key, in one launch: int32 [B, A, msg_bits].
+
+    packed, shape, l and aligns as `rows_align` takes them (a device table or a list that is uploaded here).  Row (b, a) of the result is bit
+    for bit the counts of `extract_batch(align.apply(z[b], aligns[a]), key, nonce, msg_bits, return_counts=True, l=l)`: the '1' votes of every
+    message position among the decrypted bits of `rows_align`'s row (b, a) (gsw_counts_align) -- the aligned rows themselves are never
+    written.  Viewed as [B A, msg_bits] the result is the operand of `trace_topk`.  `rows_align`'s refusals with its messages, then ValueError
+    for a lattice of more than 524 288 bits (the row and its keystream are both staged) and a msg_bits outside 8..2048 or not a multiple of 8,
+    IndexError("string index out of range") where `vote_copies` raises it -- all before any launch."""
+    _check_key_nonce(key, nonce)
+    l = check_window(l)
+    shape = _lattice_shape(shape)
+    if not isinstance(packed, torch.Tensor) or not packed.is_cuda:
+        raise ValueError(f"packed must live on a HIP device (got {getattr(packed, 'device', type(packed).__name__)}); counts_align has no CPU path")
+    _need_gpu(packed, "packed")
+    n_bits = shape[0] * shape[1] * shape[2] * l
+    if n_bits % 8:
+        raise ValueError(f"a lattice of {shape} at l = {l} holds {n_bits} bits: not whole bytes")
+    msg_bits = _counts_align_message(shape, l, msg_bits)
+    if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[0] < 1 or packed.shape[1] * 8 != n_bits:
+        raise ValueError(f"packed must be uint8 [B, {n_bits // 8}] with B >= 1 for a lattice of {shape} at l = {l}, got {packed.dtype} {tuple(packed.shape)}")
+    table = align_table(aligns, shape)
+    if isinstance(aligns, torch.Tensor):
+        _need_gpu(aligns, "aligns")
+        _same_device(aligns, packed, "aligns")
+        if aligns.dim() != 2:
+            raise ValueError("aligns must be int32 [A, 3]")
+        aligns_dev = aligns
+    else:
+        aligns_dev = torch.from_numpy(table).to(packed.device)
+    return _counts_align_launch(packed, shape, l, aligns_dev, key, nonce, msg_bits)
+
+
 # ------------------------------------------------------------------------------------------------ issuing (one record per image)
 def _records_operand(records: torch.Tensor, msg_bytes: int) -> Tuple[int, int, int]:
     """The checks `embed_records` and `extract_records` share -> (B, stride, msg_bytes)"""

@@ -47,6 +47,11 @@ ones above over the n l bits.
 Where (`tamper_tile=`, `--tamper_map DIR`): an attributed image can also be asked WHERE it still carries the record's watermark --
 `TraceResult.tamper`, the per-tile agreement with the attributed record's codeword (`tamper.TamperMap`, one `codec.tile_agreement` launch more
 per batch).  The record comes from the registry, not from the image, so each tile's count has the exact binomial null as well.
+
+Through flips, quarter turns and lattice shifts (`trace_latents_aligned`, `trace_latents_keyed_aligned`, `--align flips|d4 [--align_shift R]`): the search runs
+over every (record, alignment) pair of `align.alignments` after one inversion and one quantisation.  Under one key `codec.counts_align` writes the vote counts
+of every alignment in one launch and `codec.trace_topk` ranks them; across keys `codec.rows_align` feeds `codec.trace_keyed_topk`.  For a fixed pair the null
+law is unchanged, the bound is Bonferroni over the U A pairs, and the tamper map is taken on the un-aligned latent.
 """
 from __future__ import annotations
 
@@ -561,7 +566,8 @@ class Candidate:
     index: int
     score: int
     agree: int                  # voted bits equal to the candidate's message (what codec.bit_matches gives for it)
-    log10_p_any: float          # Bonferroni bound over the registry
+    log10_p_any: float          # Bonferroni bound over the registry (over the registry x alignments pairs of an aligned search)
+    alignment: Optional[Tuple[int, int, int]] = None   # aligned searches: this record's best alignment; `align.apply(latent, alignment)` is what matched
 
 
 @dataclass
@@ -569,6 +575,7 @@ class TraceResult:
     candidates: List[Candidate] = field(default_factory=list)
     attributed: Optional[str] = None       # the best candidate's user id if its bound is <= log10(fpr), else None: no registered user
     tamper: Optional["TamperMap"] = None   # tamper.TamperMap against the attributed record (tamper_tile=...): where the image still carries it
+    alignment: Optional[Tuple[int, int, int]] = None   # aligned searches: the attributed record's alignment (None: not attributed, or no alignments searched)
 
 
 def _attach_tamper_maps(out, z, packed, records, M: int, l: int, tile: int, fpr: float) -> None:
@@ -839,6 +846,158 @@ def trace_latents_keyed_soft_l(latents, registry: KeyedRegistry, l: int, *, leve
     return _trace_keyed_soft(latents, registry, l, levels, clip, thresholds, k, fpr, None)
 
 
+# ===================================================================================================================== tracing through flips, turns and shifts
+ALIGNED_STAT_BITS = 21                  # `align._merge_best`'s stat field: a signed score of at most 1 048 576 lattice bits in magnitude
+
+
+def _aligned_lattice(latents, what: str):
+    if latents.dim() != 4:
+        raise ValueError(f"{what} needs latents [B, C, H, W], got {tuple(latents.shape)}")
+    z = latents.contiguous()
+    return z, tuple(int(s) for s in z.shape[1:])
+
+
+def _aligned_results(found, flags, cands, limit: float, candidate):
+    """The host side of the two aligned searches: found = (index, alignment index, score) int32 [B, k] on the device, in one copy; candidate(b, index,
+    score, alignment) -> Candidate.  -> (results, the alignment index of every image's best candidate, 0 where it has none)"""
+    import torch
+    idx_h, aidx_h, score_h = torch.stack(list(found)).cpu().numpy()
+    out = _candidate_lists(idx_h, score_h, flags.cpu().numpy(), limit, lambda b, j, i, s: candidate(b, i, s, cands[int(aidx_h[b, j])]), _trace_result)
+    for r in out:
+        if isinstance(r, TraceResult) and r.attributed is not None:
+            r.alignment = r.candidates[0].alignment
+    best = [max(int(aidx_h[b, 0]), 0) if isinstance(r, TraceResult) else 0 for b, r in enumerate(out)]
+    return out, best
+
+
+def _attach_aligned_tamper_maps(out, z, cands, best, records, M: int, l: int, tile: int, fpr: float) -> None:
+    """`_attach_tamper_maps` under the alignment: every image goes through its best candidate's alignment (`align.unalign`), is quantised again and
+    mapped against its record, so the tiles are those of the lattice AS EMBEDDED"""
+    from . import align as AL
+    if any(r is not None for r in records):
+        zu = AL.unalign(z, cands, best)
+        _attach_tamper_maps(out, zu, codec.quant_pack(zu, l)[0], records, M, l, tile, fpr)
+
+
+def trace_latents_aligned(latents, key: bytes, nonce: bytes, registry: Registry, aligns, *, message_length: Optional[int] = None, k: int = 1,
+                          fpr: float = 1e-6, soft: bool = True, l: int = 1, tamper_tile: Optional[int] = None,
+                          budget_bytes: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents` through flips, quarter turns and lattice shifts: the search runs over every (record, alignment) pair.  latents [B, C, H, W] on the
+    device, aligns from `align.alignments` -> one TraceResult per image (best candidate first), or the reference's ValueError for a NaN / saturated latent.
+
+    One `codec.quant_pack`; then per chunk of images one `codec.counts_align` launch (the vote counts of every alignment of every image, the aligned rows
+    are never written) and one `codec.trace_topk` on the [B A, M] counts; then `align.search_keys`' merge per image: every record keeps its best
+    alignment, the records are ordered by (score descending, record index ascending, alignment index ascending).  The cuts follow `budget_bytes` (default
+    `align.ROWS_BUDGET_BYTES`) with 4 M bytes per aligned image; the result does not depend on them.
+    The score of a pair is `trace_latents`' score of `align.apply(latent, alignment)`, so for a FIXED pair the null law is unchanged -- exactly
+    Bin(M V, 1/2) for the margins -- and the reported bound is Bonferroni over the U A pairs: `log10_p_any(log10_p_soft(score, M V), U A)`, or
+    `log10_p_hard` over U A with soft=False.  (Choosing the alignment first by the blind statistic and tracing afterwards would condition the margins on
+    the selection and lose the exact tail)  `Candidate.alignment` is the record's best alignment, `TraceResult.alignment`
+    the attributed record's: the alignment that UNDOES the attack.  `Candidate.agree`: the voted bits of the latent with that alignment applied, one
+    `codec.extract_batch` launch over the reported (image, candidate) rows.
+    tamper_tile: every attributed image is put through its alignment (`align.unalign`), quantised and mapped against its record as in `trace_latents`.
+    The map is in the coordinates of the lattice AS EMBEDDED, not of the image as received; the border that a shift wrapped around votes as noise."""
+    import torch
+    from . import align as AL
+    limit = _log10_fpr(fpr)
+    l = codec.check_window(l)
+    codec._check_key_nonce(key, nonce)
+    z, shape = _aligned_lattice(latents, "trace_latents_aligned")
+    cands = AL._as_list(aligns, *shape[1:])
+    M = registry.message_bits if message_length is None else int(message_length)
+    B = z.shape[0]
+    rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
+    V = codec.vote_copies(z.numel() // max(B, 1), M, l)
+    M = codec._counts_align_message(shape, l, M)
+    reg_dev = registry.to_device(z.device, M)
+    packed, flags = codec.quant_pack(z, l)
+    table = AL._device_table(cands, shape, z.device)
+
+    def search(rows_b, aligns_dev):
+        counts = codec._counts_align_launch(rows_b, shape, l, aligns_dev, key, nonce, M)
+        return codec.trace_topk(counts.view(-1, M), V, reg_dev, k=int(k), soft=soft)
+
+    found = AL._search_chunks(B, 4 * M, table, reg_dev, k, budget_bytes, lambda b0, b1: packed[b0:b1], search, stat_bits=ALIGNED_STAT_BITS)
+    U, A = len(registry), len(cands)
+    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+
+    def candidate(b, i, s, a):
+        lp = log10_p_soft(s, M * V) if soft else log10_p_hard((s + M) // 2, M, V)          # hard: score = 2 agree - M
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(lp, U * A), a)
+        reported.append((b, c))
+        return c
+
+    out, best = _aligned_results(found, flags, cands, limit, candidate)
+    if reported:                                        # the vote of every reported pair on its aligned latent, one launch
+        bits, _ = codec.extract_batch(torch.stack([AL.apply(z[b], c.alignment) for b, c in reported]).contiguous(), key, nonce, M, l=l)
+        for (_, c), row in zip(reported, bits.cpu().numpy()):
+            c.agree = M - int(np.unpackbits(row ^ rows[c.index]).sum())
+    if tamper_tile is not None:
+        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, lambda i: (key, nonce, bytes(rows[i]))), M, l, tamper_tile, fpr)
+    return out
+
+
+def trace_latents_keyed_aligned(latents, registry: KeyedRegistry, aligns, *, k: int = 1, fpr: float = 1e-6, l: int = 1,
+                                tamper_tile: Optional[int] = None, budget_bytes: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed` through flips, quarter turns and lattice shifts: the composition `align.search_keys` uses, with the registry search in place of
+    the key search.  latents [B, C, H, W] on the device, aligns from `align.alignments` -> one TraceResult per image, or the reference's ValueError.
+
+    One `codec.quant_pack`; then per chunk of images one `codec.rows_align` launch and one `codec.trace_keyed_topk` on its [B A] rows; then the merge of
+    `trace_latents_aligned`.  The score of a (record, alignment) pair is n - 2 popcount(aligned row ^ codeword), for a fixed pair 2 X - n with
+    X ~ Bin(n, 1/2) exactly under the null; the bound is `log10_p_any(log10_p_soft(score, n), U A)`.  `Candidate.agree` is the voted-bit agreement of
+    the latent with the candidate's alignment applied under the candidate's own key (grouped by key, as in `trace_latents_keyed`).
+    tamper_tile: as in `trace_latents_aligned`, each map under its record's own key, in the coordinates of the lattice as embedded."""
+    import torch
+    from . import align as AL
+    limit = _log10_fpr(fpr)
+    l = codec.check_window(l)
+    z, shape = _aligned_lattice(latents, "trace_latents_keyed_aligned")
+    cands = AL._as_list(aligns, *shape[1:])
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    M, mb = registry.message_bits, registry.message_bytes
+    codec.vote_copies(n, M, l)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    nb = n * l
+    if nb > codec.ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {shape} at l = {l} holds {nb} bits, more than {codec.ROW_MAX_BITS}")
+    rec_dev = registry.to_device(z.device)
+    signs, flags = codec.quant_pack(z, l)
+    table = AL._device_table(cands, shape, z.device)
+    rowbytes = signs.shape[1]
+
+    def take(b0, b1):
+        rows_b = signs[b0:b1]
+        return rows_b.clone() if rows_b.data_ptr() % 16 else rows_b
+
+    def search(rows_b, aligns_dev):
+        al = codec._rows_align_launch(rows_b, shape, l, aligns_dev)
+        return codec.trace_keyed_topk(al.view(-1, rowbytes), nb, rec_dev, mb, k=int(k))
+
+    found = AL._search_chunks(B, rowbytes, table, rec_dev, k, budget_bytes, take, search, stat_bits=ALIGNED_STAT_BITS)
+    U, A = len(registry), len(cands)
+    reported: Dict[Tuple[bytes, bytes], List[Tuple[int, Candidate]]] = {}      # (key, nonce) -> (image, candidate)
+
+    def candidate(b, i, s, a):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(log10_p_soft(s, nb), U * A), a)
+        reported.setdefault(registry.record_at(i)[:2], []).append((b, c))
+        return c
+
+    out, best = _aligned_results(found, flags, cands, limit, candidate)
+    for (key, nonce), pairs_ in reported.items():       # one vote per key over its (image, alignment) rows, one comparison per message
+        at = {ba: r for r, ba in enumerate(sorted({(b, c.alignment) for b, c in pairs_}))}
+        bits, _ = codec.extract_batch(torch.stack([AL.apply(z[b], a) for b, a in at]).contiguous(), key, nonce, M, l=l)
+        by_message: Dict[bytes, List[Tuple[int, Candidate]]] = {}
+        for b, c in pairs_:
+            by_message.setdefault(registry.record_at(c.index)[2], []).append((b, c))
+        for msg, group in by_message.items():
+            agree = codec.bit_matches(bits, M, msg).cpu().numpy()
+            for b, c in group:
+                c.agree = int(agree[at[(b, c.alignment)]])
+    if tamper_tile is not None:
+        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, registry.record_at), M, l, tamper_tile, fpr)
+    return out
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result, message_length: int) -> str:
     """One line of trace.txt / stdout"""
@@ -852,6 +1011,9 @@ def format_line(name: str, result, message_length: int) -> str:
         text += f", next: {o.user_id} ({o.agree / message_length}, {o.log10_p_any:.3f})"
     if result.tamper is not None:
         text += f", intact tiles {result.tamper.n_intact}/{result.tamper.n_tiles}"
+    if result.alignment is not None:
+        from . import align as AL
+        text += f", alignment: {AL.describe(result.alignment)}"
     return text
 
 
@@ -861,6 +1023,12 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.align != "none":
+                for name in ("reliability", "keyed_reliability", "window_reliability"):
+                    if getattr(a, name) is not None:
+                        self.error(f"--align cannot be combined with --{name}: the level-weighted trace through alignments is not built")
+            if a.align_shift < 0 or (a.align == "none" and a.align_shift):
+                self.error("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
             if a.keyed_reliability is not None:
                 if not a.per_record_keys:
                     self.error("--keyed_reliability requires --per_record_keys: it ranks a registry whose records carry their own keys "
@@ -940,6 +1108,11 @@ def build_parser():
                    help="for every attributed image write DIR/<image>.tamper.npy (agreeing bits per tile with the attributed record's codeword) and "
                         "DIR/<image>.tamper.png (255 where the watermark's presence in the tile is proven at --fpr over the map), and report the intact tiles")
     p.add_argument("--tile", type=int, default=8, choices=codec.TILES, help="tile edge of --tamper_map, in lattice elements (one element = 8 x 8 pixels)")
+    p.add_argument("--align", default="none", choices=("none", "flips", "d4"),
+                   help="search every (record, alignment) pair over this group of alignments of the lattice: flips (half turn and the two mirrors) or d4 (all "
+                        "eight orientations); the Bonferroni factor grows by the number of candidates (not with --reliability, --keyed_reliability or "
+                        "--window_reliability); with --tamper_map the map is in the coordinates of the lattice as embedded")
+    p.add_argument("--align_shift", type=int, default=0, metavar="R", help="with --align: also every lattice shift in [-R, R]^2 (8 R pixels)")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
     return p
@@ -963,6 +1136,13 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
         if trace_batch is not None:
             return trace_batch(latents)
         tile = args.tile if getattr(args, "tamper_map", None) else None
+        if getattr(args, "align", "none") != "none":
+            from . import align as AL
+            cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
+            if args.per_record_keys:
+                return trace_latents_keyed_aligned(latents, registry, cands, k=args.top, fpr=args.fpr, l=args.l, tamper_tile=tile)
+            return trace_latents_aligned(latents, args.key, args.nonce, registry, cands, message_length=args.message_length, k=args.top, fpr=args.fpr,
+                                         soft=not args.hard, l=args.l, tamper_tile=tile)
         if args.per_record_keys and getattr(args, "window_reliability", None) is not None:
             return trace_latents_keyed_soft_l(latents, registry, args.l, levels=args.window_reliability, k=args.top, fpr=args.fpr)
         if args.per_record_keys and getattr(args, "keyed_reliability", None) is not None:
@@ -1016,6 +1196,10 @@ def _report(job, outcomes, args, registry, synthetic: bool) -> None:
                   ("nonce_hex", "per record" if keyed else args.nonce_hex), ("registry", args.registry),
                   ("users", len(registry)), *keyed, ("message_length", M), ("statistic", _statistic_name(args)), ("fpr", args.fpr),
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
+        if getattr(args, "align", "none") != "none":     # the candidate count: 2 R < the lattice's side (an 8 x 8 pixel element), so it is the group times (2 R + 1)^2
+            from . import align as AL
+            fields += [("align", args.align), ("align_shift", args.align_shift),
+                       ("alignments", len(AL.GROUPS[args.align]) * (2 * int(args.align_shift) + 1) ** 2)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the attributions below are not meaningful\n")

@@ -825,6 +825,25 @@ int gsw_level_rows_align(const uint8_t* signs_dev, const uint8_t* planes_dev, in
                          uint8_t* out_signs_dev, uint8_t* out_planes_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Aligned registry search under one key: the vote counts of every candidate alignment of a packed quantised row,
+ * in one launch; viewed as [B A, msg_bits] they are the operand of gsw_trace_topk.  Additive: gsw_version() stays 500.
+ *
+ *   rows_dev    : uint8 [B, C H W l / 8], gsw_sign_pack's / gsw_quant_pack's row (any alignment), as gsw_rows_align
+ *   aligns_dev  : int32 [A, 3] rows (d, dy, dx), 4-byte aligned, as gsw_rows_align
+ *   key, nonce16: host bytes, as gsw_extract; the keystream is the first n_bits = C H W l bits of ChaCha20 under them
+ *   counts_dev  : int32 [B, A, msg_bits], 4-byte aligned; with M = msg_bits
+ *                 counts[b, a, t] = #{ p < n_bits : p mod M == t and (bit p of gsw_rows_align's row (b, a)) ^ (keystream bit p) == 1 }
+ *                 bit for bit the counts gsw_extract / gsw_extract_l write for that transform of image b's latent, whatever its dtype
+ * The aligned rows are never written.  An entry with d outside 0..7, or an odd d when H != W, writes a row of zero counts (the callers of
+ * this package refuse such a list before it is uploaded).  Every output element is written, no atomics, no workspace, integer arithmetic
+ * only.  The row and its keystream are both staged in LDS once per workgroup (64 KiB each at most); there is no read-in-place form.
+ * GSW_ERR_BAD_ARG: null pointer, aligns_dev or counts_dev not 4-byte aligned, B, C, H, W or A < 1, l outside {1, 2, 4}, msg_bits outside
+ * 8..2048 or not a multiple of 8.  GSW_ERR_RAGGED: n_bits is not a multiple of 8 or of msg_bits.  GSW_ERR_UNSUPPORTED: n_bits > 524 288,
+ * B > 65535.  In that order; every refusal happens before any launch. */
+int gsw_counts_align(const uint8_t* rows_dev, int B, int C, int H, int W, int l, const int32_t* aligns_dev, int A, const uint8_t key[32],
+                     const uint8_t nonce16[16], int msg_bits, int32_t* counts_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Robust decode in one launch, tile weights times reliability levels: the rounds of the tile-weighted vote
  * (gsw_vote_tiled, gsw_tile_agree and the weight rule between them) with every cipher bit voting at its reliability level.
  * Additive: gsw_version() stays 500.
