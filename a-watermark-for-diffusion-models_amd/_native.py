@@ -165,6 +165,8 @@ _PROTOTYPES = {
                                        C.c_void_p]),
     "gsw_counts_align": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p,
                                    C.c_void_p]),
+    "gsw_level_counts_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsw_decode_robust": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }

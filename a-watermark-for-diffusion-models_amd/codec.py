@@ -922,6 +922,75 @@ def level_rows_align(rows: LevelRows, shape: Sequence[int], aligns) -> LevelRows
                      rows.flags.repeat_interleave(A))
 
 
+# ------------------------------------------------------------------------------------------------ aligned registry search ranked by reliability levels
+LEVEL_COUNTS_ALIGN_LDS_CAP = 131072     # bytes of LDS one image's rows, keystream and reduction region may take (csrc/gswm_counts_align_soft_plan.h)
+
+
+def level_counts_align_lds_bytes(n_bits: int, P: int, msg_bits: int) -> int:
+    """The LDS bytes of one `level_counts_align` workgroup, as csrc/gswm_counts_align_soft_plan.h lays them out: 1 + P rows padded to 16 bytes, the keystream in
+    64-byte blocks, and one uint16 per position, lane and kind (score, wsum) of the reduction region"""
+    rowbytes = n_bits // 8
+    words = msg_bits % 32 == 0
+    units = msg_bits // 32 if words else msg_bits // 8
+    lanes = 256 // units * units
+    return (1 + P) * ((rowbytes + 15) // 16 * 16) + 64 * ((rowbytes + 63) // 64) + 2 * lanes * (64 if words else 16)
+
+
+def _level_counts_align_launch(rows: LevelRows, shape: Tuple[int, int, int], aligns_dev: torch.Tensor, key: bytes, nonce: bytes, msg_bits: int, bias: int = 0,
+                               return_wsum: bool = False):
+    """`level_counts_align` after its checks: rows of a [C, H, W] lattice, an `align_table` on their device, a checked key and nonce, a message length the lattice
+    tiles and a bias within `_level_counts_align_limits` -> score int32 [B, A, msg_bits], or (score, wsum)"""
+    B, P, A = rows.signs.shape[0], rows.planes.shape[1], aligns_dev.shape[0]
+    dev = rows.signs.device
+    score = torch.empty((B, A, int(msg_bits)), dtype=torch.int32, device=dev)
+    wsum = torch.empty_like(score) if return_wsum else None
+    with torch.cuda.device(dev):
+        N.check(N.lib().gsw_level_counts_align(rows.signs.data_ptr(), rows.planes.data_ptr(), P, B, shape[0], shape[1], shape[2], aligns_dev.data_ptr(), A, key, nonce,
+                                               int(msg_bits), int(bias), score.data_ptr(), wsum.data_ptr() if return_wsum else None, _stream_ptr()))
+    return (score, wsum) if return_wsum else score
+
+
+def _level_counts_align_limits(shape: Tuple[int, int, int], P: int, msg_bits: int, bias) -> int:
+    """bias as `level_counts_align` takes it for a [C, H, W] lattice with P planes and a checked msg_bits, or ValueError: the staged regions pass the LDS cap, or
+    |bias| + 15 copies leaves int32"""
+    n = shape[0] * shape[1] * shape[2]
+    if isinstance(bias, bool) or not isinstance(bias, (int, np.integer)):
+        raise ValueError(f"bias must be an int, got {bias!r}")
+    lds = level_counts_align_lds_bytes(n, P, msg_bits)
+    if lds > LEVEL_COUNTS_ALIGN_LDS_CAP:
+        raise ValueError(f"a lattice of {shape} with {P} level planes and {msg_bits}-bit messages needs {lds} bytes of LDS in level_counts_align, "
+                         f"more than {LEVEL_COUNTS_ALIGN_LDS_CAP}")
+    if abs(int(bias)) + SOFT_MAX_LEVELS * (n // msg_bits) >= 2 ** 31:
+        raise ValueError(f"bias {bias} plus {SOFT_MAX_LEVELS} x {n // msg_bits} copies does not fit int32")
+    return int(bias)
+
+
+def level_counts_align(rows: LevelRows, shape: Sequence[int], aligns, key: bytes, nonce: bytes, msg_bits: int, *, bias: int = 0, return_wsum: bool = False):
+    """The level-weighted vote of every candidate alignment of `level_pack`'s rows under one key, in one launch (gsw_level_counts_align): int32
+    [B, A, msg_bits], or the pair (score, wsum) with return_wsum.
+
+    rows, shape and aligns as `level_rows_align` takes them.  score[b, a] - bias and wsum[b, a] are bit for bit the `score` and `wsum` of
+    `extract_soft(align.apply(z[b], aligns[a]), ...)` under (key, nonce) with the thresholds the rows were packed with: `counts_align` for level rows.  The
+    aligned rows are never written.  With bias = levels * copies the scores, viewed as [B A, msg_bits], are the counts' of `trace.reliability_counts` and go
+    to `trace_topk` as they are.  RuntimeError for host tensors (there is no CPU fallback); ValueError for `level_rows_align`'s refusals, a msg_bits outside
+    8..2048 or not a multiple of 8, rows, keystream and reduction region beyond 128 KiB of LDS (a 4 x 128 x 128 lattice at 15 levels takes 80 KiB) and a bias
+    that would leave int32; IndexError("string index out of range") where `vote_copies` raises it -- all before any launch."""
+    _check_key_nonce(key, nonce)
+    shape = _level_rows_align_checks(rows, shape)
+    msg_bits = _counts_align_message(shape, 1, msg_bits)
+    bias = _level_counts_align_limits(shape, rows.planes.shape[1], msg_bits, bias)
+    table = align_table(aligns, shape)
+    if isinstance(aligns, torch.Tensor):
+        _need_gpu(aligns, "aligns")
+        _same_device(aligns, rows.signs, "aligns")
+        if aligns.dim() != 2:
+            raise ValueError("aligns must be int32 [A, 3]")
+        aligns_dev = aligns if aligns.is_contiguous() else aligns.contiguous()
+    else:
+        aligns_dev = torch.from_numpy(table).to(rows.signs.device)
+    return _level_counts_align_launch(rows, shape, aligns_dev, key, nonce, msg_bits, bias, bool(return_wsum))
+
+
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)
 TILES =(8, 16, 32)             # supported tile edges, in lattice elements
 

@@ -55,6 +55,7 @@
 #include "gswm_search_plan.h"   // search_decide: every refusal and every launch decision of the three searches; KY_WAVES, KY_WG, KS_WG
 #include "gswm_keysearch_soft_plan.h"   // key_soft_decide: the same for the level-weighted key search
 #include "gswm_counts_align_plan.h"   // counts_align_decide: the same for the vote counts of every alignment under one key
+#include "gswm_counts_align_soft_plan.h"   // level_counts_align_decide: the same for the level-weighted vote of every alignment under one key
 #include "gswm_topk.h"
 
 namespace {
@@ -327,3 +328,4 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 #include "gswm_align.inc"        // gsw_rows_align: every candidate alignment of a packed row, the input of an alignment search
 #include "gswm_align_soft.inc"   // gsw_level_rows_align: the same for a sign row and its level planes, one index walk for all of them
 #include "gswm_counts_align.inc" // gsw_counts_align: the vote counts of every candidate alignment under one key, the operand of an aligned registry search
+#include "gswm_counts_align_soft.inc" // gsw_level_counts_align: the same for gsw_level_pack's rows, the level-weighted vote of every alignment

@@ -998,6 +998,158 @@ def trace_latents_keyed_aligned(latents, registry: KeyedRegistry, aligns, *, k: 
     return out
 
 
+# ===================================================================================================================== the aligned searches ranked by reliability levels
+def _aligned_soft_table(z, levels, clip, thresholds):
+    """(levels, P, make) of an aligned level-weighted search: the number of levels and of planes, known before anything is launched, and make() -> the float32
+    table on z's device (`soft.uniform_thresholds` of the UN-aligned latents, or the given one)"""
+    import torch
+    from . import soft as S
+    if thresholds is None:
+        T, clip = S._check_table(levels, clip)
+        return T, codec.level_planes(T), lambda: S.uniform_thresholds(z, T, clip)
+    if not isinstance(thresholds, torch.Tensor) or thresholds.dim() not in (1, 2):
+        raise ValueError("thresholds must be float32 [levels] or [B, levels]")
+    T = int(thresholds.shape[-1])
+    return T, codec.level_planes(T), lambda: thresholds.to(device=z.device, dtype=torch.float32).contiguous()
+
+
+def _aligned_stack(z, pairs, thr):
+    """The aligned latents of (image, alignment) pairs and the threshold rows that go with them: the operands of one soft vote over the pairs"""
+    import torch
+    from . import align as AL
+    zs = torch.stack([AL.apply(z[b], a) for b, a in pairs]).contiguous()
+    return zs, thr if thr.dim() == 1 else thr[torch.tensor([b for b, _ in pairs], device=z.device)].contiguous()
+
+
+def trace_latents_aligned_soft(latents, key: bytes, nonce: bytes, registry: Registry, aligns, *, levels: int = 15, clip: float = 2.5, thresholds=None,
+                               message_length: Optional[int] = None, k: int = 1, fpr: float = 1e-6, tamper_tile: Optional[int] = None,
+                               budget_bytes: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_aligned` ranked by reliability levels (one cipher bit per element): the search runs over every (record,
+    alignment) pair and every lattice element votes with an integer level 0..levels taken from its magnitude.  latents [B, C, H, W] on the device, aligns
+    from `align.alignments` -> one TraceResult per image (best candidate first), or the reference's ValueError for a NaN / saturated latent.
+
+    thresholds: float32 [levels] or [B, levels]; None: `soft.uniform_thresholds(latents, levels, clip)`, taken ONCE on the un-aligned latents (an alignment
+    permutes the elements, so their levels travel with them).  One `codec.level_pack`; then per chunk of images one `codec.level_counts_align` launch with
+    bias = levels V -- its output is already the counts' of `reliability_counts` -- and one `codec.trace_topk(counts', 2 levels V)`, whose scores are halved
+    as in `trace_latents(reliability=)`; then `trace_latents_aligned`'s merge.  The cuts follow `budget_bytes` with 4 M bytes per aligned image; the result
+    does not depend on them.  The limits are `reliability_counts`', raised before any launch.
+    The score of a pair is sum_t (2 r_t - 1) score[t] of `soft.extract_soft(align.apply(latent, alignment))`.  For a FIXED pair and an image independent of
+    the key the decrypted bits are fair coins given the levels, so Hoeffding's bound `soft.log10_p(score, wsq)` holds with the image's own wsq (a permutation
+    keeps it); the reported bound is Bonferroni over the U A pairs.  A bound, not the exact tail of `trace_latents_aligned`.
+    `Candidate.agree`: the soft vote's bits of the latent with that alignment applied, one `soft.extract_soft` launch over the reported (image, alignment)
+    rows, each with its image's own threshold row.  tamper_tile: as in `trace_latents_aligned`, on the sign row of the un-aligned latent."""
+    import torch
+    from . import align as AL
+    from . import soft as S
+    limit = _log10_fpr(fpr)
+    codec._check_key_nonce(key, nonce)
+    z, shape = _aligned_lattice(latents, "trace_latents_aligned_soft")
+    cands = AL._as_list(aligns, *shape[1:])
+    M = registry.message_bits if message_length is None else int(message_length)
+    B = z.shape[0]
+    rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
+    V = codec.vote_copies(z.numel() // max(B, 1), M, 1)
+    M = codec._counts_align_message(shape, 1, M)
+    T, P, table_of = _aligned_soft_table(z, levels, clip, thresholds)
+    if 2 * T * V > 2000000 or M * 2 * T * V >= 2 ** 31:
+        raise ValueError(f"levels={T} with {V} copies of {M} message bits is beyond the registry search's limits "
+                         "(2 levels copies <= 2 000 000 and msg_bits 2 levels copies < 2^31)")
+    if shape[0] * shape[1] * shape[2] * (1 + P) > codec.ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {shape} with {P} level planes is beyond the search's domain: n (1 + P) <= {codec.ROW_MAX_BITS}")
+    bias = codec._level_counts_align_limits(shape, P, M, T * V)
+    reg_dev = registry.to_device(z.device, M)
+    thr = table_of()
+    lrows = codec.level_pack(z, thr)
+    codec._level_rows_align_checks(lrows, shape)
+    table = AL._device_table(cands, shape, z.device)
+
+    def search(rows_b, aligns_dev):
+        counts = codec._level_counts_align_launch(rows_b, shape, aligns_dev, key, nonce, M, bias)
+        idx, score = codec.trace_topk(counts.view(-1, M), 2 * T * V, reg_dev, k=int(k), soft=True)
+        return idx, torch.where(idx >= 0, score // 2, score)             # the search weighs 2 score[b, a, t]: every score is even
+
+    found = AL._search_chunks(B, 4 * M, table, reg_dev, k, budget_bytes, lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in lrows)), search,
+                              stat_bits=AL.SOFT_STAT_BITS)
+    U, A = len(registry), len(cands)
+    wsq_h = lrows.wsq.cpu().numpy()
+    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+
+    def candidate(b, i, s, a):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U * A), a)
+        reported.append((b, c))
+        return c
+
+    out, best = _aligned_results(found, lrows.flags, cands, limit, candidate)
+    if reported:                                        # the soft vote of every reported pair on its aligned latent, one launch
+        zs, thr_rows = _aligned_stack(z, [(b, c.alignment) for b, c in reported], thr)
+        vote = S.extract_soft(zs, key, nonce, M, thresholds=thr_rows)
+        for (_, c), row in zip(reported, vote.bits.cpu().numpy()):
+            c.agree = M - int(np.unpackbits(row ^ rows[c.index]).sum())
+    if tamper_tile is not None:
+        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, lambda i: (key, nonce, bytes(rows[i]))), M, 1, tamper_tile, fpr)
+    return out
+
+
+def trace_latents_keyed_aligned_soft(latents, registry: KeyedRegistry, aligns, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
+                                     fpr: float = 1e-6, tamper_tile: Optional[int] = None,
+                                     budget_bytes: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed_aligned` ranked by reliability levels (one cipher bit per element): `trace_latents_keyed_soft` over every
+    (record, alignment) pair.  latents [B, C, H, W] on the device, aligns from `align.alignments` -> one TraceResult per image, or the reference's ValueError.
+
+    thresholds as in `trace_latents_aligned_soft`.  One `codec.level_pack`; then per chunk of images one `codec.level_rows_align` launch and one
+    `codec.trace_keyed_soft_topk` on its [B A] rows (wsum repeated: a permutation keeps it); then `trace_latents_aligned`'s merge, with (1 + P) rows counted
+    per aligned image against `budget_bytes`.  No kernel of its own.  The score of a pair is sum_j level_j (1 - 2 (sign_j ^ codeword_j)) of the aligned
+    rows; the bound is `log10_p_any(soft.log10_p(score, wsq), U A)`, Hoeffding's with the image's wsq for a fixed pair, Bonferroni over the pairs.
+    `Candidate.agree` counts the bits of the soft vote of the aligned latent under the candidate's own record: one `codec.extract_soft` launch over the
+    reported (image, candidate) pairs.  tamper_tile: as in `trace_latents_keyed_aligned`.  n (1 + P) may not exceed 1 048 576, P the bit length of `levels`."""
+    import torch
+    from . import align as AL
+    from . import soft as S
+    limit = _log10_fpr(fpr)
+    z, shape = _aligned_lattice(latents, "trace_latents_keyed_aligned_soft")
+    cands = AL._as_list(aligns, *shape[1:])
+    B = z.shape[0]
+    n = z.numel() // max(B, 1)
+    M, mb = registry.message_bits, registry.message_bytes
+    codec.vote_copies(n, M, 1)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    T, P, table_of = _aligned_soft_table(z, levels, clip, thresholds)
+    if n * (1 + P) > codec.ROW_MAX_BITS:
+        raise ValueError(f"a lattice of {shape} with {P} level planes is beyond the search's domain: n (1 + P) <= {codec.ROW_MAX_BITS}")
+    rec_dev = registry.to_device(z.device)
+    thr = table_of()
+    lrows = codec.level_pack(z, thr)
+    codec._level_rows_align_checks(lrows, shape)
+    table = AL._device_table(cands, shape, z.device)
+    rowbytes = lrows.signs.shape[1]
+
+    def search(rows_b, aligns_dev):
+        signs, planes = codec._level_rows_align_launch(rows_b, shape, aligns_dev)
+        al = codec.LevelRows(signs.view(-1, rowbytes), planes.view(-1, P, rowbytes), rows_b.wsum.repeat_interleave(aligns_dev.shape[0]), rows_b.wsq, rows_b.flags)
+        return codec.trace_keyed_soft_topk(al, n, rec_dev, mb, k=int(k))
+
+    found = AL._search_chunks(B, (1 + P) * rowbytes, table, rec_dev, k, budget_bytes, lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in lrows)), search,
+                              stat_bits=AL.SOFT_STAT_BITS)
+    U, A = len(registry), len(cands)
+    wsq_h = lrows.wsq.cpu().numpy()
+    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+
+    def candidate(b, i, s, a):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U * A), a)
+        reported.append((b, c))
+        return c
+
+    out, best = _aligned_results(found, lrows.flags, cands, limit, candidate)
+    if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
+        zs, thr_rows = _aligned_stack(z, [(b, c.alignment) for b, c in reported], thr)
+        rec = torch.tensor([c.index for _, c in reported], device=z.device)
+        vote = codec.extract_soft(zs, rec_dev[rec].contiguous(), mb, thr_rows)
+        for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
+            c.agree = int(a)
+    if tamper_tile is not None:
+        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, registry.record_at), M, 1, tamper_tile, fpr)
+    return out
+
+
 # ===================================================================================================================== front end
 def format_line(name: str, result, message_length: int) -> str:
     """One line of trace.txt / stdout"""
@@ -1023,10 +1175,22 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.align_reliability is not None:
+                if a.align == "none":
+                    self.error("--align_reliability requires --align flips or --align d4: it ranks the (record, alignment) pairs of an aligned search "
+                               "(without alignments: --reliability, or --keyed_reliability with --per_record_keys)")
+                if a.hard:
+                    self.error("--align_reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
+                if a.l != 1:
+                    self.error(f"--align_reliability cannot be combined with --l {a.l}: reliability levels under alignments are defined for one cipher bit "
+                               "per element (--l 1)")
+                for name in ("reliability", "keyed_reliability", "window_reliability"):
+                    if getattr(a, name) is not None:
+                        self.error(f"--align_reliability cannot be combined with --{name}: --{name} is the same statistic without alignments")
             if a.align != "none":
                 for name in ("reliability", "keyed_reliability", "window_reliability"):
                     if getattr(a, name) is not None:
-                        self.error(f"--align cannot be combined with --{name}: the level-weighted trace through alignments is not built")
+                        self.error(f"--align cannot be combined with --{name}: the level-weighted trace through alignments is --align_reliability (--l 1)")
             if a.align_shift < 0 or (a.align == "none" and a.align_shift):
                 self.error("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
             if a.keyed_reliability is not None:
@@ -1113,6 +1277,10 @@ def build_parser():
                         "eight orientations); the Bonferroni factor grows by the number of candidates (not with --reliability, --keyed_reliability or "
                         "--window_reliability); with --tamper_map the map is in the coordinates of the lattice as embedded")
     p.add_argument("--align_shift", type=int, default=0, metavar="R", help="with --align: also every lattice shift in [-R, R]^2 (8 R pixels)")
+    p.add_argument("--align_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
+                   help="with --align flips or d4: rank the (record, alignment) pairs by level-weighted margins, LEVELS (1..15) reliability levels per lattice "
+                        "element, the p-value is a Hoeffding bound over the pairs (with or without --per_record_keys; --l 1, not with --hard, --reliability, "
+                        "--keyed_reliability or --window_reliability)")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
     return p
@@ -1139,6 +1307,12 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
+            levels = getattr(args, "align_reliability", None)
+            if levels is not None and args.per_record_keys:
+                return trace_latents_keyed_aligned_soft(latents, registry, cands, levels=levels, k=args.top, fpr=args.fpr, tamper_tile=tile)
+            if levels is not None:
+                return trace_latents_aligned_soft(latents, args.key, args.nonce, registry, cands, levels=levels, message_length=args.message_length,
+                                                  k=args.top, fpr=args.fpr, tamper_tile=tile)
             if args.per_record_keys:
                 return trace_latents_keyed_aligned(latents, registry, cands, k=args.top, fpr=args.fpr, l=args.l, tamper_tile=tile)
             return trace_latents_aligned(latents, args.key, args.nonce, registry, cands, message_length=args.message_length, k=args.top, fpr=args.fpr,
@@ -1177,9 +1351,17 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
     return out
 
 
+def _alignment_count(args) -> int:
+    """the candidates of --align / --align_shift: 2 R < the lattice's side (an 8 x 8 pixel element), so it is the group times (2 R + 1)^2"""
+    from . import align as AL
+    return len(AL.GROUPS[args.align]) * (2 * int(args.align_shift) + 1) ** 2
+
+
 def _statistic_name(args) -> str:
     """the `statistic` field of trace.txt's header"""
     levels = args.reliability if args.reliability is not None else getattr(args, "keyed_reliability", None)
+    if levels is None and getattr(args, "align_reliability", None) is not None:
+        return f"soft, {args.align_reliability} reliability levels over {_alignment_count(args)} alignments"
     if levels is None and getattr(args, "window_reliability", None) is not None:
         return f"soft, {args.window_reliability} reliability levels per window bit"
     return "hard" if args.hard else "soft" if levels is None else f"soft, {levels} reliability levels"
@@ -1196,10 +1378,8 @@ def _report(job, outcomes, args, registry, synthetic: bool) -> None:
                   ("nonce_hex", "per record" if keyed else args.nonce_hex), ("registry", args.registry),
                   ("users", len(registry)), *keyed, ("message_length", M), ("statistic", _statistic_name(args)), ("fpr", args.fpr),
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
-        if getattr(args, "align", "none") != "none":     # the candidate count: 2 R < the lattice's side (an 8 x 8 pixel element), so it is the group times (2 R + 1)^2
-            from . import align as AL
-            fields += [("align", args.align), ("align_shift", args.align_shift),
-                       ("alignments", len(AL.GROUPS[args.align]) * (2 * int(args.align_shift) + 1) ** 2)]
+        if getattr(args, "align", "none") != "none":
+            fields += [("align", args.align), ("align_shift", args.align_shift), ("alignments", _alignment_count(args))]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the attributions below are not meaningful\n")

@@ -844,6 +844,30 @@ int gsw_counts_align(const uint8_t* rows_dev, int B, int C, int H, int W, int l,
                      const uint8_t nonce16[16], int msg_bits, int32_t* counts_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Aligned registry search ranked by reliability levels: gsw_counts_align for gsw_level_pack's rows.  The
+ * level-weighted vote of every candidate alignment under one key, in one launch; viewed as [B A, msg_bits] the scores are the operand of
+ * gsw_trace_topk.  One cipher bit per element (l = 1).  Additive: gsw_version() stays 500.
+ *
+ *   signs_dev, planes_dev : gsw_level_pack's sign row uint8 [B, n / 8] and plane rows uint8 [B, P, n / 8], n = C H W (any alignment); P in 1 .. 4
+ *   aligns_dev  : int32 [A, 3] rows (d, dy, dx), 4-byte aligned, as gsw_rows_align
+ *   key, nonce16: host bytes, as gsw_extract; the keystream is the first n bits of ChaCha20 under them
+ *   bias        : added to every score (a caller that feeds gsw_trace_topk passes levels * n / msg_bits: the scores are then its counts)
+ *   score_dev   : int32 [B, A, msg_bits], 4-byte aligned;  wsum_dev : the same shape, or null (then it is not written).  With M = msg_bits,
+ *                 d_p = (bit p of gsw_rows_align's row (b, a) of the sign row) ^ (keystream bit p), level_p = sum_k 2^k (bit p of the aligned plane k):
+ *                 score[b, a, t] = bias + sum over p = t (mod M) of level_p (2 d_p - 1),  wsum[b, a, t] = sum over p = t (mod M) of level_p
+ *                 bit for bit gsw_extract_soft's score (plus bias) and wsum of that transform of image b's latent under the table the rows were packed with
+ * The aligned rows are never written.  An entry with d outside 0..7, or an odd d when H != W, writes `bias` to its scores and zeros to its wsum
+ * (the callers of this package refuse such a list before it is uploaded).  Every element of a present output is written, no atomics, no
+ * workspace, integer arithmetic only.  The 1 + P rows (each padded to 16 bytes), the keystream and a reduction region (64 KiB at most) are staged
+ * in LDS; there is no read-in-place form.
+ * GSW_ERR_BAD_ARG: null pointer (wsum_dev apart), aligns_dev, score_dev or wsum_dev not 4-byte aligned, B, C, H, W or A < 1, P outside 1..4,
+ * msg_bits outside 8..2048 or not a multiple of 8.  GSW_ERR_RAGGED: n is not a multiple of 8 or of msg_bits.  GSW_ERR_UNSUPPORTED:
+ * n (1 + P) > 1 048 576, B > 65535, the staged regions beyond 128 KiB (a 4 x 128 x 128 lattice at P = 4 takes 80 KiB, 4 x 256 x 256 at P = 1 the
+ * whole of it), |bias| + 15 n / msg_bits beyond int32.  In that order; every refusal happens before any launch. */
+int gsw_level_counts_align(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int B, int C, int H, int W, const int32_t* aligns_dev, int A,
+                           const uint8_t key[32], const uint8_t nonce16[16], int msg_bits, int bias, int32_t* score_dev, int32_t* wsum_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Robust decode in one launch, tile weights times reliability levels: the rounds of the tile-weighted vote
  * (gsw_vote_tiled, gsw_tile_agree and the weight rule between them) with every cipher bit voting at its reliability level.
  * Additive: gsw_version() stays 500.
