@@ -832,6 +832,106 @@ def trace_keyed_soft_topk(rows: LevelRows, n_bits: int, records: torch.Tensor, m
     return idx, score
 
 
+# ------------------------------------------------------------------------------------------------ pooled evidence across the images of a set
+POOL_MAX_PLANES = 10            # Q: planes of a pooled row, at most (csrc/gswm_pool_plan.h)
+
+
+class PooledRows(NamedTuple):
+    """What `pool_rows` returns, all on the rows' device: the operands of `trace_keyed_pooled_topk`"""
+    signs: torch.Tensor     # uint8 [G, n/8], bit j = (S_j < 0)
+    planes: torch.Tensor    # uint8 [G, Q, n/8], plane k = bit k of |S_j|, packed MSB first
+    wsum: torch.Tensor      # int32 [G], sum_j |S_j|
+    wsq: torch.Tensor       # int64 [G], sum_j S_j^2
+
+
+def pool_planes(P: int, max_set: int) -> int:
+    """Q: the bit length of Lmax * max_set, Lmax = 2**P - 1 (1 without planes) -- the planes that hold every pooled level of sets of at most
+    `max_set` images; ValueError beyond `POOL_MAX_PLANES`."""
+    lmax = (1 << P) - 1 if P else 1
+    Q = (lmax * int(max_set)).bit_length()
+    if Q > POOL_MAX_PLANES:
+        raise ValueError(f"a set of {max_set} images at levels up to {lmax} needs {Q} planes: pool_rows holds at most {POOL_MAX_PLANES} "
+                         f"(sets of at most {((1 << POOL_MAX_PLANES) - 1) // lmax} images at these levels)")
+    return Q
+
+
+def _pool_domain(n_bits: int, Q: int, what: str):
+    if n_bits * (1 + Q) > ROW_MAX_BITS:
+        raise ValueError(f"{what}: a lattice of {n_bits} bits with {Q} pooled planes is beyond the searches' domain: n_bits (1 + Q) <= {ROW_MAX_BITS}")
+    if n_bits * ((1 << Q) - 1) >= 2 ** 31:
+        raise ValueError(f"{what}: a lattice of {n_bits} bits with {Q} pooled planes is beyond int32 scores: n_bits (2**Q - 1) < 2**31")
+
+
+def pool_rows(signs: torch.Tensor, planes: Optional[torch.Tensor], set_sizes: Sequence[int]) -> PooledRows:
+    """Pool the packed rows of the images of every set into ONE row per set, in one launch (gsw_pool_rows): with lev_bj the level of element j of
+    image b (1 without planes) and h_bj its sign bit, S_j = sum over the set of lev_bj (1 - 2 h_bj); the pooled sign bit is S_j < 0, the pooled
+    level |S_j| (S_j = 0: sign 0, level 0).  A record's `trace_keyed_topk` / `trace_keyed_soft_topk` scores summed over a set are its
+    `trace_keyed_pooled_topk` score on the pooled row: every score is linear in the image.
+
+    signs: uint8 [B, n/8] (`sign_pack`, `quant_pack`, `level_pack`); planes: uint8 [B, P, n/8] with P in 1..4 (`level_pack`), or None for unit levels;
+    set_sizes: the sizes of the G sets, whose images are contiguous in that order (sum = B, every size >= 1; the caller gathers).
+    Q = `pool_planes(P, max(set_sizes))` planes come back: at most 1023 images per set at unit levels, 68 at 15 levels (ValueError beyond, before
+    any launch); n (1 + Q) may not exceed 1 048 576 and n (2**Q - 1) must stay below 2**31."""
+    _need_gpu(signs, "signs")
+    if signs.dtype != torch.uint8 or signs.dim() != 2 or signs.shape[0] < 1 or signs.shape[1] < 1:
+        raise ValueError("signs must be uint8 [B, n_bits / 8] with at least one image")
+    B, nbytes = signs.shape
+    P = 0
+    if planes is not None:
+        _need_gpu(planes, "planes")
+        _same_device(planes, signs, "planes")
+        if planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != B or planes.shape[2] != nbytes or not 1 <= planes.shape[1] <= 4:
+            raise ValueError(f"planes must be uint8 [{B}, P, {nbytes}] with P in 1..4")
+        P = planes.shape[1]
+    sizes = [int(s) for s in set_sizes]
+    if not sizes or min(sizes) < 1 or sum(sizes) != B:
+        raise ValueError(f"set_sizes must be at least one set of at least one image each, {B} images in all (got {sizes[:8]}{'...' if len(sizes) > 8 else ''})")
+    G, biggest = len(sizes), max(sizes)
+    Q = pool_planes(P, biggest)
+    _pool_domain(nbytes * 8, Q, "pool_rows")
+    signs = signs.contiguous()
+    planes = planes.contiguous() if planes is not None else None
+    dev = signs.device
+    set_ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dev)
+    out = PooledRows(torch.empty((G, nbytes), dtype=torch.uint8, device=dev), torch.empty((G, Q, nbytes), dtype=torch.uint8, device=dev),
+                     torch.empty((G,), dtype=torch.int32, device=dev), torch.empty((G,), dtype=torch.int64, device=dev))
+    with torch.cuda.device(dev):
+        N.check(N.lib().gsw_pool_rows(signs.data_ptr(), planes.data_ptr() if planes is not None else None, P, B, nbytes * 8, set_ptr.data_ptr(), G, biggest, Q,
+                                      out.signs.data_ptr(), out.planes.data_ptr(), out.wsum.data_ptr(), out.wsq.data_ptr(), _stream_ptr()))
+    return out
+
+
+def trace_keyed_pooled_topk(rows: PooledRows, n_bits: int, records: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`trace_keyed_soft_topk` for pooled rows: (idx int32 [G, k], score int32 [G, k]) per set, best first, ties towards the lower row; past the
+    registry's end idx = -1 and score = INT32_MIN.
+
+    rows: `pool_rows`' result (signs [G, n_bits / 8], planes [G, Q, n_bits / 8] with Q in 1..10, wsum [G]), records: as `trace_keyed_topk`.
+    score = wsum - 2 sum_k 2**k popcount(plane_k & (signs ^ codeword)): the sum over the set's images of the record's per-image score.  One search
+    launch (gsw_trace_keyed_pooled_topk); n_bits (1 + Q) may not exceed 1 048 576 (ValueError).  Raises IndexError when n_bits is not a multiple
+    of 8 msg_bytes."""
+    signs, planes, wsum = rows.signs, rows.planes, rows.wsum
+
+    def planes_check(G):
+        if planes.dtype != torch.uint8 or planes.dim() != 3 or planes.shape[0] != G or planes.shape[2] != signs.shape[1] or not 1 <= planes.shape[1] <= POOL_MAX_PLANES:
+            raise ValueError(f"rows.planes must be uint8 [{G}, Q, {signs.shape[1]}] with Q in 1..{POOL_MAX_PLANES}")
+
+    def wsum_check(G):
+        if wsum.dtype != torch.int32 or tuple(wsum.shape) != (G,):
+            raise ValueError(f"rows.wsum must be int32 [{G}]")
+
+    G, U, stride, n_bits, msg_bytes, k = _search_operands(signs, n_bits, records, msg_bytes, k, prefix="rows.",
+                                                          extras=((planes, "rows.planes", planes_check), (wsum, "rows.wsum", wsum_check)))
+    Q = planes.shape[1]
+    _pool_domain(n_bits, Q, "trace_keyed_pooled_topk")
+    lib = N.lib()
+    signs, planes = signs.contiguous(), planes.contiguous()
+    ws, idx, score = _search_outputs(lib.gsw_trace_keyed_workspace_bytes, G, U, k, "records", signs.device)
+    with torch.cuda.device(signs.device):
+        N.check(lib.gsw_trace_keyed_pooled_topk(signs.data_ptr(), planes.data_ptr(), wsum.data_ptr(), Q, G, n_bits, records.data_ptr(),
+                                                stride, msg_bytes, U, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), _stream_ptr()))
+    return idx, score
+
+
 # ------------------------------------------------------------------------------------------------ blind key search ranked by reliability levels
 def key_search_soft_topk(rows: LevelRows, n_bits: int, keys: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """`key_search_topk` ranked by reliability levels: (idx int32 [B, k], stat int32 [B, k]), best first, ties towards the lower row; past

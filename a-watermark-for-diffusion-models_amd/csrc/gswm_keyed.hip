@@ -44,6 +44,7 @@
 //   (gswm_keyed_soft.inc, included at the end: gsw_trace_keyed_soft_scan_kernel<T, MSG4, P>, the level-weighted search)
 //   (gswm_keysearch.inc, included after it: gsw_key_search_scan_kernel<PL, SG>, the blind key search)
 //   (gswm_keysearch_soft.inc, after that: gsw_key_search_soft_scan_kernel<CP, P, SG>, the blind key search ranked by reliability levels)
+//   (gswm_pool.inc, last: gsw_pool_rows_kernel<P> and gsw_trace_keyed_pooled_scan_kernel<T, MSG4>, the images of a set pooled and searched as one row)
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -56,6 +57,7 @@
 #include "gswm_keysearch_soft_plan.h"   // key_soft_decide: the same for the level-weighted key search
 #include "gswm_counts_align_plan.h"   // counts_align_decide: the same for the vote counts of every alignment under one key
 #include "gswm_counts_align_soft_plan.h"   // level_counts_align_decide: the same for the level-weighted vote of every alignment under one key
+#include "gswm_pool_plan.h"   // pool_decide: the same for pooling the images of a set and for the record walk over pooled rows
 #include "gswm_topk.h"
 
 namespace {
@@ -329,3 +331,4 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 #include "gswm_align_soft.inc"   // gsw_level_rows_align: the same for a sign row and its level planes, one index walk for all of them
 #include "gswm_counts_align.inc" // gsw_counts_align: the vote counts of every candidate alignment under one key, the operand of an aligned registry search
 #include "gswm_counts_align_soft.inc" // gsw_level_counts_align: the same for gsw_level_pack's rows, the level-weighted vote of every alignment
+#include "gswm_pool.inc"         // gsw_pool_rows, gsw_trace_keyed_pooled_topk: the images of a set pooled into one row, and the record walk for its up to 10 planes

@@ -1150,7 +1150,194 @@ def trace_latents_keyed_aligned_soft(latents, registry: KeyedRegistry, aligns, *
     return out
 
 
+# ===================================================================================================================== tracing a SET of images to one user
+@dataclass
+class SetTraceResult:
+    candidates: List[Candidate] = field(default_factory=list)   # best first; `score` is the pooled score, the sum of the record's scores over the set's images
+    attributed: Optional[str] = None       # the best candidate's user id if its bound is <= log10(fpr), else None
+    size: int = 0                          # images pooled
+    skipped: int = 0                       # images of the set left out: NaN / saturated latents
+    wsq: int = 0                           # sum_j S_j^2 of the pooled row: what Hoeffding's bound divides by
+
+
+def _pool_levels(levels, l: int) -> Tuple[int, int]:
+    """(levels, l) of a pooled trace, or ValueError: levels = 0 pools `quant_pack` rows at l = 1, 2, 4; levels in 1..15 pools `level_pack` rows, l = 1 only"""
+    l = codec.check_window(l)
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= int(levels) <= codec.SOFT_MAX_LEVELS:
+        raise ValueError(f"levels must be 0 (unit levels) or an int in 1..{codec.SOFT_MAX_LEVELS}, got {levels!r}")
+    if int(levels) and l != 1:
+        raise ValueError(f"levels = {levels} cannot be combined with l = {l}: pooled reliability levels are defined for one cipher bit per element (l = 1)")
+    return int(levels), l
+
+
+def _pool_pack(z, levels: int, clip: float, l: int):
+    """The rows a pooled trace adds up, packed once per image -> (signs [B, n l / 8], planes [B, P, n l / 8] or None, flags on the host)"""
+    if levels == 0:
+        signs, flags = codec.quant_pack(z, l)
+        return signs, None, flags.cpu().numpy()
+    from . import soft as S
+    rows = codec.level_pack(z, S.uniform_thresholds(z, levels, clip))      # thresholds per image: a level means the same share of every image's range
+    return rows.signs, rows.planes, rows.flags.cpu().numpy()
+
+
+def _unpack_bits(rows):
+    """uint8 [..., n / 8] on the device -> int64 [..., n], MSB first"""
+    import torch
+    shifts = torch.arange(7, -1, -1, device=rows.device, dtype=torch.int64)
+    return ((rows.to(torch.int64)[..., None] >> shifts) & 1).reshape(*rows.shape[:-1], rows.shape[-1] * 8)
+
+
+def _pooled_agree(pooled, row: int, record: Tuple[bytes, bytes, bytes]) -> int:
+    """Message bits of the pooled level-weighted vote under the record's own key that equal its message: torch ops over one pooled row"""
+    import torch
+    key, nonce, msg = record
+    signs = pooled.signs[row]
+    S = _unpack_bits(pooled.planes[row])                                    # [Q, n]
+    level = (S << torch.arange(S.shape[0], device=S.device, dtype=torch.int64)[:, None]).sum(dim=0)
+    d = _unpack_bits(signs) ^ _unpack_bits(codec.keystream(key, nonce, signs.shape[0], device=signs.device))
+    vote = (level * (2 * d - 1)).reshape(-1, 8 * len(msg)).sum(dim=0)      # position j votes for message bit j mod M
+    want = _unpack_bits(torch.frombuffer(bytearray(msg), dtype=torch.uint8).to(signs.device))
+    return int(((vote > 0).to(torch.int64) == want).sum())
+
+
+def _trace_pooled(signs, planes, flags_h, sets, registry: KeyedRegistry, k: int, fpr: float) -> list:
+    """Packed rows of B images, the sets as lists of image indices -> one SetTraceResult per set (or the ValueError of a set left empty): gather the
+    unflagged images set by set, one `codec.pool_rows` launch, one `codec.trace_keyed_pooled_topk` launch, the candidates"""
+    import torch
+    from . import soft as S
+    limit = _log10_fpr(fpr)
+    B, n_bits, U = signs.shape[0], signs.shape[1] * 8, len(registry)
+    out: list = [None] * len(sets)
+    live = []                                            # (set, its unflagged images, how many were left out)
+    for g, members in enumerate(sets):
+        members = [int(b) for b in members]
+        if not members:
+            raise ValueError(f"set {g} is empty: a set holds at least one image")
+        if min(members) < 0 or max(members) >= B:
+            raise IndexError(f"set {g} names image {min(members) if min(members) < 0 else max(members)}, the batch holds {B}")
+        kept = [b for b in members if _flag_error(int(flags_h[b])) is None]
+        if kept:
+            live.append((g, kept, len(members) - len(kept)))
+        else:
+            out[g] = _flag_error(int(flags_h[members[0]]))
+    if not live:
+        return out
+    order = torch.tensor([b for _, kept, _ in live for b in kept], device=signs.device)
+    pooled = codec.pool_rows(signs[order], planes[order] if planes is not None else None, [len(kept) for _, kept, _ in live])
+    idx, score = codec.trace_keyed_pooled_topk(pooled, n_bits, registry.to_device(signs.device), registry.message_bytes, k=k)
+    idx_h, score_h = _pairs_to_host(idx, score)
+    wsq_h = pooled.wsq.cpu().numpy()
+    for row, (g, kept, skipped) in enumerate(live):
+        wsq, found = int(wsq_h[row]), []
+        for j in range(idx_h.shape[1]):
+            i = int(idx_h[row, j])
+            if i < 0:
+                break
+            s = int(score_h[row, j])
+            found.append(Candidate(registry.user_at(i), i, s, _pooled_agree(pooled, row, registry.record_at(i)), log10_p_any(S.log10_p(s, wsq), U)))
+        out[g] = SetTraceResult(found, found[0].user_id if found and found[0].log10_p_any <= limit else None, len(kept), skipped, wsq)
+    return out
+
+
+def trace_sets_keyed(latents, sets, keyed_registry: KeyedRegistry, *, levels: int = 0, clip: float = 2.5, k: int = 1, fpr: float = 1e-6,
+                     l: int = 1) -> List[Union[SetTraceResult, ValueError]]:
+    """Trace SETS of images to one user each, pooling the evidence of a set's images: latents [B, ...] on the device, sets a
+    list of lists of image indices (an image may appear in several sets) -> one SetTraceResult per set.
+
+    Every keyed score is linear in the image, so the sum of a record's scores over a set is its score against one pooled row: `codec.pool_rows` adds
+    the set's packed rows into S_j = sum_b lev_bj (1 - 2 h_bj), `codec.trace_keyed_pooled_topk` walks the records ONCE per set whatever its size.
+    levels = 0 pools `codec.quant_pack` rows (unit levels; l = 1, 2 or 4), levels in 1..15 pools `codec.level_pack` rows under
+    `soft.uniform_thresholds(latents, levels, clip)` taken per image (l = 1 only).
+    The p-value is Hoeffding's bound `soft.log10_p(score, wsq)` with wsq = sum_j S_j^2, Bonferroni over the records.  It conditions on the images: a
+    record whose key they are independent of has a uniform codeword, so the pooled score is sum_j +-|S_j| with fair signs -- whatever the dependence
+    BETWEEN the images (eight copies of one image carry that image's own bound, not eight times its evidence; Bin(n |set|, 1/2) would be wrong).
+    The sets are the caller's choice, made before looking at scores: trying several groupings costs Bonferroni over them.
+    Images flagged NaN or saturated are left out of their set and counted in `skipped`; a set left empty gets the reference's ValueError for such an
+    image.  `Candidate.agree` counts the message bits of the pooled level-weighted vote under the candidate's own key (torch ops over the reported
+    rows).  A set holds at most 1023 images at unit levels and 1023 // (2**P - 1) at `levels` of P bits (68 at 15): ValueError beyond."""
+    levels, l = _pool_levels(levels, l)
+    _log10_fpr(fpr)
+    z = latents.contiguous()
+    B = z.shape[0]
+    codec.vote_copies(z.numel() // max(B, 1), keyed_registry.message_bits, l)   # (a lattice the messages do not tile fails here, as extract_batch would)
+    signs, planes, flags_h = _pool_pack(z, levels, clip, l)
+    return _trace_pooled(signs, planes, flags_h, sets, keyed_registry, k, fpr)
+
+
+def keyed_from_shared(registry: Registry, key: bytes, nonce: bytes, message_length: Optional[int] = None) -> KeyedRegistry:
+    """The shared-key registry as keyed records: `key | nonce` in front of every message, same order, same user ids"""
+    M = registry.message_bits if message_length is None else int(message_length)
+    rows = registry.packed(M)
+    keyed = KeyedRegistry(M // 8)
+    for i in range(len(registry)):
+        keyed.add(registry.user_at(i), key, nonce, bytes(rows[i]))
+    return keyed
+
+
+def trace_sets(latents, sets, key: bytes, nonce: bytes, registry: Registry, *, message_length: Optional[int] = None, levels: int = 0, clip: float = 2.5,
+               k: int = 1, fpr: float = 1e-6, l: int = 1) -> List[Union[SetTraceResult, ValueError]]:
+    """`trace_sets_keyed` for a registry whose users share one key: `key | nonce` is written in front of every message (`keyed_from_shared`) and the keyed
+    form runs.  For records that share a key the scores are the same numbers as a vote-based search would give, and with a few sets the record walk
+    is milliseconds against 2^20 records: there is no kernel path of its own."""
+    return trace_sets_keyed(latents, sets, keyed_from_shared(registry, key, nonce, message_length), levels=levels, clip=clip, k=k, fpr=fpr, l=l)
+
+
 # ===================================================================================================================== front end
+def format_set_line(name: str, result) -> str:
+    """One line per set of trace.txt / stdout, after the per-image lines: name, images, skipped, user or none, bound, score"""
+    if isinstance(result, Exception):
+        return f"set {name}, Error: {result}"
+    head = f"set {name}, images, {result.size}, skipped, {result.skipped}, user: {result.attributed if result.attributed is not None else 'none'}"
+    if not result.candidates:
+        return head + ", log10 p, 0.0, score, nan"
+    c = result.candidates[0]
+    text = head + f", log10 p, {c.log10_p_any:.3f}, score, {c.score}"
+    for o in result.candidates[1:]:
+        text += f", next: {o.user_id} ({o.log10_p_any:.3f}, {o.score})"
+    return text
+
+
+class _PoolStore:
+    """The packed rows of every traced image of a run, kept across device batches for --pool: file -> (sign row, plane rows or None, flags)"""
+
+    def __init__(self, args, registry):
+        self.levels = int(args.pool_reliability or 0)
+        self.l, self.k, self.fpr = int(args.l), int(args.top), float(args.fpr)
+        self.rows: Dict[str, tuple] = {}
+        self.registry = registry if args.per_record_keys else keyed_from_shared(registry, args.key, args.nonce, args.message_length)
+
+    def add(self, files: Sequence[str], latents) -> None:
+        signs, planes, flags_h = _pool_pack(latents.contiguous(), self.levels, 2.5, self.l)
+        for r, f in enumerate(files):
+            self.rows[f] = (signs[r], planes[r] if planes is not None else None, int(flags_h[r]))
+
+    def drop(self, f: str) -> None:
+        self.rows.pop(f, None)
+
+    def trace(self, named_sets: Sequence[Tuple[str, Sequence[str]]]) -> List[Tuple[str, object]]:
+        """(name, files) per set -> (name, SetTraceResult or the exception) per set that has any traced image"""
+        import torch
+        files = [f for f in dict.fromkeys(f for _, fs in named_sets for f in fs) if f in self.rows]
+        at = {f: i for i, f in enumerate(files)}
+        named = [(name, [at[f] for f in fs if f in at]) for name, fs in named_sets]
+        named = [(name, members) for name, members in named if members]
+        if not named:
+            return []
+        signs = torch.stack([self.rows[f][0] for f in files])
+        planes = torch.stack([self.rows[f][1] for f in files]) if self.levels else None
+        flags_h = np.array([self.rows[f][2] for f in files])
+        try:
+            results = _trace_pooled(signs, planes, flags_h, [m for _, m in named], self.registry, self.k, self.fpr)
+        except Exception:                                # (a set beyond the pooling limits): redone set by set so that each reports its own error
+            results = []
+            for _, members in named:
+                try:
+                    results += _trace_pooled(signs, planes, flags_h, [members], self.registry, self.k, self.fpr)
+                except Exception as e:
+                    results.append(e)
+        return [(name, r) for (name, _), r in zip(named, results)]
+
+
 def format_line(name: str, result, message_length: int) -> str:
     """One line of trace.txt / stdout"""
     if isinstance(result, Exception):
@@ -1175,6 +1362,21 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.pool_reliability is not None:
+                if a.pool is None:
+                    self.error("--pool_reliability requires --pool all or --pool subdirs: it sets the reliability levels of the rows a pooled trace adds up")
+                if a.l != 1:
+                    self.error(f"--pool_reliability cannot be combined with --l {a.l}: pooled reliability levels are defined for one cipher bit per "
+                               "element (--l 1); --pool alone pools the --l rows at unit levels")
+            if a.pool is not None:
+                if a.hard:
+                    self.error("--pool cannot be combined with --hard: pooled evidence is a sum of margins, the majority-voted bits do not add up")
+                if a.align != "none":
+                    self.error("--pool cannot be combined with --align: alignment searches inside a set are out of scope")
+                if a.tamper_map:
+                    self.error("--pool cannot be combined with --tamper_map: a tamper map belongs to one image")
+                if a.pool == "subdirs" and str(a.is_traverse_subdirectories) != "1":
+                    self.error("--pool subdirs needs --is_traverse_subdirectories 1: its sets are the directories that traversal visits")
             if a.align_reliability is not None:
                 if a.align == "none":
                     self.error("--align_reliability requires --align flips or --align d4: it ranks the (record, alignment) pairs of an aligned search "
@@ -1281,15 +1483,23 @@ def build_parser():
                    help="with --align flips or d4: rank the (record, alignment) pairs by level-weighted margins, LEVELS (1..15) reliability levels per lattice "
                         "element, the p-value is a Hoeffding bound over the pairs (with or without --per_record_keys; --l 1, not with --hard, --reliability, "
                         "--keyed_reliability or --window_reliability)")
+    p.add_argument("--pool", default=None, choices=("all", "subdirs"),
+                   help="after the per-image lines, trace SETS of images by pooled evidence, one line per set: all (every traced image is one set) or subdirs "
+                        "(one set per directory; needs --is_traverse_subdirectories 1).  The sets are chosen before looking at scores; at most 1023 images per "
+                        "set (not with --hard, --align or --tamper_map)")
+    p.add_argument("--pool_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
+                   help="with --pool: pool rows of LEVELS (1..15) reliability levels per lattice element instead of unit levels; a set then holds at most "
+                        "1023 // (2^P - 1) images, P the bit length of LEVELS (68 at 15) (--l 1)")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
     return p
 
 
-def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list:
+def _trace_files(files: Sequence[str], args, registry, trace_batch=None, store=None) -> list:
     """files -> outcomes in order (TraceResult or the exception that file raised): decode on host threads, invert and trace in device
     batches; a batch that raises is redone image by image so that each reports its own error (extract._recover_items does the same).
-    trace_batch: None, or what to do with a batch of inverted latents instead of the registry search (`detect` runs its key search here)."""
+    trace_batch: None, or what to do with a batch of inverted latents instead of the registry search (`detect` runs its key search here).
+    store: None, or the `_PoolStore` that keeps every traced image's packed rows for --pool (a file that raises keeps none)."""
     from concurrent.futures import ThreadPoolExecutor
     from . import extract as X
 
@@ -1299,8 +1509,10 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
         except Exception as e:
             return e
 
-    def run(arrs):
+    def run(arrs, names=()):
         latents = X.invert_decoded_images(arrs, args)
+        if store is not None:
+            store.add(names, latents)
         if trace_batch is not None:
             return trace_batch(latents)
         tile = args.tile if getattr(args, "tamper_map", None) else None
@@ -1333,14 +1545,16 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None) -> list
     for k0 in range(0, len(ready), int(args.batch_size)):
         idx = ready[k0:k0 + int(args.batch_size)]
         try:
-            results = run([decoded[i] for i in idx])
+            results = run([decoded[i] for i in idx], [files[i] for i in idx])
         except Exception:
             results = []
             for i in idx:
                 try:
-                    results += run([decoded[i]])
+                    results += run([decoded[i]], [files[i]])
                 except Exception as e:
                     results.append(e)
+                    if store is not None:
+                        store.drop(files[i])
         for i, r in zip(idx, results):
             out[i] = r
     if getattr(args, "tamper_map", None):
@@ -1367,7 +1581,7 @@ def _statistic_name(args) -> str:
     return "hard" if args.hard else "soft" if levels is None else f"soft, {levels} reliability levels"
 
 
-def _report(job, outcomes, args, registry, synthetic: bool) -> None:
+def _report(job, outcomes, args, registry, synthetic: bool, set_lines: Sequence[str] = ()) -> None:
     from . import extract as X
     from datetime import datetime
     M = args.message_length
@@ -1380,11 +1594,16 @@ def _report(job, outcomes, args, registry, synthetic: bool) -> None:
                   ("num_inference_steps", args.num_inference_steps), ("scheduler", args.scheduler)]
         if getattr(args, "align", "none") != "none":
             fields += [("align", args.align), ("align_shift", args.align_shift), ("alignments", _alignment_count(args))]
+        if getattr(args, "pool", None) is not None:
+            fields += [("pool", args.pool)] + ([("pool_reliability", args.pool_reliability)] if args.pool_reliability is not None else [])
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the attributions below are not meaningful\n")
         for f, r in zip(job.files, outcomes):
             line = format_line(f if isinstance(r, Exception) else os.path.basename(f), r, M)
+            print(line)
+            out.write(line + "\n")
+        for line in set_lines:                           # --pool: one line per set, after the per-image lines
             print(line)
             out.write(line + "\n")
         out.write(bar + "Batch End" + bar + "\n")
@@ -1413,17 +1632,30 @@ def main(argv=None):
             jobs = [j for kind, j in script if kind == "job"]
             if any(j.files for j in jobs):
                 X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))      # fail before touching any result file
+            pool = _PoolStore(args, registry) if args.pool is not None else None
+            with_files = [x for kind, x in script if kind == "job" and x.files]
             for kind, x in script:
                 if kind == "banner":
                     print("=" * 20 + x + "=" * 20)
                 elif x.files:
-                    _report(x, _trace_files(x.files, args, registry), args, registry, synthetic)
+                    outcomes = _trace_files(x.files, args, registry, store=pool)
+                    named = []
+                    if args.pool == "subdirs":
+                        named = [(os.path.basename(os.path.normpath(x.path)), x.files)]
+                    elif args.pool == "all" and x is with_files[-1]:     # every traced image of the run: the line follows the last directory's images
+                        named = [("all", [f for j in with_files for f in j.files])]
+                    lines = [format_set_line(name, r) for name, r in pool.trace(named)] if named else []
+                    _report(x, outcomes, args, registry, synthetic, lines)
         elif args.single_image_path != "":
             if synthetic:
                 X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))
                 print(f"{X.SYNTHETIC_MARKER}: '{args.model_id}' is not a local checkpoint, the attribution below is not meaningful", file=sys.stderr)
-            r = _trace_files([args.single_image_path], args, registry)[0]
+            pool = _PoolStore(args, registry) if args.pool is not None else None
+            r = _trace_files([args.single_image_path], args, registry, store=pool)[0]
             print(format_line(args.single_image_path if isinstance(r, Exception) else os.path.basename(args.single_image_path), r, args.message_length))
+            if pool is not None:                         # a set of one: the image's own pooled bound
+                for name, s in pool.trace([("all", [args.single_image_path])]):
+                    print(format_set_line(name, s))
         else:
             print("Please set the argument 'images_directory_path' or 'single_image_path'")
 

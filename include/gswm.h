@@ -896,6 +896,42 @@ int gsw_decode_robust(const uint8_t* signs_dev, const uint8_t* planes_dev, int P
                       int msg_bits, int iters, int sign_rounds, uint8_t* bits_dev, int32_t* score_dev, int32_t* wsum_dev, int32_t* excess_dev,
                       int32_t* wsq_dev, int32_t* weights_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Pooled evidence across the images of a set: every score of the keyed searches is linear in the image, so the
+ * sum of a record's scores over a set of images is its score against ONE pooled row.  Additive: gsw_version() stays 500.
+ *
+ * gsw_pool_rows, one launch per batch of sets:
+ *   signs_dev   : uint8 [B, n_bits / 8], packed sign rows (gsw_sign_pack, gsw_quant_pack, gsw_level_pack[_l]); any alignment
+ *   planes_dev  : uint8 [B, P, n_bits / 8], gsw_level_pack[_l]'s planes with P in 1 .. 4, or null with P = 0: every level is 1
+ *   set_ptr_dev : int32 [G + 1], 4-byte aligned: set g is the images set_ptr[g] .. set_ptr[g + 1] - 1; set_ptr[0] = 0, strictly ascending,
+ *                 set_ptr[G] = B (the caller gathers the images of a set into that order; indices outside [0, B] are clipped, not read)
+ *   max_set     : the size of the largest set, stated by the caller (set_ptr lives on the device)
+ *   Q           : planes of the pooled rows, 1 .. 10, at least the bit length of Lmax max_set with Lmax = 2^P - 1 (1 with P = 0)
+ * With lev_bj = sum_k 2^k (bit j of plane k of image b) (1 with P = 0), h_bj bit j of the sign row and S_j = sum over the set of lev_bj (1 - 2 h_bj):
+ *   out_signs_dev  : uint8 [G, n_bits / 8], bit j = (S_j < 0)
+ *   out_planes_dev : uint8 [G, Q, n_bits / 8], plane k = bit k of |S_j|, packed as the rows (S_j = 0: sign 0, level 0)
+ *   wsum_dev       : int32 [G], sum_j |S_j|            wsq_dev : int64 [G], 8-byte aligned, sum_j S_j^2
+ * Every output byte is written, no atomics, no workspace, integer arithmetic only; a set larger than max_set loses the bits above plane Q - 1.
+ * GSW_ERR_BAD_ARG: null pointer (planes_dev present exactly when P > 0), set_ptr_dev / wsum_dev / wsq_dev misaligned, P outside 0..4, B, G or
+ * max_set < 1, G or max_set > B, n_bits < 8 or not a multiple of 8, Q < 1 or below the bit length above when that is at most 10.
+ * GSW_ERR_UNSUPPORTED: Q or that bit length above 10 (more than 1023 images at unit levels, more than 68 at 15 levels), n_bits (1 + Q) >
+ * 1 048 576 (the searches' domain), n_bits (2^Q - 1) >= 2^31.  In that order; every refusal happens before any launch.
+ *
+ * gsw_trace_keyed_pooled_topk: gsw_trace_keyed_soft_topk for rows of Q in 1 .. 10 planes, G sets in the place of its B images.
+ * records_dev, record_stride, msg_bytes, n_records, k, idx_dev, score_dev and workspace_dev (gsw_trace_keyed_workspace_bytes(G, n_records,
+ * k) bytes) as gsw_trace_keyed_topk; signs_dev, planes_dev, wsum_dev as gsw_pool_rows writes them.
+ *   score[g, u] = wsum[g] - 2 sum_{k < Q} 2^k popcount(plane_k[g] & (signs[g] ^ codeword[u])), an exact int32: the sum over the set's images of
+ *                 gsw_trace_keyed_topk's (P = 0) or gsw_trace_keyed_soft_topk's score of record u
+ *   out         : the k best records per set by (score descending, index ascending), idx = -1 / score = INT32_MIN past the end
+ * GSW_ERR_BAD_ARG: as gsw_trace_keyed_soft_topk, with Q < 1 in the place of its levels.  GSW_ERR_RAGGED: n_bits is not a multiple of
+ * 8 msg_bytes.  GSW_ERR_UNSUPPORTED: Q > 10, n_bits (1 + Q) > 1 048 576, n_bits (2^Q - 1) >= 2^31, G > 65535, or the 1 + Q rows, each padded
+ * to whole 64-byte blocks, beyond 128 KiB of LDS (a ragged row at the very end of the domain). */
+int gsw_pool_rows(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int B, int64_t n_bits, const int32_t* set_ptr_dev, int G, int max_set, int Q,
+                  uint8_t* out_signs_dev, uint8_t* out_planes_dev, int32_t* wsum_dev, int64_t* wsq_dev, void* stream);
+int gsw_trace_keyed_pooled_topk(const uint8_t* signs_dev, const uint8_t* planes_dev, const int32_t* wsum_dev, int Q, int G, int64_t n_bits,
+                                const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records, int k, int32_t* idx_dev,
+                                int32_t* score_dev, void* workspace_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
