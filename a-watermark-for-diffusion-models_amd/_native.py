@@ -167,6 +167,10 @@ _PROTOTYPES = {
                                    C.c_void_p]),
     "gsw_level_counts_align": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gsw_level_rows_align_l": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "gsw_level_counts_align_l": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_char_p,
+                                           C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gsw_pool_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
     "gsw_trace_keyed_pooled_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64,

@@ -255,15 +255,16 @@ SOFT_STAT_BITS = 25                     # the level-weighted statistic is at mos
 
 
 def _search_level_rows(rows: "codec.LevelRows", shape, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], k: int,
-                       budget_bytes: Optional[int] = None):
-    """`search_keys_soft` from `codec.level_pack`'s rows on: `_search_packed` with 1 + P rows per aligned image"""
+                       budget_bytes: Optional[int] = None, l: int = 1):
+    """`search_keys_soft` from `codec.level_pack`'s rows on, and `search_keys_soft_l` from `codec.level_pack_l`'s at that l: `_search_packed` with 1 + P rows per
+    aligned image"""
     shape = tuple(int(s) for s in shape)
     table = _device_table(aligns, shape, rows.signs.device)
     B, rowbytes = rows.signs.shape
     P = rows.planes.shape[1]
 
     def search(rows_b, aligns_dev):
-        signs, planes = codec._level_rows_align_launch(rows_b, shape, aligns_dev)
+        signs, planes = codec._level_rows_align_launch(rows_b, shape, aligns_dev, l)
         al = codec.LevelRows(signs.view(-1, rowbytes), planes.view(-1, P, rowbytes), rows_b.wsum, rows_b.wsq, rows_b.flags)   # (the search reads signs and planes alone)
         return codec.key_search_soft_topk(al, rowbytes * 8, keys_dev, msg_bytes, k=int(k))
 
@@ -291,6 +292,29 @@ def search_keys_soft(latents: torch.Tensor, keys_dev: torch.Tensor, msg_bytes: i
     rows = codec.level_pack(z, thresholds)
     codec._level_rows_align_checks(rows, z.shape[1:])
     return _search_level_rows(rows, z.shape[1:], keys_dev, msg_bytes, table, k, budget_bytes)
+
+
+def search_keys_soft_l(latents: torch.Tensor, keys_dev: torch.Tensor, msg_bytes: int, aligns: Sequence[Alignment], l: int, *, levels: int = 15,
+                       clip: float = 2.5, thresholds: Optional[torch.Tensor] = None, k: int = 1, budget_bytes: Optional[int] = None):
+    """`search_keys_soft` for multi-bit windows (l = 2 or 4): (key_idx, align_idx, stat), int32 [B, k] each, on the device; stat is
+    `codec.key_search_soft_topk`'s level-weighted statistic over the n l cipher bits of the image under that alignment.
+
+    thresholds: float32 [l, levels] or [B, l, levels] as `codec.level_pack_l` takes them (`levels` and `clip` are then not read); None:
+    `soft.window_thresholds(latents, l, levels, clip)`, computed ONCE on the un-aligned latents.  One `codec.level_pack_l`, then per chunk of images one
+    `codec.level_rows_align_l` launch -- the l window bits of an element and its l level bits in every plane move together -- and one
+    `codec.key_search_soft_topk` on its [B A] rows with n_bits = n l, and `search_keys`' merge per image.  The cuts and the merge are `search_keys_soft`'s.
+    l = 1 is refused: that is `search_keys_soft`."""
+    l = codec._multi_bit_window(l, "search_keys_soft")
+    if latents.dim() != 4:
+        raise ValueError(f"search_keys_soft_l needs latents [B, C, H, W], got {tuple(latents.shape)}")
+    table = _as_list(aligns, *latents.shape[2:])
+    z = latents.contiguous()
+    if thresholds is None:
+        from . import soft as S
+        thresholds = S.window_thresholds(z, l, levels, clip)
+    rows = codec.level_pack_l(z, thresholds, l)
+    codec._level_rows_align_checks(rows, z.shape[1:], l)
+    return _search_level_rows(rows, z.shape[1:], keys_dev, msg_bytes, table, k, budget_bytes, l)
 
 
 # ===================================================================================================================== known key
@@ -345,9 +369,25 @@ def extract_aligned_soft(latents: torch.Tensor, key: bytes, nonce: bytes, messag
     codec._check_key_nonce(key, nonce)
     ring = D.Keyring()
     ring.add("key", key, nonce)
-    results, aidx, bits = D._aligned_soft(latents, ring, message_length, aligns, levels, 1, fpr)
+    return _aligned_extracts(*D._aligned_soft(latents, ring, message_length, aligns, levels, 1, fpr))
+
+
+def _aligned_extracts(results, aidx, bits) -> List[AlignedExtract]:
     out = []
     for r, i, row in zip(results, aidx, bits):
         c = r.candidates[0]
         out.append(AlignedExtract(c.alignment, int(i), c.stat, c.log10_p_any, r.key_id is not None, row.copy(), r.flags))
     return out
+
+
+def extract_aligned_soft_l(latents: torch.Tensor, key: bytes, nonce: bytes, message_length: int, aligns: Sequence[Alignment], l: int, *, levels: int = 15,
+                           fpr: float = 1e-6) -> List[AlignedExtract]:
+    """`extract_aligned_soft` for multi-bit windows (l = 2 or 4), a keyring of one through `detect.detect_latents_aligned_soft_l`: per image the best alignment
+    by the level-weighted statistic over its n l cipher bits, its Chernoff bound given the levels under that alignment over the A candidates, and the soft vote
+    (`codec.extract_soft_l`, the same thresholds) on the latent with that alignment applied.  l = 1 is refused: that is `extract_aligned_soft`."""
+    from . import detect as D
+    codec._check_key_nonce(key, nonce)
+    l = codec._multi_bit_window(l, "extract_aligned_soft")
+    ring = D.Keyring()
+    ring.add("key", key, nonce)
+    return _aligned_extracts(*D._aligned_soft(latents, ring, message_length, aligns, levels, 1, fpr, l))

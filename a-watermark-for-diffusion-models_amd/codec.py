@@ -957,28 +957,31 @@ def key_search_soft_topk(rows: LevelRows, n_bits: int, keys: torch.Tensor, msg_b
 
 
 # ------------------------------------------------------------------------------------------------ alignment search ranked by reliability levels
-def _level_rows_align_launch(rows: LevelRows, shape: Tuple[int, int, int], aligns_dev: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """`level_rows_align` after its checks -> (signs uint8 [B, A, rowbytes], planes uint8 [B, A, P, rowbytes])"""
+def _level_rows_align_launch(rows: LevelRows, shape: Tuple[int, int, int], aligns_dev: torch.Tensor, l: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`level_rows_align` (l = 1) and `level_rows_align_l` (l = 2, 4) after their checks -> (signs uint8 [B, A, rowbytes], planes uint8 [B, A, P, rowbytes])"""
     B, rowbytes = rows.signs.shape
     P, A = rows.planes.shape[1], aligns_dev.shape[0]
     signs = torch.empty((B, A, rowbytes), dtype=torch.uint8, device=rows.signs.device)
     planes = torch.empty((B, A, P, rowbytes), dtype=torch.uint8, device=rows.signs.device)
+    window = () if l == 1 else (l,)                                 # gsw_level_rows_align_l takes l after P, gsw_level_rows_align has no such argument
     with torch.cuda.device(rows.signs.device):
-        N.check(N.lib().gsw_level_rows_align(rows.signs.data_ptr(), rows.planes.data_ptr(), P, B, shape[0], shape[1], shape[2], aligns_dev.data_ptr(), A,
-                                             signs.data_ptr(), planes.data_ptr(), _stream_ptr()))
+        launch = N.lib().gsw_level_rows_align if l == 1 else N.lib().gsw_level_rows_align_l
+        N.check(launch(rows.signs.data_ptr(), rows.planes.data_ptr(), P, *window, B, shape[0], shape[1], shape[2], aligns_dev.data_ptr(), A,
+                       signs.data_ptr(), planes.data_ptr(), _stream_ptr()))
     return signs, planes
 
 
-def _level_rows_align_checks(rows: LevelRows, shape) -> Tuple[int, int, int]:
-    """The operand checks of `level_rows_align` (everything but the list of alignments) -> (C, H, W)"""
+def _level_rows_align_checks(rows: LevelRows, shape, l: int = 1) -> Tuple[int, int, int]:
+    """The operand checks of `level_rows_align` and, with l = 2 or 4, of `level_rows_align_l` (everything but the list of alignments) -> (C, H, W)"""
     shape = _lattice_shape(shape)
     signs, planes = rows.signs, rows.planes
     _need_gpu(signs, "rows.signs")
-    n = shape[0] * shape[1] * shape[2]
+    n = shape[0] * shape[1] * shape[2] * l                          # the bits of a row
+    at = "" if l == 1 else f" at l = {l}"
     if n % 8:
-        raise ValueError(f"a lattice of {shape} holds {n} bits: not whole bytes")
+        raise ValueError(f"a lattice of {shape}{at} holds {n} bits: not whole bytes")
     if signs.dtype != torch.uint8 or signs.dim() != 2 or signs.shape[0] < 1 or signs.shape[1] * 8 != n:
-        raise ValueError(f"rows.signs must be uint8 [B, {n // 8}] with B >= 1 for a lattice of {shape}, got {signs.dtype} {tuple(signs.shape)}")
+        raise ValueError(f"rows.signs must be uint8 [B, {n // 8}] with B >= 1 for a lattice of {shape}{at}, got {signs.dtype} {tuple(signs.shape)}")
     B = signs.shape[0]
     for t, name, check in _level_rows_checks(rows, True) + ((rows.wsq, "rows.wsq", None), (rows.flags, "rows.flags", None)):
         _need_gpu(t, name)
@@ -991,8 +994,27 @@ def _level_rows_align_checks(rows: LevelRows, shape) -> Tuple[int, int, int]:
     if n * (1 + P) > ROW_MAX_BITS:
         raise ValueError(f"a lattice of {n} bits with {P} level planes is beyond the search's domain: n_bits (1 + P) <= {ROW_MAX_BITS}")
     if B > 65535:
-        raise ValueError(f"level_rows_align takes at most 65535 images per launch, got {B}")
+        raise ValueError(f"level_rows_align{'' if l == 1 else '_l'} takes at most 65535 images per launch, got {B}")
     return shape
+
+
+def _aligns_operand(aligns, shape: Tuple[int, int, int], ref: torch.Tensor) -> torch.Tensor:
+    """A list of alignments, or a device table, checked by `align_table` -> the int32 [A, 3] table on ref's device"""
+    table = align_table(aligns, shape)
+    if not isinstance(aligns, torch.Tensor):
+        return torch.from_numpy(table).to(ref.device)
+    _need_gpu(aligns, "aligns")
+    _same_device(aligns, ref, "aligns")
+    if aligns.dim() != 2:
+        raise ValueError("aligns must be int32 [A, 3]")
+    return aligns if aligns.is_contiguous() else aligns.contiguous()
+
+
+def _aligned_level_rows(rows: LevelRows, signs: torch.Tensor, planes: torch.Tensor) -> LevelRows:
+    """[B, A, ...] aligned rows as the `LevelRows` of B A images: wsum, wsq and flags are the image's, repeated (a permutation keeps them)"""
+    B, A, rowbytes = signs.shape
+    return LevelRows(signs.view(B * A, rowbytes), planes.view(B * A, planes.shape[2], rowbytes), rows.wsum.repeat_interleave(A), rows.wsq.repeat_interleave(A),
+                     rows.flags.repeat_interleave(A))
 
 
 def level_rows_align(rows: LevelRows, shape: Sequence[int], aligns) -> LevelRows:
@@ -1006,20 +1028,25 @@ def level_rows_align(rows: LevelRows, shape: Sequence[int], aligns) -> LevelRows
     permutation keeps them).  RuntimeError for host tensors (there is no CPU fallback); ValueError for a ragged lattice, n (1 + P) beyond 1 048 576,
     more than 65 535 images, and the list checks of `rows_align` -- all before any launch."""
     shape = _level_rows_align_checks(rows, shape)
-    table = align_table(aligns, shape)
-    if isinstance(aligns, torch.Tensor):
-        _need_gpu(aligns, "aligns")
-        _same_device(aligns, rows.signs, "aligns")
-        if aligns.dim() != 2:
-            raise ValueError("aligns must be int32 [A, 3]")
-        aligns_dev = aligns if aligns.is_contiguous() else aligns.contiguous()
-    else:
-        aligns_dev = torch.from_numpy(table).to(rows.signs.device)
-    A = table.shape[0]
-    signs, planes = _level_rows_align_launch(rows, shape, aligns_dev)
-    B, P, rowbytes = rows.planes.shape
-    return LevelRows(signs.view(B * A, rowbytes), planes.view(B * A, P, rowbytes), rows.wsum.repeat_interleave(A), rows.wsq.repeat_interleave(A),
-                     rows.flags.repeat_interleave(A))
+    aligns_dev = _aligns_operand(aligns, shape, rows.signs)
+    return _aligned_level_rows(rows, *_level_rows_align_launch(rows, shape, aligns_dev))
+
+
+def level_rows_align_l(rows: LevelRows, shape: Sequence[int], l: int, aligns) -> LevelRows:
+    """`level_rows_align` at l = 2 or 4, in one launch (gsw_level_rows_align_l): every candidate alignment of `level_pack_l`'s rows, signs uint8
+    [B A, n l / 8] and planes uint8 [B A, P, n l / 8], row b A + a the rows of image b under aligns[a] -- the operand of `key_search_soft_topk`
+    and `trace_keyed_soft_topk` with n_bits = n l as it is.
+
+    rows: `level_pack_l`'s result for latents [B, C, H, W] at that l; shape = (C, H, W); aligns as `level_rows_align` takes them.  Every row is bit
+    for bit `rows_align` of that input row at l, and the rows of (b, a) are `level_pack_l(align.apply(z[b], aligns[a]), thresholds[b], l)` for the
+    thresholds the rows were packed with: the kernel computes where an ELEMENT comes from once and moves its l window bits and the l level bits of
+    every plane together.  wsum, wsq and flags are those of the image, repeated A times.  ValueError for l outside (2, 4) -- l = 1 is
+    `level_rows_align` -- then `level_rows_align`'s refusals with n l bits per row: a ragged lattice, n l (1 + P) beyond 1 048 576, more than
+    65 535 images, the list checks of `rows_align`; RuntimeError for host tensors -- all before any launch."""
+    l = _multi_bit_window(l, "level_rows_align")
+    shape = _level_rows_align_checks(rows, shape, l)
+    aligns_dev = _aligns_operand(aligns, shape, rows.signs)
+    return _aligned_level_rows(rows, *_level_rows_align_launch(rows, shape, aligns_dev, l))
 
 
 # ------------------------------------------------------------------------------------------------ aligned registry search ranked by reliability levels
@@ -1037,29 +1064,31 @@ def level_counts_align_lds_bytes(n_bits: int, P: int, msg_bits: int) -> int:
 
 
 def _level_counts_align_launch(rows: LevelRows, shape: Tuple[int, int, int], aligns_dev: torch.Tensor, key: bytes, nonce: bytes, msg_bits: int, bias: int = 0,
-                               return_wsum: bool = False):
+                               return_wsum: bool = False, l: int = 1):
     """`level_counts_align` after its checks: rows of a [C, H, W] lattice, an `align_table` on their device, a checked key and nonce, a message length the lattice
     tiles and a bias within `_level_counts_align_limits` -> score int32 [B, A, msg_bits], or (score, wsum)"""
     B, P, A = rows.signs.shape[0], rows.planes.shape[1], aligns_dev.shape[0]
     dev = rows.signs.device
     score = torch.empty((B, A, int(msg_bits)), dtype=torch.int32, device=dev)
     wsum = torch.empty_like(score) if return_wsum else None
+    window = () if l == 1 else (l,)                                 # gsw_level_counts_align_l takes l after P
     with torch.cuda.device(dev):
-        N.check(N.lib().gsw_level_counts_align(rows.signs.data_ptr(), rows.planes.data_ptr(), P, B, shape[0], shape[1], shape[2], aligns_dev.data_ptr(), A, key, nonce,
-                                               int(msg_bits), int(bias), score.data_ptr(), wsum.data_ptr() if return_wsum else None, _stream_ptr()))
+        launch = N.lib().gsw_level_counts_align if l == 1 else N.lib().gsw_level_counts_align_l
+        N.check(launch(rows.signs.data_ptr(), rows.planes.data_ptr(), P, *window, B, shape[0], shape[1], shape[2], aligns_dev.data_ptr(), A, key, nonce,
+                       int(msg_bits), int(bias), score.data_ptr(), wsum.data_ptr() if return_wsum else None, _stream_ptr()))
     return (score, wsum) if return_wsum else score
 
 
-def _level_counts_align_limits(shape: Tuple[int, int, int], P: int, msg_bits: int, bias) -> int:
-    """bias as `level_counts_align` takes it for a [C, H, W] lattice with P planes and a checked msg_bits, or ValueError: the staged regions pass the LDS cap, or
-    |bias| + 15 copies leaves int32"""
-    n = shape[0] * shape[1] * shape[2]
+def _level_counts_align_limits(shape: Tuple[int, int, int], P: int, msg_bits: int, bias, l: int = 1) -> int:
+    """bias as `level_counts_align` (and, with l = 2 or 4, `level_counts_align_l`) takes it for a [C, H, W] lattice with P planes and a checked msg_bits, or
+    ValueError: the staged regions pass the LDS cap, or |bias| + 15 copies leaves int32"""
+    n = shape[0] * shape[1] * shape[2] * l                          # the bits of a row
     if isinstance(bias, bool) or not isinstance(bias, (int, np.integer)):
         raise ValueError(f"bias must be an int, got {bias!r}")
     lds = level_counts_align_lds_bytes(n, P, msg_bits)
     if lds > LEVEL_COUNTS_ALIGN_LDS_CAP:
-        raise ValueError(f"a lattice of {shape} with {P} level planes and {msg_bits}-bit messages needs {lds} bytes of LDS in level_counts_align, "
-                         f"more than {LEVEL_COUNTS_ALIGN_LDS_CAP}")
+        raise ValueError(f"a lattice of {shape}{'' if l == 1 else f' at l = {l}'} with {P} level planes and {msg_bits}-bit messages needs {lds} bytes of LDS in "
+                         f"level_counts_align{'' if l == 1 else '_l'}, more than {LEVEL_COUNTS_ALIGN_LDS_CAP}")
     if abs(int(bias)) + SOFT_MAX_LEVELS * (n // msg_bits) >= 2 ** 31:
         raise ValueError(f"bias {bias} plus {SOFT_MAX_LEVELS} x {n // msg_bits} copies does not fit int32")
     return int(bias)
@@ -1079,16 +1108,32 @@ def level_counts_align(rows: LevelRows, shape: Sequence[int], aligns, key: bytes
     shape = _level_rows_align_checks(rows, shape)
     msg_bits = _counts_align_message(shape, 1, msg_bits)
     bias = _level_counts_align_limits(shape, rows.planes.shape[1], msg_bits, bias)
-    table = align_table(aligns, shape)
-    if isinstance(aligns, torch.Tensor):
-        _need_gpu(aligns, "aligns")
-        _same_device(aligns, rows.signs, "aligns")
-        if aligns.dim() != 2:
-            raise ValueError("aligns must be int32 [A, 3]")
-        aligns_dev = aligns if aligns.is_contiguous() else aligns.contiguous()
-    else:
-        aligns_dev = torch.from_numpy(table).to(rows.signs.device)
+    aligns_dev = _aligns_operand(aligns, shape, rows.signs)
     return _level_counts_align_launch(rows, shape, aligns_dev, key, nonce, msg_bits, bias, bool(return_wsum))
+
+
+def level_counts_align_l_lds_bytes(n_bits: int, P: int, msg_bits: int) -> int:
+    """The LDS bytes of one `level_counts_align_l` workgroup for rows of n_bits = n l bits: `level_counts_align_lds_bytes` of such a row
+    (csrc/gswm_counts_align_soft_l_plan.h lays the regions out as the l = 1 plan does)"""
+    return level_counts_align_lds_bytes(n_bits, P, msg_bits)
+
+
+def level_counts_align_l(rows: LevelRows, shape: Sequence[int], l: int, aligns, key: bytes, nonce: bytes, msg_bits: int, *, bias: int = 0, return_wsum: bool = False):
+    """`level_counts_align` at l = 2 or 4, in one launch (gsw_level_counts_align_l): the level-weighted vote of every candidate alignment of
+    `level_pack_l`'s rows under one key, int32 [B, A, msg_bits], or the pair (score, wsum) with return_wsum.
+
+    rows, shape, l and aligns as `level_rows_align_l` takes them.  score[b, a] - bias and wsum[b, a] are bit for bit the `score` and `wsum` of
+    `extract_soft_l(align.apply(z[b], aligns[a]), ..., l)` under (key, nonce) with the thresholds the rows were packed with, summed over the n l cipher
+    positions.  The aligned rows are never written.  With bias = levels * copies, copies = n l / msg_bits, the scores viewed as [B A, msg_bits] are the
+    counts' of `trace.reliability_counts` and go to `trace_topk` as they are.  ValueError for l outside (2, 4) -- l = 1 is `level_counts_align` -- then that
+    function's refusals with n l bits per row (128 KiB of LDS hold a 4 x 64 x 64 lattice at l = 4 and 15 levels in 80 KiB) -- all before any launch."""
+    _check_key_nonce(key, nonce)
+    l = _multi_bit_window(l, "level_counts_align")
+    shape = _level_rows_align_checks(rows, shape, l)
+    msg_bits = _counts_align_message(shape, l, msg_bits)
+    bias = _level_counts_align_limits(shape, rows.planes.shape[1], msg_bits, bias, l)
+    aligns_dev = _aligns_operand(aligns, shape, rows.signs)
+    return _level_counts_align_launch(rows, shape, aligns_dev, key, nonce, msg_bits, bias, bool(return_wsum), l)
 
 
 # ------------------------------------------------------------------------------------------------ localising edits (tile map, tile-weighted vote)

@@ -22,7 +22,8 @@
 // level_align_decide is the whole launch policy and every refusal; the entry point only fills LevelAlignArgs from its plan.  All arithmetic is integer.
 //
 // Kernel
-//   gsw_level_rows_align_kernel<P, SG> : P level planes (1..4), SG: the source rows are read from global memory
+//   gsw_level_rows_align_kernel<L, P, SG> : L bits per element (1 here; 2 and 4 are gswm_align_soft_l.inc's), P level planes (1..4), SG: the source rows are
+//                                           read from global memory
 
 namespace {
 
@@ -80,9 +81,9 @@ struct LevelAlignArgs {
     int C, H, W, A, chunk, rowbytes, lstride;
 };
 
-// `count` elements from output element e0 on, MSB first in the low count bits of acc[r], for the R rows src[0 .. R): the source bit of an element is
-// computed once and read from every row
-template <int R, typename Src>
+// `count` elements of L bits from output element e0 on, MSB first in the low count * L bits of acc[r], for the R rows src[0 .. R): the source group of an
+// element is computed once and read from every row (L in 1, 2, 4 divides 8: a group never straddles a byte)
+template <int L, int R, typename Src>
 __device__ __forceinline__ void level_align_gather(const Src (&src)[R], const AlignMap& m, int e0, int count, int H, int W, uint32_t (&acc)[R]) {
     const int hw = H * W;
     const int c = e0 / hw, r = e0 - c * hw;
@@ -95,10 +96,10 @@ __device__ __forceinline__ void level_align_gather(const Src (&src)[R], const Al
     for (int q = 0; q < R; ++q) acc[q] = 0u;
 #pragma unroll 8
     for (int k = 0; k < count; ++k) {
-        const uint32_t pbit = (uint32_t)(cb + i * m.si + j * m.sj);
-        const uint32_t at = pbit >> 3, sh = 7u - (pbit & 7u);
+        const uint32_t pbit = (uint32_t)(cb + i * m.si + j * m.sj) * L;
+        const uint32_t at = pbit >> 3, sh = (8u - L) - (pbit & 7u);
 #pragma unroll
-        for (int q = 0; q < R; ++q) acc[q] = (acc[q] << 1) | (((uint32_t)src[q][at] >> sh) & 1u);
+        for (int q = 0; q < R; ++q) acc[q] = (acc[q] << L) | (((uint32_t)src[q][at] >> sh) & ((1u << L) - 1u));
         ++x;
         if (++j == W) j = 0;
         if (x == W) {
@@ -119,10 +120,10 @@ __device__ __forceinline__ void level_align_store_word(uint8_t* at, uint32_t v) 
     }
 }
 
-template <int P, bool SG>
+template <int L, int P, bool SG>
 __global__ __launch_bounds__(LA_WG) void gsw_level_rows_align_kernel(LevelAlignArgs s) {
     extern __shared__ __attribute__((aligned(16))) uint8_t la_lds[];
-    constexpr int R = 1 + P;
+    constexpr int R = 1 + P, EPW = 32 / L, EPB = 8 / L;             // elements per output word, per byte
     const int tid = threadIdx.x, b = blockIdx.y;
     const uint8_t* src[R];
     src[0] = s.signs + (int64_t)b * s.rowbytes;
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(LA_WG) void gsw_level_rows_align_kernel(LevelAlignA
             uint32_t acc[R];
 #pragma unroll
             for (int q = 0; q < R; ++q) acc[q] = 0u;
-            if (m.ok) level_align_gather<R>(src, m, (head + 4 * w) * 8, 32, s.H, s.W, acc);
+            if (m.ok) level_align_gather<L, R>(src, m, (head + 4 * w) * EPB, EPW, s.H, s.W, acc);
 #pragma unroll
             for (int q = 0; q < R; ++q) level_align_store_word(orow[q] + head + 4 * w, __builtin_bswap32(acc[q]));   // MSB first: the first element lands in the lowest address
         }
@@ -172,16 +173,16 @@ __global__ __launch_bounds__(LA_WG) void gsw_level_rows_align_kernel(LevelAlignA
             uint32_t acc[R];
 #pragma unroll
             for (int q = 0; q < R; ++q) acc[q] = 0u;
-            if (m.ok) level_align_gather<R>(src, m, byte * 8, 8, s.H, s.W, acc);
+            if (m.ok) level_align_gather<L, R>(src, m, byte * EPB, EPB, s.H, s.W, acc);
 #pragma unroll
             for (int q = 0; q < R; ++q) orow[q][byte] = (uint8_t)acc[q];
         }
     }
 }
 
-template <int P>
+template <int L, int P>
 int launch_level_rows_align(const LevelAlignArgs& s, const LevelAlignPlan& p, hipStream_t st) {
-    void (*kernel)(LevelAlignArgs) = p.sg ? gsw_level_rows_align_kernel<P, true> : gsw_level_rows_align_kernel<P, false>;
+    void (*kernel)(LevelAlignArgs) = p.sg ? gsw_level_rows_align_kernel<L, P, true> : gsw_level_rows_align_kernel<L, P, false>;
     GSW_HIP(allow_dynamic_lds((const void*)kernel, p.lds));
     hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y), dim3(LA_WG), p.lds, st, s);
     GSW_HIP(hipGetLastError());
@@ -199,10 +200,10 @@ int gsw_level_rows_align(const uint8_t* signs_dev, const uint8_t* planes_dev, in
     if (p.status != GSW_OK) return p.status;
     const LevelAlignArgs s{signs_dev, planes_dev, aligns_dev, out_signs_dev, out_planes_dev, C, H, W, A, p.chunk, p.rowbytes, p.lstride};
     switch (P) {
-        case 1: return launch_level_rows_align<1>(s, p, (hipStream_t)stream);
-        case 2: return launch_level_rows_align<2>(s, p, (hipStream_t)stream);
-        case 3: return launch_level_rows_align<3>(s, p, (hipStream_t)stream);
-        default: return launch_level_rows_align<4>(s, p, (hipStream_t)stream);
+        case 1: return launch_level_rows_align<1, 1>(s, p, (hipStream_t)stream);
+        case 2: return launch_level_rows_align<1, 2>(s, p, (hipStream_t)stream);
+        case 3: return launch_level_rows_align<1, 3>(s, p, (hipStream_t)stream);
+        default: return launch_level_rows_align<1, 4>(s, p, (hipStream_t)stream);
     }
 }
 

@@ -12,7 +12,7 @@
 //
 // Work split as gsw_counts_align_kernel.  Grid (alignment chunks, images), 256 lanes.  A workgroup stages its image's 1 + P rows and generates the keystream into
 // LDS, both once, then walks its chunk.  Per alignment, on the word path (M % 32 == 0): a lane computes the source bit of each of a word's 32 elements ONCE
-// (level_align_gather<1 + P>), forms d = signs ^ keystream once, and per plane k adds plane_k & d to the vertical counters X_k and plane_k to N_k.  Lane `tid`
+// (level_align_gather<L, 1 + P>), forms d = signs ^ keystream once, and per plane k adds plane_k & d to the vertical counters X_k and plane_k to N_k.  Lane `tid`
 // only ever sees message word tid % (M / 32), so its counters are 32 adjacent message positions.  It combines its planes in registers, X' = sum_k 2^k X_k and
 // N' = sum_k 2^k N_k (two positions per dword, 11 bits used of 16), leaves 32 + 32 uint16 in the reduction region, and after a barrier lane t sums column t over
 // the lanes that share its message word and stores bias + 2 X' - N' and N': coalesced dwords, no atomic.  The byte path (any other M % 8 == 0) is the same
@@ -22,7 +22,8 @@
 // through it.
 //
 // Kernel
-//   gsw_level_counts_align_kernel<P, WORDS> : P level planes (1..4); WORDS: the word path
+//   gsw_level_counts_align_kernel<L, P, WORDS> : L bits per element (1 here; 2 and 4 are gswm_counts_align_soft_l.inc's), P level planes (1..4); WORDS: the
+//                                                word path
 
 namespace {
 
@@ -47,10 +48,10 @@ __device__ __forceinline__ uint32_t lca_nibble_counts(const uint32_t (&c)[LCA_PL
     return v;
 }
 
-template <int P, bool WORDS>
+template <int L, int P, bool WORDS>
 __global__ __launch_bounds__(LCA_WG) void gsw_level_counts_align_kernel(LevelCountsAlignArgs s) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lca_lds[];
-    constexpr int R = 1 + P;
+    constexpr int R = 1 + P, EPW = 32 / L, EPB = 8 / L;             // elements per word of the row, per byte
     const int tid = threadIdx.x, b = blockIdx.y;
     uint32_t* ks_words = (uint32_t*)(lca_lds + s.off_ks);
     uint8_t* red_x = lca_lds + s.off_red;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(LCA_WG) void gsw_level_counts_align_kernel(LevelCou
                 const int nwords = s.rowbytes >> 2;
                 for (int w = tid; w < nwords; w += s.lanes) {
                     uint32_t acc[R];
-                    level_align_gather<R>(src, m, w * 32, 32, s.H, s.W, acc);
+                    level_align_gather<L, R>(src, m, w * EPW, EPW, s.H, s.W, acc);
                     const uint32_t d = acc[0] ^ __builtin_bswap32(ks_words[w]);           // MSB first: bit 31 - q is position 32 w + q
 #pragma unroll
                     for (int k = 0; k < P; ++k) {
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(LCA_WG) void gsw_level_counts_align_kernel(LevelCou
                 const uint8_t* ks_bytes = (const uint8_t*)ks_words;
                 for (int j = tid; j < s.rowbytes; j += s.lanes) {
                     uint32_t acc[R];
-                    level_align_gather<R>(src, m, j * 8, 8, s.H, s.W, acc);
+                    level_align_gather<L, R>(src, m, j * EPB, EPB, s.H, s.W, acc);
                     const uint32_t d = acc[0] ^ (uint32_t)ks_bytes[j];
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
@@ -159,9 +160,9 @@ __global__ __launch_bounds__(LCA_WG) void gsw_level_counts_align_kernel(LevelCou
     }
 }
 
-template <int P>
+template <int L, int P>
 int launch_level_counts_align(const LevelCountsAlignArgs& s, const LevelCountsAlignPlan& p, hipStream_t st) {
-    void (*kernel)(LevelCountsAlignArgs) = p.words ? gsw_level_counts_align_kernel<P, true> : gsw_level_counts_align_kernel<P, false>;
+    void (*kernel)(LevelCountsAlignArgs) = p.words ? gsw_level_counts_align_kernel<L, P, true> : gsw_level_counts_align_kernel<L, P, false>;
     GSW_HIP(allow_dynamic_lds((const void*)kernel, p.lds));
     hipLaunchKernelGGL(kernel, dim3(p.grid_x, p.grid_y), dim3(LCA_WG), p.lds, st, s);
     GSW_HIP(hipGetLastError());
@@ -185,10 +186,10 @@ int gsw_level_counts_align(const uint8_t* signs_dev, const uint8_t* planes_dev, 
                                  C, H, W, A, p.chunk, p.rowbytes, p.lstride, p.nblk, msg_bits, p.lanes, p.groups, p.cplanes, bias,
                                  p.off_ks, p.off_red, p.off_red_n};
     switch (P) {
-        case 1: return launch_level_counts_align<1>(s, p, (hipStream_t)stream);
-        case 2: return launch_level_counts_align<2>(s, p, (hipStream_t)stream);
-        case 3: return launch_level_counts_align<3>(s, p, (hipStream_t)stream);
-        default: return launch_level_counts_align<4>(s, p, (hipStream_t)stream);
+        case 1: return launch_level_counts_align<1, 1>(s, p, (hipStream_t)stream);
+        case 2: return launch_level_counts_align<1, 2>(s, p, (hipStream_t)stream);
+        case 3: return launch_level_counts_align<1, 3>(s, p, (hipStream_t)stream);
+        default: return launch_level_counts_align<1, 4>(s, p, (hipStream_t)stream);
     }
 }
 

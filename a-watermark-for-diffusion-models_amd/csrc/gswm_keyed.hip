@@ -57,6 +57,7 @@
 #include "gswm_keysearch_soft_plan.h"   // key_soft_decide: the same for the level-weighted key search
 #include "gswm_counts_align_plan.h"   // counts_align_decide: the same for the vote counts of every alignment under one key
 #include "gswm_counts_align_soft_plan.h"   // level_counts_align_decide: the same for the level-weighted vote of every alignment under one key
+#include "gswm_counts_align_soft_l_plan.h"   // level_counts_align_l_decide: the same at l = 2, 4 (rows of n l bits)
 #include "gswm_pool_plan.h"   // pool_decide: the same for pooling the images of a set and for the record walk over pooled rows
 #include "gswm_topk.h"
 
@@ -331,4 +332,6 @@ int gsw_trace_keyed_topk(const uint8_t* signs_dev, int B, int64_t n_bits, const 
 #include "gswm_align_soft.inc"   // gsw_level_rows_align: the same for a sign row and its level planes, one index walk for all of them
 #include "gswm_counts_align.inc" // gsw_counts_align: the vote counts of every candidate alignment under one key, the operand of an aligned registry search
 #include "gswm_counts_align_soft.inc" // gsw_level_counts_align: the same for gsw_level_pack's rows, the level-weighted vote of every alignment
+#include "gswm_align_soft_l.inc" // gsw_level_rows_align_l: gsw_level_rows_align for gsw_level_pack_l's rows (l = 2, 4), one index walk per element
+#include "gswm_counts_align_soft_l.inc" // gsw_level_counts_align_l: gsw_level_counts_align for those rows
 #include "gswm_pool.inc"         // gsw_pool_rows, gsw_trace_keyed_pooled_topk: the images of a set pooled into one row, and the record walk for its up to 10 planes

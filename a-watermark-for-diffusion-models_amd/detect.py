@@ -480,8 +480,8 @@ def _search_signs_aligned(packed, shape, l, keys_dev, mb, table, k):
 
 def _search_levels_aligned(packed, shape, l, keys_dev, mb, table, k):
     from . import align as AL
-    codec._level_rows_align_checks(packed, shape)
-    idx, aidx, stat = AL._search_level_rows(packed, shape, keys_dev, mb, table, k)
+    codec._level_rows_align_checks(packed, shape, l)
+    idx, aidx, stat = AL._search_level_rows(packed, shape, keys_dev, mb, table, k, l=l)
     return idx, stat, aidx
 
 
@@ -505,10 +505,14 @@ def _law_levels(packed, M, V, shape, table):
     lv = levels_from_planes(packed.planes.cpu().numpy())           # over the n l cipher bits, bit j on message position j mod M
     laws: Dict[Tuple[int, Optional[int]], _SoftNullLaw] = {}
 
+    def aligned(row, a):                                           # the l levels of an element travel with it: [C, H, W, l] -> l lattices -> back
+        cube = torch.from_numpy(row.reshape(tuple(shape) + (-1,))).movedim(-1, 0)
+        return AL.apply(cube, a).movedim(0, -1).reshape(-1).numpy()
+
     def bound(b: int, a: Optional[int], s: int) -> float:
         t = laws.get((b, a))
         if t is None:
-            row = lv[b] if a is None else AL.apply(torch.from_numpy(lv[b].reshape(shape)), table[a]).reshape(-1).numpy()
+            row = lv[b] if a is None else aligned(lv[b], table[a])
             t = laws[(b, a)] = _SoftNullLaw(row, M)
         return t.log10_bound(s)
 
@@ -524,7 +528,7 @@ _DECODERS = {  # (level-weighted, with alignments) -> (pack, search, read, law);
 
 
 def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int, levels: int, aligns):
-    """The one flow behind `detect_latents`, `detect_latents_soft_l` and `detect_latents_aligned_soft`, after the checks that are each entry's own: pack the
+    """The one flow behind `detect_latents`, `detect_latents_soft_l`, `detect_latents_aligned_soft` and `detect_latents_aligned_soft_l`, after the checks that are each entry's own: pack the
     images, search the keyring, read every image under its best key, bound every reported statistic, build the candidate lists
     -> (results, the best candidate's alignment index int [B] or None, the bytes voted under the best key uint8 [B, mb]).
 
@@ -532,8 +536,6 @@ def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int,
     (key, alignment) pair and the image is read with its best alignment applied.  `_DECODERS` holds the four steps of each combination."""
     import torch
     from . import align as AL
-    if levels and aligns is not None and l != 1:
-        raise ValueError(f"reliability levels cannot be combined with alignments at l = {l}: the level-weighted alignment search is defined for one cipher bit per element")
     pack, search, read, law = _DECODERS[(bool(levels), aligns is not None)]
     M = 8 * mb
     k = int(k)
@@ -591,13 +593,14 @@ def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int
     return _detect(latents, keyring, mb, k, limit, l=l, levels=levels, aligns=None)[0]
 
 
-def _aligned_soft(latents, keyring: Keyring, message_length: int, aligns, levels: int, k: int, fpr: float):
-    """`detect_latents_aligned_soft` -> (results, the best candidate's alignment index int [B], the bytes voted under it uint8 [B, msg_bytes])"""
+def _aligned_soft(latents, keyring: Keyring, message_length: int, aligns, levels: int, k: int, fpr: float, l: int = 1):
+    """`detect_latents_aligned_soft` and, with l = 2 or 4, `detect_latents_aligned_soft_l` -> (results, the best candidate's alignment index int [B], the bytes
+    voted under it uint8 [B, msg_bytes])"""
     limit, mb = _rate_and_bytes(fpr, message_length)
     levels = _reliability_levels(levels)
     if not levels:
         raise ValueError(f"levels must be in 1..{codec.SOFT_MAX_LEVELS}: a search without levels is detect_latents(align=...)")
-    return _detect(latents, keyring, mb, k, limit, l=1, levels=levels, aligns=aligns)
+    return _detect(latents, keyring, mb, k, limit, l=l, levels=levels, aligns=aligns)
 
 
 def detect_latents_aligned_soft(latents, keyring: Keyring, message_length: int, aligns, *, levels: int = 15, k: int = 1,
@@ -614,6 +617,20 @@ def detect_latents_aligned_soft(latents, keyring: Keyring, message_length: int, 
     the K A (key, alignment) pairs: under a key the image is independent of, the bits of any fixed permutation are fair coins independent of
     the levels, so the bound holds for every pair and the union bound needs nothing else."""
     return _aligned_soft(latents, keyring, message_length, aligns, levels, k, fpr)[0]
+
+
+def detect_latents_aligned_soft_l(latents, keyring: Keyring, message_length: int, aligns, l: int, *, levels: int = 15, k: int = 1,
+                                  fpr: float = 1e-6) -> List[DetectResult]:
+    """`detect_latents_aligned_soft` for multi-bit windows (l = 2 or 4): the alignment search with every one of the n l cipher bits
+    weighted by its level of `codec.extract_soft_l`.  latents [B, C, H, W] on the device, aligns from `align.alignments`.
+
+    `soft.window_thresholds` once on the un-aligned latents, one `codec.level_pack_l`, `align.search_keys_soft_l`'s search (per chunk of images one
+    `codec.level_rows_align_l` and the unchanged `codec.key_search_soft_topk` with n_bits = n l), and the message of the best key read by one
+    `codec.extract_soft_l` launch on the latents with their best alignment applied, under the SAME table.  The bound is `log10_p_blind_soft` given the n l levels
+    UNDER THAT ALIGNMENT -- the host permutes the levels it read from the planes in groups of l, as the kernel does -- then Bonferroni over the K A pairs.
+    n l (1 + P) may not exceed 1 048 576.  l = 1 is refused: that is `detect_latents_aligned_soft`."""
+    l = codec._multi_bit_window(l, "detect_latents_aligned_soft")
+    return _aligned_soft(latents, keyring, message_length, aligns, levels, k, fpr, l)[0]
 
 
 # ===================================================================================================================== front end
@@ -671,6 +688,10 @@ def build_parser():
                    help="with --l 2 or 4: rank the keys by level-weighted margins, every cipher bit of a lattice element votes with one of L (1..15) "
                         "levels taken from its distance to the quantiser boundaries that would flip it; the p-value is a Chernoff bound given the levels "
                         "(not with --align, --reliability or --align_reliability); 0: the sign statistic")
+    p.add_argument("--align_window_reliability", type=int, default=0, choices=range(0, 16), metavar="L",
+                   help="with --align and --l 2 or 4: rank every (key, alignment) pair by level-weighted margins, every cipher bit of a lattice element votes "
+                        "with one of L (1..15) levels taken from its distance to the quantiser boundaries that would flip it; the p-value is a Chernoff bound "
+                        "given the levels under the alignment (not with --reliability, --align_reliability or --window_reliability); 0: the sign statistic")
     p.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     p.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     p.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -696,6 +717,9 @@ def _detect_files(files, args, keyring) -> list:
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
+            if getattr(args, "align_window_reliability", 0):
+                return detect_latents_aligned_soft_l(latents, keyring, args.message_length, cands, args.l, levels=args.align_window_reliability, k=args.top,
+                                                     fpr=args.fpr)
             if getattr(args, "align_reliability", 0):
                 return detect_latents_aligned_soft(latents, keyring, args.message_length, cands, levels=args.align_reliability, k=args.top, fpr=args.fpr)
         if getattr(args, "window_reliability", 0):
@@ -721,6 +745,8 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
             fields += [("align_reliability", args.align_reliability)]
         if getattr(args, "window_reliability", 0):
             fields += [("window_reliability", args.window_reliability)]
+        if getattr(args, "align_window_reliability", 0):
+            fields += [("align_window_reliability", args.align_window_reliability)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
@@ -743,6 +769,13 @@ def main(argv=None):
         raise SystemExit("--align_reliability needs --align flips or --align d4 and --l 1, and cannot be combined with --reliability")
     if args.window_reliability and (args.l == 1 or args.align != "none" or args.reliability or args.align_reliability):
         raise SystemExit("--window_reliability needs --l 2 or --l 4 and cannot be combined with --align, --reliability or --align_reliability")
+    if args.align_window_reliability:
+        if args.align == "none":
+            raise SystemExit("--align_window_reliability needs --align flips or --align d4 (without alignments: --window_reliability)")
+        if args.l == 1:
+            raise SystemExit("--align_window_reliability needs --l 2 or --l 4: at --l 1 the level-weighted alignment search is --align_reliability")
+        if args.reliability or args.align_reliability or args.window_reliability:
+            raise SystemExit("--align_window_reliability cannot be combined with --reliability, --align_reliability or --window_reliability")
     keyring = load_keyring(args.keyring)
     keyring.packed()
     synthetic = X._no_checkpoint(args.model_id)

@@ -52,6 +52,10 @@ Through flips, quarter turns and lattice shifts (`trace_latents_aligned`, `trace
 over every (record, alignment) pair of `align.alignments` after one inversion and one quantisation.  Under one key `codec.counts_align` writes the vote counts
 of every alignment in one launch and `codec.trace_topk` ranks them; across keys `codec.rows_align` feeds `codec.trace_keyed_topk`.  For a fixed pair the null
 law is unchanged, the bound is Bonferroni over the U A pairs, and the tamper map is taken on the un-aligned latent.
+
+The aligned searches ranked by reliability levels: `trace_latents_aligned_soft`, `trace_latents_keyed_aligned_soft` (`--align_reliability LEVELS`, l = 1,
+DESIGN.md section 4.26) and, for multi-bit windows, `trace_latents_aligned_soft_l`, `trace_latents_keyed_aligned_soft_l` (`--align_window_reliability LEVELS
+--l 2|4`, section 4.28): `codec.level_counts_align[_l]` under one key, `codec.level_rows_align[_l]` + `codec.trace_keyed_soft_topk` across keys.
 """
 from __future__ import annotations
 
@@ -999,26 +1003,92 @@ def trace_latents_keyed_aligned(latents, registry: KeyedRegistry, aligns, *, k: 
 
 
 # ===================================================================================================================== the aligned searches ranked by reliability levels
-def _aligned_soft_table(z, levels, clip, thresholds):
+def _aligned_soft_table(z, levels, clip, thresholds, l: int = 1):
     """(levels, P, make) of an aligned level-weighted search: the number of levels and of planes, known before anything is launched, and make() -> the float32
-    table on z's device (`soft.uniform_thresholds` of the UN-aligned latents, or the given one)"""
+    table on z's device (`soft.uniform_thresholds` of the UN-aligned latents, at l = 2 and 4 `soft.window_thresholds`, or the given one)"""
     import torch
     from . import soft as S
     if thresholds is None:
         T, clip = S._check_table(levels, clip)
-        return T, codec.level_planes(T), lambda: S.uniform_thresholds(z, T, clip)
-    if not isinstance(thresholds, torch.Tensor) or thresholds.dim() not in (1, 2):
-        raise ValueError("thresholds must be float32 [levels] or [B, levels]")
+        return T, codec.level_planes(T), lambda: S._default_table(z, l, T, clip)
+    if l == 1:
+        if not isinstance(thresholds, torch.Tensor) or thresholds.dim() not in (1, 2):
+            raise ValueError("thresholds must be float32 [levels] or [B, levels]")
+    elif not isinstance(thresholds, torch.Tensor) or thresholds.dim() not in (2, 3) or thresholds.shape[-2] != l:
+        raise ValueError(f"thresholds must be float32 [{l}, levels] or [B, {l}, levels]")
     T = int(thresholds.shape[-1])
     return T, codec.level_planes(T), lambda: thresholds.to(device=z.device, dtype=torch.float32).contiguous()
 
 
-def _aligned_stack(z, pairs, thr):
+def _aligned_stack(z, pairs, thr, l: int = 1):
     """The aligned latents of (image, alignment) pairs and the threshold rows that go with them: the operands of one soft vote over the pairs"""
     import torch
     from . import align as AL
     zs = torch.stack([AL.apply(z[b], a) for b, a in pairs]).contiguous()
-    return zs, thr if thr.dim() == 1 else thr[torch.tensor([b for b, _ in pairs], device=z.device)].contiguous()
+    shared = thr.dim() == (1 if l == 1 else 2)           # one table for all images
+    return zs, thr if shared else thr[torch.tensor([b for b, _ in pairs], device=z.device)].contiguous()
+
+
+def _aligned_soft_domain(shape, l: int, P: int) -> None:
+    """The soft searches' domain for the rows of an aligned level-weighted search: n l (1 + P) bits of one image"""
+    if shape[0] * shape[1] * shape[2] * l * (1 + P) > codec.ROW_MAX_BITS:
+        at = "" if l == 1 else f" at l = {l}"
+        raise ValueError(f"a lattice of {shape}{at} with {P} level planes is beyond the search's domain: n{'' if l == 1 else ' l'} (1 + P) <= {codec.ROW_MAX_BITS}")
+
+
+def _trace_aligned_soft(what: str, latents, key: bytes, nonce: bytes, registry: Registry, aligns, l: int, levels: int, clip: float, thresholds,
+                        message_length: Optional[int], k: int, fpr: float, tamper_tile: Optional[int], budget_bytes: Optional[int]):
+    """`trace_latents_aligned_soft` (l = 1) and `trace_latents_aligned_soft_l` (l = 2, 4) after the check of l: one level packer, per chunk one launch of the
+    level-weighted counts of every alignment over the n l cipher bits and one registry search, the merge, the bounds and the read-back"""
+    import torch
+    from . import align as AL
+    from . import soft as S
+    limit = _log10_fpr(fpr)
+    codec._check_key_nonce(key, nonce)
+    z, shape = _aligned_lattice(latents, what)
+    cands = AL._as_list(aligns, *shape[1:])
+    M = registry.message_bits if message_length is None else int(message_length)
+    B = z.shape[0]
+    rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
+    V = codec.vote_copies(z.numel() // max(B, 1), M, l)
+    M = codec._counts_align_message(shape, l, M)
+    T, P, table_of = _aligned_soft_table(z, levels, clip, thresholds, l)
+    if 2 * T * V > 2000000 or M * 2 * T * V >= 2 ** 31:
+        raise ValueError(f"levels={T} with {V} copies of {M} message bits is beyond the registry search's limits "
+                         "(2 levels copies <= 2 000 000 and msg_bits 2 levels copies < 2^31)")
+    _aligned_soft_domain(shape, l, P)
+    bias = codec._level_counts_align_limits(shape, P, M, T * V, l)
+    reg_dev = registry.to_device(z.device, M)
+    thr = table_of()
+    lrows = codec.level_pack(z, thr) if l == 1 else codec.level_pack_l(z, thr, l)
+    codec._level_rows_align_checks(lrows, shape, l)
+    table = AL._device_table(cands, shape, z.device)
+
+    def search(rows_b, aligns_dev):
+        counts = codec._level_counts_align_launch(rows_b, shape, aligns_dev, key, nonce, M, bias, l=l)
+        idx, score = codec.trace_topk(counts.view(-1, M), 2 * T * V, reg_dev, k=int(k), soft=True)
+        return idx, torch.where(idx >= 0, score // 2, score)             # the search weighs 2 score[b, a, t]: every score is even
+
+    found = AL._search_chunks(B, 4 * M, table, reg_dev, k, budget_bytes, lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in lrows)), search,
+                              stat_bits=AL.SOFT_STAT_BITS)
+    U, A = len(registry), len(cands)
+    wsq_h = lrows.wsq.cpu().numpy()
+    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+
+    def candidate(b, i, s, a):
+        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U * A), a)
+        reported.append((b, c))
+        return c
+
+    out, best = _aligned_results(found, lrows.flags, cands, limit, candidate)
+    if reported:                                        # the soft vote of every reported pair on its aligned latent, one launch
+        zs, thr_rows = _aligned_stack(z, [(b, c.alignment) for b, c in reported], thr, l)
+        vote = S.extract_soft_l(zs, key, nonce, M, l, thresholds=thr_rows)                # (l = 1: `soft.extract_soft`, to which it delegates)
+        for (_, c), row in zip(reported, vote.bits.cpu().numpy()):
+            c.agree = M - int(np.unpackbits(row ^ rows[c.index]).sum())
+    if tamper_tile is not None:
+        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, lambda i: (key, nonce, bytes(rows[i]))), M, l, tamper_tile, fpr)
+    return out
 
 
 def trace_latents_aligned_soft(latents, key: bytes, nonce: bytes, registry: Registry, aligns, *, levels: int = 15, clip: float = 2.5, thresholds=None,
@@ -1038,37 +1108,57 @@ def trace_latents_aligned_soft(latents, key: bytes, nonce: bytes, registry: Regi
     keeps it); the reported bound is Bonferroni over the U A pairs.  A bound, not the exact tail of `trace_latents_aligned`.
     `Candidate.agree`: the soft vote's bits of the latent with that alignment applied, one `soft.extract_soft` launch over the reported (image, alignment)
     rows, each with its image's own threshold row.  tamper_tile: as in `trace_latents_aligned`, on the sign row of the un-aligned latent."""
+    return _trace_aligned_soft("trace_latents_aligned_soft", latents, key, nonce, registry, aligns, 1, levels, clip, thresholds, message_length, k, fpr,
+                               tamper_tile, budget_bytes)
+
+
+def trace_latents_aligned_soft_l(latents, key: bytes, nonce: bytes, registry: Registry, aligns, l: int, *, levels: int = 15, clip: float = 2.5,
+                                 thresholds=None, message_length: Optional[int] = None, k: int = 1, fpr: float = 1e-6, tamper_tile: Optional[int] = None,
+                                 budget_bytes: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_aligned_soft` for multi-bit windows (l = 2 or 4): the search runs over every (record, alignment) pair and every
+    one of the n l cipher bits votes with its level 0..levels of `codec.extract_soft_l`.  latents [B, C, H, W] on the device, aligns from `align.alignments`.
+
+    thresholds: float32 [l, levels] or [B, l, levels]; None: `soft.window_thresholds(latents, l, levels, clip)`, taken ONCE on the un-aligned latents (an
+    alignment permutes elements, and the l level bits of an element travel with it).  One `codec.level_pack_l`; then per chunk of images one
+    `codec.level_counts_align_l` launch with bias = levels V, V = n l / M, and one `codec.trace_topk(counts', 2 levels V)`; then `trace_latents_aligned`'s
+    merge.  The limits are `reliability_counts`', n l (1 + P) <= 1 048 576 and `codec.level_counts_align_l`'s LDS cap, all raised before any launch.
+    The bound is `trace_latents_aligned_soft`'s: Hoeffding's `soft.log10_p(score, wsq)` with the image's own wsq over its n l bits, Bonferroni over the U A
+    pairs.  `Candidate.agree`: the bits of `soft.extract_soft_l` on the latent with that alignment applied, one launch over the reported pairs.  tamper_tile: as
+    in `trace_latents_aligned` at that l.  l = 1 is refused: that is `trace_latents_aligned_soft`."""
+    l = codec._multi_bit_window(l, "trace_latents_aligned_soft")
+    return _trace_aligned_soft("trace_latents_aligned_soft_l", latents, key, nonce, registry, aligns, l, levels, clip, thresholds, message_length, k, fpr,
+                               tamper_tile, budget_bytes)
+
+
+def _trace_keyed_aligned_soft(what: str, latents, registry: KeyedRegistry, aligns, l: int, levels: int, clip: float, thresholds, k: int, fpr: float,
+                              tamper_tile: Optional[int], budget_bytes: Optional[int]):
+    """`trace_latents_keyed_aligned_soft` (l = 1) and `trace_latents_keyed_aligned_soft_l` (l = 2, 4) after the check of l: one level packer, per chunk one
+    launch of every alignment of the 1 + P rows of n l bits and one keyed soft search, the merge, the bounds and the read-back"""
     import torch
     from . import align as AL
     from . import soft as S
     limit = _log10_fpr(fpr)
-    codec._check_key_nonce(key, nonce)
-    z, shape = _aligned_lattice(latents, "trace_latents_aligned_soft")
+    z, shape = _aligned_lattice(latents, what)
     cands = AL._as_list(aligns, *shape[1:])
-    M = registry.message_bits if message_length is None else int(message_length)
     B = z.shape[0]
-    rows = registry.packed(M)                            # (a message_length the registry cannot be tiled to fails here)
-    V = codec.vote_copies(z.numel() // max(B, 1), M, 1)
-    M = codec._counts_align_message(shape, 1, M)
-    T, P, table_of = _aligned_soft_table(z, levels, clip, thresholds)
-    if 2 * T * V > 2000000 or M * 2 * T * V >= 2 ** 31:
-        raise ValueError(f"levels={T} with {V} copies of {M} message bits is beyond the registry search's limits "
-                         "(2 levels copies <= 2 000 000 and msg_bits 2 levels copies < 2^31)")
-    if shape[0] * shape[1] * shape[2] * (1 + P) > codec.ROW_MAX_BITS:
-        raise ValueError(f"a lattice of {shape} with {P} level planes is beyond the search's domain: n (1 + P) <= {codec.ROW_MAX_BITS}")
-    bias = codec._level_counts_align_limits(shape, P, M, T * V)
-    reg_dev = registry.to_device(z.device, M)
+    n = z.numel() // max(B, 1)
+    M, mb = registry.message_bits, registry.message_bytes
+    codec.vote_copies(n, M, l)                           # (a lattice the messages do not tile fails here, as extract_batch would)
+    T, P, table_of = _aligned_soft_table(z, levels, clip, thresholds, l)
+    _aligned_soft_domain(shape, l, P)
+    rec_dev = registry.to_device(z.device)
     thr = table_of()
-    lrows = codec.level_pack(z, thr)
-    codec._level_rows_align_checks(lrows, shape)
+    lrows = codec.level_pack(z, thr) if l == 1 else codec.level_pack_l(z, thr, l)
+    codec._level_rows_align_checks(lrows, shape, l)
     table = AL._device_table(cands, shape, z.device)
+    rowbytes = lrows.signs.shape[1]
 
     def search(rows_b, aligns_dev):
-        counts = codec._level_counts_align_launch(rows_b, shape, aligns_dev, key, nonce, M, bias)
-        idx, score = codec.trace_topk(counts.view(-1, M), 2 * T * V, reg_dev, k=int(k), soft=True)
-        return idx, torch.where(idx >= 0, score // 2, score)             # the search weighs 2 score[b, a, t]: every score is even
+        signs, planes = codec._level_rows_align_launch(rows_b, shape, aligns_dev, l)
+        al = codec.LevelRows(signs.view(-1, rowbytes), planes.view(-1, P, rowbytes), rows_b.wsum.repeat_interleave(aligns_dev.shape[0]), rows_b.wsq, rows_b.flags)
+        return codec.trace_keyed_soft_topk(al, n * l, rec_dev, mb, k=int(k))
 
-    found = AL._search_chunks(B, 4 * M, table, reg_dev, k, budget_bytes, lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in lrows)), search,
+    found = AL._search_chunks(B, (1 + P) * rowbytes, table, rec_dev, k, budget_bytes, lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in lrows)), search,
                               stat_bits=AL.SOFT_STAT_BITS)
     U, A = len(registry), len(cands)
     wsq_h = lrows.wsq.cpu().numpy()
@@ -1080,13 +1170,15 @@ def trace_latents_aligned_soft(latents, key: bytes, nonce: bytes, registry: Regi
         return c
 
     out, best = _aligned_results(found, lrows.flags, cands, limit, candidate)
-    if reported:                                        # the soft vote of every reported pair on its aligned latent, one launch
-        zs, thr_rows = _aligned_stack(z, [(b, c.alignment) for b, c in reported], thr)
-        vote = S.extract_soft(zs, key, nonce, M, thresholds=thr_rows)
-        for (_, c), row in zip(reported, vote.bits.cpu().numpy()):
-            c.agree = M - int(np.unpackbits(row ^ rows[c.index]).sum())
+    if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
+        zs, thr_rows = _aligned_stack(z, [(b, c.alignment) for b, c in reported], thr, l)
+        rec = torch.tensor([c.index for _, c in reported], device=z.device)
+        pairs_ = (zs, rec_dev[rec].contiguous(), mb, thr_rows)
+        vote = codec.extract_soft(*pairs_) if l == 1 else codec.extract_soft_l(*pairs_, l)
+        for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
+            c.agree = int(a)
     if tamper_tile is not None:
-        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, lambda i: (key, nonce, bytes(rows[i]))), M, 1, tamper_tile, fpr)
+        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, registry.record_at), M, l, tamper_tile, fpr)
     return out
 
 
@@ -1102,52 +1194,22 @@ def trace_latents_keyed_aligned_soft(latents, registry: KeyedRegistry, aligns, *
     rows; the bound is `log10_p_any(soft.log10_p(score, wsq), U A)`, Hoeffding's with the image's wsq for a fixed pair, Bonferroni over the pairs.
     `Candidate.agree` counts the bits of the soft vote of the aligned latent under the candidate's own record: one `codec.extract_soft` launch over the
     reported (image, candidate) pairs.  tamper_tile: as in `trace_latents_keyed_aligned`.  n (1 + P) may not exceed 1 048 576, P the bit length of `levels`."""
-    import torch
-    from . import align as AL
-    from . import soft as S
-    limit = _log10_fpr(fpr)
-    z, shape = _aligned_lattice(latents, "trace_latents_keyed_aligned_soft")
-    cands = AL._as_list(aligns, *shape[1:])
-    B = z.shape[0]
-    n = z.numel() // max(B, 1)
-    M, mb = registry.message_bits, registry.message_bytes
-    codec.vote_copies(n, M, 1)                           # (a lattice the messages do not tile fails here, as extract_batch would)
-    T, P, table_of = _aligned_soft_table(z, levels, clip, thresholds)
-    if n * (1 + P) > codec.ROW_MAX_BITS:
-        raise ValueError(f"a lattice of {shape} with {P} level planes is beyond the search's domain: n (1 + P) <= {codec.ROW_MAX_BITS}")
-    rec_dev = registry.to_device(z.device)
-    thr = table_of()
-    lrows = codec.level_pack(z, thr)
-    codec._level_rows_align_checks(lrows, shape)
-    table = AL._device_table(cands, shape, z.device)
-    rowbytes = lrows.signs.shape[1]
+    return _trace_keyed_aligned_soft("trace_latents_keyed_aligned_soft", latents, registry, aligns, 1, levels, clip, thresholds, k, fpr, tamper_tile, budget_bytes)
 
-    def search(rows_b, aligns_dev):
-        signs, planes = codec._level_rows_align_launch(rows_b, shape, aligns_dev)
-        al = codec.LevelRows(signs.view(-1, rowbytes), planes.view(-1, P, rowbytes), rows_b.wsum.repeat_interleave(aligns_dev.shape[0]), rows_b.wsq, rows_b.flags)
-        return codec.trace_keyed_soft_topk(al, n, rec_dev, mb, k=int(k))
 
-    found = AL._search_chunks(B, (1 + P) * rowbytes, table, rec_dev, k, budget_bytes, lambda b0, b1: codec.LevelRows(*(t[b0:b1] for t in lrows)), search,
-                              stat_bits=AL.SOFT_STAT_BITS)
-    U, A = len(registry), len(cands)
-    wsq_h = lrows.wsq.cpu().numpy()
-    reported: List[Tuple[int, Candidate]] = []          # (image, candidate), in order
+def trace_latents_keyed_aligned_soft_l(latents, registry: KeyedRegistry, aligns, l: int, *, levels: int = 15, clip: float = 2.5, thresholds=None, k: int = 1,
+                                       fpr: float = 1e-6, tamper_tile: Optional[int] = None,
+                                       budget_bytes: Optional[int] = None) -> List[Union[TraceResult, ValueError]]:
+    """`trace_latents_keyed_aligned_soft` for multi-bit windows (l = 2 or 4): `trace_latents_keyed_soft_l` over every (record,
+    alignment) pair.  latents [B, C, H, W] on the device, aligns from `align.alignments`.
 
-    def candidate(b, i, s, a):
-        c = Candidate(registry.user_at(i), i, s, 0, log10_p_any(S.log10_p(s, int(wsq_h[b])), U * A), a)
-        reported.append((b, c))
-        return c
-
-    out, best = _aligned_results(found, lrows.flags, cands, limit, candidate)
-    if reported:                                        # the soft vote of every reported pair under the candidate's own record, one launch
-        zs, thr_rows = _aligned_stack(z, [(b, c.alignment) for b, c in reported], thr)
-        rec = torch.tensor([c.index for _, c in reported], device=z.device)
-        vote = codec.extract_soft(zs, rec_dev[rec].contiguous(), mb, thr_rows)
-        for (_, c), a in zip(reported, vote.matches.cpu().tolist()):
-            c.agree = int(a)
-    if tamper_tile is not None:
-        _attach_aligned_tamper_maps(out, z, cands, best, _best_records(out, registry.record_at), M, 1, tamper_tile, fpr)
-    return out
+    thresholds as in `trace_latents_aligned_soft_l`.  One `codec.level_pack_l`; then per chunk of images one `codec.level_rows_align_l` launch and the unchanged
+    `codec.trace_keyed_soft_topk` on its [B A] rows with n_bits = n l; then `trace_latents_aligned`'s merge.  The bound is
+    `log10_p_any(soft.log10_p(score, wsq), U A)`.  `Candidate.agree`: one `codec.extract_soft_l` launch over the reported (image, candidate) pairs.
+    tamper_tile: as in `trace_latents_keyed_aligned` at that l.  n l (1 + P) may not exceed 1 048 576.  l = 1 is refused: that is
+    `trace_latents_keyed_aligned_soft`."""
+    l = codec._multi_bit_window(l, "trace_latents_keyed_aligned_soft")
+    return _trace_keyed_aligned_soft("trace_latents_keyed_aligned_soft_l", latents, registry, aligns, l, levels, clip, thresholds, k, fpr, tamper_tile, budget_bytes)
 
 
 # ===================================================================================================================== tracing a SET of images to one user
@@ -1377,6 +1439,17 @@ def build_parser():
                     self.error("--pool cannot be combined with --tamper_map: a tamper map belongs to one image")
                 if a.pool == "subdirs" and str(a.is_traverse_subdirectories) != "1":
                     self.error("--pool subdirs needs --is_traverse_subdirectories 1: its sets are the directories that traversal visits")
+            if a.align_window_reliability is not None:
+                if a.align == "none":
+                    self.error("--align_window_reliability requires --align flips or --align d4: it ranks the (record, alignment) pairs of an aligned search at "
+                               "--l 2 or 4 (without alignments: --window_reliability with --per_record_keys)")
+                if a.l == 1:
+                    self.error("--align_window_reliability needs --l 2 or --l 4: at --l 1 the level-weighted trace through alignments is --align_reliability")
+                if a.hard:
+                    self.error("--align_window_reliability cannot be combined with --hard: the level-weighted statistic ranks by weighted margins")
+                for name in ("reliability", "keyed_reliability", "window_reliability", "align_reliability", "pool"):
+                    if getattr(a, name) is not None:
+                        self.error(f"--align_window_reliability cannot be combined with --{name}")
             if a.align_reliability is not None:
                 if a.align == "none":
                     self.error("--align_reliability requires --align flips or --align d4: it ranks the (record, alignment) pairs of an aligned search "
@@ -1483,6 +1556,11 @@ def build_parser():
                    help="with --align flips or d4: rank the (record, alignment) pairs by level-weighted margins, LEVELS (1..15) reliability levels per lattice "
                         "element, the p-value is a Hoeffding bound over the pairs (with or without --per_record_keys; --l 1, not with --hard, --reliability, "
                         "--keyed_reliability or --window_reliability)")
+    p.add_argument("--align_window_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
+                   help="with --align flips or d4 and --l 2 or 4: rank the (record, alignment) pairs by level-weighted margins, every cipher bit of a lattice "
+                        "element votes with one of LEVELS (1..15) levels taken from its distance to the quantiser boundaries that would flip it, the p-value "
+                        "is a Hoeffding bound over the pairs (with or without --per_record_keys, with --tamper_map; not with --hard, --reliability, "
+                        "--keyed_reliability, --window_reliability, --align_reliability or --pool)")
     p.add_argument("--pool", default=None, choices=("all", "subdirs"),
                    help="after the per-image lines, trace SETS of images by pooled evidence, one line per set: all (every traced image is one set) or subdirs "
                         "(one set per directory; needs --is_traverse_subdirectories 1).  The sets are chosen before looking at scores; at most 1023 images per "
@@ -1519,6 +1597,12 @@ def _trace_files(files: Sequence[str], args, registry, trace_batch=None, store=N
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
+            wlevels = getattr(args, "align_window_reliability", None)
+            if wlevels is not None and args.per_record_keys:
+                return trace_latents_keyed_aligned_soft_l(latents, registry, cands, args.l, levels=wlevels, k=args.top, fpr=args.fpr, tamper_tile=tile)
+            if wlevels is not None:
+                return trace_latents_aligned_soft_l(latents, args.key, args.nonce, registry, cands, args.l, levels=wlevels, message_length=args.message_length,
+                                                    k=args.top, fpr=args.fpr, tamper_tile=tile)
             levels = getattr(args, "align_reliability", None)
             if levels is not None and args.per_record_keys:
                 return trace_latents_keyed_aligned_soft(latents, registry, cands, levels=levels, k=args.top, fpr=args.fpr, tamper_tile=tile)
@@ -1576,6 +1660,8 @@ def _statistic_name(args) -> str:
     levels = args.reliability if args.reliability is not None else getattr(args, "keyed_reliability", None)
     if levels is None and getattr(args, "align_reliability", None) is not None:
         return f"soft, {args.align_reliability} reliability levels over {_alignment_count(args)} alignments"
+    if levels is None and getattr(args, "align_window_reliability", None) is not None:
+        return f"soft, {args.align_window_reliability} reliability levels per window bit over {_alignment_count(args)} alignments"
     if levels is None and getattr(args, "window_reliability", None) is not None:
         return f"soft, {args.window_reliability} reliability levels per window bit"
     return "hard" if args.hard else "soft" if levels is None else f"soft, {levels} reliability levels"

@@ -868,6 +868,32 @@ int gsw_level_counts_align(const uint8_t* signs_dev, const uint8_t* planes_dev, 
                            const uint8_t key[32], const uint8_t nonce16[16], int msg_bits, int bias, int32_t* score_dev, int32_t* wsum_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------------------
+ * Reliability levels through the alignment searches at l = 2, 4: gsw_level_rows_align and gsw_level_counts_align
+ * for gsw_level_pack_l's rows.  Element e of the [C, H, W] lattice owns bits [e l, e l + l), MSB first, of the quantised row and of every
+ * level plane; an alignment moves the l-bit group of an element in all 1 + P rows after ONE computation of where the element comes from.
+ * Additive: gsw_version() stays 500.
+ *
+ *   signs_dev, planes_dev : gsw_level_pack_l's row uint8 [B, n l / 8] and plane rows uint8 [B, P, n l / 8], n = C H W (any alignment); P in 1 .. 4
+ *   l           : 1, 2 or 4.  At l = 1 both entry points write byte for byte what gsw_level_rows_align / gsw_level_counts_align write
+ *   aligns_dev  : int32 [A, 3] rows (d, dy, dx), 4-byte aligned, as gsw_rows_align
+ * gsw_level_rows_align_l: out_signs_dev uint8 [B, A, n l / 8], out_planes_dev uint8 [B, A, P, n l / 8] (any alignment); row (b, a) of each is
+ * bit for bit gsw_rows_align's row at that l.  Viewed as [B A, ...] they are the operands of gsw_key_search_soft_topk and
+ * gsw_trace_keyed_soft_topk with n_bits = n l.  Staged in LDS while the 1 + P padded rows total at most 65 536 bytes, else read in place.
+ * GSW_ERR_BAD_ARG: null pointer, aligns_dev not 4-byte aligned, l outside {1, 2, 4}, P outside 1..4, B, C, H, W or A < 1.
+ * GSW_ERR_UNSUPPORTED: n l (1 + P) > 1 048 576, B > 65535.  GSW_ERR_RAGGED: n l is not a multiple of 8.
+ * gsw_level_counts_align_l: key, nonce16, bias, score_dev, wsum_dev as gsw_level_counts_align, over the n l cipher positions p:
+ *                 score[b, a, t] = bias + sum over p = t (mod M) of level_p (2 d_p - 1),  wsum[b, a, t] = sum over p = t (mod M) of level_p
+ *                 bit for bit gsw_extract_soft_l's score (plus bias) and wsum of that transform of image b's latent under the table the rows were packed with
+ * GSW_ERR_BAD_ARG: as gsw_level_counts_align, and l outside {1, 2, 4}.  GSW_ERR_RAGGED: n l is not a multiple of 8 or of msg_bits.
+ * GSW_ERR_UNSUPPORTED: n l (1 + P) > 1 048 576, B > 65535, the staged regions beyond 128 KiB, |bias| + 15 n l / msg_bits beyond int32.  In that
+ * order.  An entry without a map (d outside 0..7, or an odd d when H != W) writes zero rows, or `bias` and zeros.  Every output byte is
+ * written, no atomics, no workspace, integer arithmetic only; every refusal happens before any launch. */
+int gsw_level_rows_align_l(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int l, int B, int C, int H, int W, const int32_t* aligns_dev, int A,
+                           uint8_t* out_signs_dev, uint8_t* out_planes_dev, void* stream);
+int gsw_level_counts_align_l(const uint8_t* signs_dev, const uint8_t* planes_dev, int P, int l, int B, int C, int H, int W, const int32_t* aligns_dev, int A,
+                             const uint8_t key[32], const uint8_t nonce16[16], int msg_bits, int bias, int32_t* score_dev, int32_t* wsum_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------
  * Robust decode in one launch, tile weights times reliability levels: the rounds of the tile-weighted vote
  * (gsw_vote_tiled, gsw_tile_agree and the weight rule between them) with every cipher bit voting at its reliability level.
  * Additive: gsw_version() stays 500.
