@@ -10,11 +10,12 @@ through the `gswm_amd` loader module at the repo root:
     from gswm_amd import soft                         # the soft-decision vote: every element weighted by its reliability level
     from gswm_amd import detect                       # a keyring instead of a registry: which key is this image under, and what does it say
     from gswm_amd import align                        # the same through flips, quarter turns and lattice shifts of the image
+    from gswm_amd import ecc                          # error-corrected payloads: a convolutional code under the votes, read by one Viterbi launch
 """
 from . import _native  # noqa: F401
 from . import codec  # noqa: F401
 
-__all__ = ["codec", "gs_insert", "extract", "comfy", "ddim", "dist", "distortions", "trace", "tamper", "soft", "detect", "align"]
+__all__ = ["codec", "gs_insert", "extract", "comfy", "ddim", "dist", "distortions", "trace", "tamper", "soft", "detect", "align", "ecc"]
 
 
 def __getattr__(name):  # lazy sub-modules (keep `import gswm_amd` light)

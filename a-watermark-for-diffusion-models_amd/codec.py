@@ -932,6 +932,50 @@ def trace_keyed_pooled_topk(rows: PooledRows, n_bits: int, records: torch.Tensor
     return idx, score
 
 
+# ------------------------------------------------------------------------------------------------ error-corrected payloads: the Viterbi read of the votes
+VITERBI_MIN_BITS, VITERBI_MAX_BITS = 64, 8192   # message bits of a coded message (csrc/gswm_viterbi_plan.h)
+
+
+class ViterbiDecode(NamedTuple):
+    """What `viterbi_decode` returns, all on score's device"""
+    info: torch.Tensor      # uint8 [B, M / 16], the I = M / 2 - 6 info bits MSB first: payload, CRC-16, 2 pad bits (the rest of the last byte is zero)
+    message: torch.Tensor   # uint8 [B, M / 8], the re-encoded, re-interleaved codeword: the corrected message
+    metric: torch.Tensor    # int32 [B], the winning path's correlation
+    flips: torch.Tensor     # int32 [B], positions where the corrected message disagrees with score > 0
+    ok: torch.Tensor        # int32 [B], 1: the CRC matches and the pad bits are zero
+
+
+def viterbi_decode(score: torch.Tensor) -> ViterbiDecode:
+    """Decode the soft votes of B images under the rate-1/2, constraint-length-7 convolutional code of `ecc.encode`, in one launch
+    (gsw_viterbi_decode, one wavefront per image): the maximum-correlation codeword for every row.
+
+    score: int32 [B, M] on a HIP device, positive = bit 1 (`SoftVote.score`, `RobustVote.score`, 2 counts - copies); rows may be strided (a column
+    slice of a wider tensor), elements may not; M a multiple of 16 in 64..8192 (ValueError); sum_t |score[b, t]| < 2**30 is the caller's bound,
+    which every vote of this library keeps.  Integer arithmetic: the results equal tests/ecc_reference.py bit for bit."""
+    if not isinstance(score, torch.Tensor) or score.dim() != 2 or score.dtype != torch.int32:
+        raise ValueError("score must be an int32 tensor [B, message bits]")
+    B, M = score.shape
+    if M % 16 or not VITERBI_MIN_BITS <= M <= VITERBI_MAX_BITS:
+        raise ValueError(f"score holds {M} message bits: a coded message has a multiple of 16 bits in {VITERBI_MIN_BITS}..{VITERBI_MAX_BITS}")
+    if B < 1:
+        raise ValueError("score holds no image")
+    if not score.is_cuda:
+        raise RuntimeError(f"score must live on a HIP device (got {score.device}); the watermark hot path has no CPU fallback")
+    if score.stride(1) != 1 or (B > 1 and score.stride(0) < M):
+        raise ValueError("score must have unit stride along the message and rows that do not overlap")
+    if score.data_ptr() % 4:
+        raise ValueError("score must be 4-byte aligned")
+    stride = score.stride(0) if B > 1 else M
+    dev = score.device
+    out = ViterbiDecode(torch.empty((B, M // 16), dtype=torch.uint8, device=dev), torch.empty((B, M // 8), dtype=torch.uint8, device=dev),
+                        torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
+                        torch.empty((B,), dtype=torch.int32, device=dev))
+    with torch.cuda.device(dev):
+        N.check(N.lib().gsw_viterbi_decode(score.data_ptr(), stride, B, M, out.info.data_ptr(), out.message.data_ptr(), out.metric.data_ptr(),
+                                           out.flips.data_ptr(), out.ok.data_ptr(), _stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ blind key search ranked by reliability levels
 def key_search_soft_topk(rows: LevelRows, n_bits: int, keys: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """`key_search_topk` ranked by reliability levels: (idx int32 [B, k], stat int32 [B, k]), best first, ties towards the lower row; past

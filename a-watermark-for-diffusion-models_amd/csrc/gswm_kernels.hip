@@ -1668,3 +1668,9 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
 // Soft-decision vote for multi-bit windows (l = 2, 4; a level per cipher bit): gsw_extract_soft_l / gsw_level_pack_l, kernels and entry points
 // ------------------------------------------------------------------------------------------------
 #include "gswm_codec_soft_l.inc"
+
+// ------------------------------------------------------------------------------------------------
+// Error-corrected payloads (rate-1/2, K = 7 convolutional code under the votes): gsw_viterbi_decode, kernel and entry point
+// ------------------------------------------------------------------------------------------------
+#include "gswm_viterbi_plan.h"
+#include "gswm_viterbi.inc"

@@ -493,6 +493,15 @@ def _read_levels(z, rows, mb, l, thr):
     return (codec.extract_soft(z, rows, mb, thr) if l == 1 else codec.extract_soft_l(z, rows, mb, thr, l)).bits
 
 
+def _read_scored(z, rows, mb, l, thr):
+    """the read of `_read_signs` (thr None) or `_read_levels`, with the votes it was taken from -> (bits, score int32 [B, 8 mb]): what `detect_payloads` decodes"""
+    if thr is None:
+        bits, _, _, counts = codec.extract_records(z, rows, mb, l=l, return_counts=True)
+        return bits, 2 * counts - codec.vote_copies(z.numel() // z.shape[0], 8 * mb, l)
+    vote = codec.extract_soft(z, rows, mb, thr) if l == 1 else codec.extract_soft_l(z, rows, mb, thr, l)
+    return vote.bits, vote.score
+
+
 def _law_signs(packed, M, V, shape, table):
     return lambda b, a, s: log10_p_blind(s, M, V)                  # exact, and the same under every alignment: a permutation keeps the copies per position
 
@@ -527,13 +536,14 @@ _DECODERS = {  # (level-weighted, with alignments) -> (pack, search, read, law);
 }
 
 
-def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int, levels: int, aligns):
+def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int, levels: int, aligns, scores: bool = False):
     """The one flow behind `detect_latents`, `detect_latents_soft_l`, `detect_latents_aligned_soft` and `detect_latents_aligned_soft_l`, after the checks that are each entry's own: pack the
     images, search the keyring, read every image under its best key, bound every reported statistic, build the candidate lists
     -> (results, the best candidate's alignment index int [B] or None, the bytes voted under the best key uint8 [B, mb]).
 
     levels: 0 -- the sign statistic; 1..15 -- the level-weighted statistic.  aligns: None, or the candidate alignments: the search then runs over every
-    (key, alignment) pair and the image is read with its best alignment applied.  `_DECODERS` holds the four steps of each combination."""
+    (key, alignment) pair and the image is read with its best alignment applied.  `_DECODERS` holds the four steps of each combination.
+    scores: also return, as a fourth entry, the votes the read was taken from (int32 [B, 8 mb] on the device; `detect_payloads`)."""
     import torch
     from . import align as AL
     pack, search, read, law = _DECODERS[(bool(levels), aligns is not None)]
@@ -553,7 +563,12 @@ def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int,
     idx, stat, aidx = search(packed, shape, l, keys_dev, mb, table, k)
     rows = torch.zeros((B, codec.keyed_record_stride(mb)), dtype=torch.uint8, device=z.device)
     rows[:, :codec.KEYED_RECORD_HEAD] = keys_dev[idx[:, 0].long()]      # every image under its own best key, a zero message: `matches` is not read
-    if aidx is None:
+    score = None
+    if aidx is None and scores:
+        bits, score = _read_scored(z, rows, mb, l, thr)
+        idx_h, stat_h = T._pairs_to_host(idx, stat)
+        aidx_h = None
+    elif aidx is None:
         bits = read(z, rows, mb, l, thr)
         idx_h, stat_h = T._pairs_to_host(idx, stat)
         aidx_h = None
@@ -572,7 +587,8 @@ def _detect(latents, keyring: Keyring, mb: int, k: int, limit: float, *, l: int,
                              lambda b, c, named: DetectResult(c, c[0].key_id if named else None, bits_h[b].tobytes() if named else None, int(flags_h[b]),
                                                               c[0].alignment if named else None),
                              refuse=False)
-    return out, None if aidx_h is None else aidx_h[:, 0], bits_h
+    best = None if aidx_h is None else aidx_h[:, 0]
+    return (out, best, bits_h, score) if scores else (out, best, bits_h)
 
 
 def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int, *, levels: int = 15, k: int = 1, fpr: float = 1e-6) -> List[DetectResult]:
@@ -591,6 +607,42 @@ def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int
     if not levels:
         raise ValueError(f"levels must be a number of levels in 1..{codec.SOFT_MAX_LEVELS}, got 0")
     return _detect(latents, keyring, mb, k, limit, l=l, levels=levels, aligns=None)[0]
+
+
+def detect_payloads(latents, keyring: Keyring, message_length: int, *, ecc: str = "conv", k: int = 1, fpr: float = 1e-6, l: int = 1, reliability: int = 0,
+                    window_reliability: int = 0):
+    """Blind detection of images whose messages are error-corrected payloads (`ecc.encode`) -> (results, reads):
+    `results` is what `detect_latents` (sign statistic, or `reliability=L` at l = 1) or `detect_latents_soft_l` (`window_reliability=L` at l = 2, 4)
+    returns, unchanged -- `DetectResult.message` stays the majority-voted CODED message -- and reads[b] is the `ecc.EccRead` of image b (one entry in each
+    of its lists) when a key is named, else None.  The votes of every image under its own best key -- the read's score, or 2 counts - copies of the sign
+    read -- go through ONE `codec.viterbi_decode` launch for the whole batch.  Alignments are not wired yet: `ecc` with `align` is the next step."""
+    from . import ecc as E
+    if E.check_code(ecc) is None:
+        raise ValueError('detect_payloads needs ecc="conv": without a code this is detect_latents')
+    limit, mb = _rate_and_bytes(fpr, message_length)
+    E.check_length(8 * mb)
+    l = codec.check_window(l)
+    reliability, window_reliability = _reliability_levels(reliability), _reliability_levels(window_reliability)
+    if reliability and window_reliability:
+        raise ValueError("reliability (l = 1) and window_reliability (l = 2, 4) cannot be combined")
+    if reliability and l != 1:
+        raise ValueError(f"reliability cannot be combined with l = {l}: at l = 2 and 4 the levels are window_reliability")
+    if window_reliability and l == 1:
+        raise ValueError("window_reliability needs l = 2 or 4: at l = 1 the levels are reliability")
+    results, _, _, score = _detect(latents, keyring, mb, k, limit, l=l, levels=reliability or window_reliability, aligns=None, scores=True)
+    read = E.read(score.contiguous())
+    return results, [read.image(b) if r.key_id is not None else None for b, r in enumerate(results)]
+
+
+class _PayloadOutcome:
+    """what the command line carries per image with --ecc: the unchanged DetectResult and the text appended to its line"""
+
+    def __init__(self, result: DetectResult, text: str):
+        self.result, self.text = result, text
+
+
+def _line(name: str, r) -> str:
+    return format_line(name, r.result) + r.text if isinstance(r, _PayloadOutcome) else format_line(name, r)
 
 
 def _aligned_soft(latents, keyring: Keyring, message_length: int, aligns, levels: int, k: int, fpr: float, l: int = 1):
@@ -701,7 +753,23 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=16, help="images per device batch")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
+    p.add_argument("--ecc", default=None, choices=("conv",),
+                   help="the messages are error-corrected payloads (issue --ecc conv): for a named key the votes are decoded by one Viterbi launch per batch and "
+                        "the line gains 'payload <hex> crc ok|FAILED, corrected <flips> of <M>' (with the sign statistic, --reliability or "
+                        "--window_reliability; not with --align, --align_shift, --align_reliability or --align_window_reliability yet)")
     return p
+
+
+def ecc_refusal(args) -> Optional[str]:
+    """--ecc next to an alignment flag: refused by name (the decode composes with the alignment search; wiring it is not part of this step)"""
+    if getattr(args, "ecc", None) is None:
+        return None
+    for flag, on in (("--align", getattr(args, "align", "none") != "none"), ("--align_shift", bool(getattr(args, "align_shift", 0))),
+                     ("--align_reliability", bool(getattr(args, "align_reliability", 0))),
+                     ("--align_window_reliability", bool(getattr(args, "align_window_reliability", 0)))):
+        if on:
+            return f"--ecc cannot be combined with {flag} yet: the payload read is not wired through the alignment search"
+    return None
 
 
 def load_keyring(path) -> Keyring:
@@ -714,6 +782,11 @@ def _detect_files(files, args, keyring) -> list:
     module's search in place of the registry search"""
     def batch(latents):
         cands = None
+        if getattr(args, "ecc", None) is not None:
+            from . import ecc as E
+            results, reads = detect_payloads(latents, keyring, args.message_length, ecc=args.ecc, k=args.top, fpr=args.fpr, l=args.l,
+                                             reliability=getattr(args, "reliability", 0), window_reliability=getattr(args, "window_reliability", 0))
+            return [_PayloadOutcome(r, "" if e is None else ", " + E.format_read(e, 0, int(args.message_length))) for r, e in zip(results, reads)]
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
@@ -747,11 +820,13 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
             fields += [("window_reliability", args.window_reliability)]
         if getattr(args, "align_window_reliability", 0):
             fields += [("align_window_reliability", args.align_window_reliability)]
+        if getattr(args, "ecc", None) is not None:
+            fields += [("ecc", args.ecc)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")
         for f, r in zip(job.files, outcomes):
-            line = format_line(f if isinstance(r, Exception) else os.path.basename(f), r)
+            line = _line(f if isinstance(r, Exception) else os.path.basename(f), r)
             print(line)
             out.write(line + "\n")
         out.write(bar + "Batch End" + bar + "\n")
@@ -761,6 +836,11 @@ def main(argv=None):
     args = build_parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     from . import extract as X
     _message_bytes(args.message_length)                            # fails before any model loads
+    if ecc_refusal(args):
+        raise SystemExit(ecc_refusal(args))
+    if args.ecc is not None:
+        from . import ecc as E
+        E.check_length(args.message_length)
     if args.align_shift < 0 or (args.align == "none" and args.align_shift):
         raise SystemExit("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
     if args.reliability and (args.l != 1 or args.align != "none"):
@@ -795,7 +875,7 @@ def main(argv=None):
                 X.load_models(args.model_id, allow_synthetic=X._synthetic_allowed(args))
                 print(f"{X.SYNTHETIC_MARKER}: '{args.model_id}' is not a local checkpoint, the detection below is not meaningful", file=sys.stderr)
             r = _detect_files([args.single_image_path], args, keyring)[0]
-            print(format_line(args.single_image_path if isinstance(r, Exception) else os.path.basename(args.single_image_path), r))
+            print(_line(args.single_image_path if isinstance(r, Exception) else os.path.basename(args.single_image_path), r))
         else:
             print("Please set the argument 'images_directory_path' or 'single_image_path'")
 

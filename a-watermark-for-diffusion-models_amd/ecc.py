@@ -1,0 +1,127 @@
+"""Error-corrected payloads: the M-bit message is a codeword of the rate-1/2, constraint-length-7 convolutional code (generators
+0o171, 0o133, zero tail) over payload | CRC-16/CCITT-FALSE | pad, its code bits spread over the message by a multiplicative interleaver.  `encode` runs on
+the host (a few hundred bit operations); `read` decodes the soft votes of a batch in one launch (`codec.viterbi_decode`, gsw_viterbi_decode) -- there is no
+CPU decoder here.  The coded message is a message like any other: embed, registries, trace and the searches take it as it is."""
+from __future__ import annotations
+
+import math
+from typing import List, NamedTuple
+
+import numpy as np
+import torch
+
+from . import codec
+
+G0, G1 = 0o171, 0o133
+TAIL = 6
+MIN_LENGTH, MAX_LENGTH = 64, 8192
+CODES = ("conv",)
+
+
+def check_code(ecc):
+    """`ecc=` / `--ecc`: None or "conv" """
+    if ecc is not None and ecc not in CODES:
+        raise ValueError(f"ecc must be None or one of {CODES}, got {ecc!r}")
+    return ecc
+
+
+def check_length(message_length) -> int:
+    M = message_length
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M % 16 or not MIN_LENGTH <= M <= MAX_LENGTH:
+        raise ValueError(f"ecc: message_length must be a multiple of 16 in {MIN_LENGTH}..{MAX_LENGTH}, got {M!r}")
+    return int(M)
+
+
+def info_bits(message_length) -> int:
+    return check_length(message_length) // 2 - TAIL
+
+
+def capacity(message_length) -> int:
+    """payload bytes a message of `message_length` bits carries: (I - 16) // 8 with I = M / 2 - 6 (13 at M = 256)"""
+    return (info_bits(message_length) - 16) // 8
+
+
+def interleaver_step(message_length) -> int:
+    """S: code bit i sits at message position (i S) mod M -- the smallest odd integer >= (isqrt(M) | 1) coprime to M"""
+    M = check_length(message_length)
+    S = math.isqrt(M) | 1
+    while math.gcd(S, M) != 1:
+        S += 2
+    return S
+
+
+def crc16(data: bytes) -> int:
+    """CRC-16/CCITT-FALSE: polynomial 0x1021, init 0xFFFF, no reflection, no final xor"""
+    crc = 0xFFFF
+    for byte in bytes(data):
+        crc ^= byte << 8
+        for _ in range(8):
+            crc = ((crc << 1) ^ 0x1021) & 0xFFFF if crc & 0x8000 else (crc << 1) & 0xFFFF
+    return crc
+
+
+def check_payload(payload, message_length) -> bytes:
+    if not isinstance(payload, (bytes, bytearray)):
+        raise ValueError(f"ecc: a payload is bytes, got {type(payload).__name__}")
+    cap = capacity(message_length)
+    if len(payload) != cap:
+        raise ValueError(f"ecc: a payload of {len(payload)} bytes; a message of {message_length} bits carries exactly {cap}")
+    return bytes(payload)
+
+
+def encode(payload: bytes, message_length: int) -> bytes:
+    """payload (exactly `capacity(message_length)` bytes) -> the coded message of message_length / 8 bytes"""
+    payload = check_payload(payload, message_length)
+    M, I = int(message_length), info_bits(message_length)
+    c = crc16(payload)
+    word = np.unpackbits(np.frombuffer(payload + bytes([c >> 8, c & 0xFF]), dtype=np.uint8))
+    u = np.concatenate([word, np.zeros(I - word.size + TAIL, dtype=np.uint8)])
+    S, s = interleaver_step(M), 0
+    msg = np.zeros(M, dtype=np.uint8)
+    for t, bit in enumerate(u.tolist()):
+        r = (bit << 6) | s
+        msg[(2 * t) * S % M] = bin(r & G0).count("1") & 1
+        msg[(2 * t + 1) * S % M] = bin(r & G1).count("1") & 1
+        s = r >> 1
+    return np.packbits(msg).tobytes()
+
+
+def pad_payload(payload, message_length: int) -> bytes:
+    """the CLI's convenience: text or bytes, cut or zero-padded to the capacity (as `codec.pad_message` does for messages; nothing random)"""
+    raw = payload.encode() if isinstance(payload, str) else bytes(payload)
+    cap = capacity(message_length)
+    return raw[:cap] + b"\0" * max(0, cap - len(raw))
+
+
+class EccRead(NamedTuple):
+    """What `read` returns for a batch of B images"""
+    payload: List[bytes]     # B payloads of `capacity(M)` bytes
+    ok: List[bool]           # the CRC matches and the pad bits are zero
+    flips: List[int]         # positions where the corrected message disagrees with score > 0
+    metric: List[int]        # the winning path's correlation
+    message: torch.Tensor    # uint8 [B, M / 8] on score's device: the corrected message, for `bit_matches` and the registries
+
+    def image(self, b: int) -> "EccRead":
+        return EccRead([self.payload[b]], [self.ok[b]], [self.flips[b]], [self.metric[b]], self.message[b:b + 1])
+
+
+def read(score: torch.Tensor) -> EccRead:
+    """Decode soft votes score int32 [B, M] (positive = bit 1: `SoftVote.score`, `RobustVote.score`, or 2 counts - copies of
+    `extract_batch(..., return_counts=True)`) in one launch; one device-to-host copy brings the small results over."""
+    d = codec.viterbi_decode(score)
+    M = score.shape[1]
+    pb = capacity(M)
+    info = d.info.cpu().numpy()
+    small = torch.stack([d.ok, d.flips, d.metric]).cpu().numpy()
+    return EccRead([info[b, :pb].tobytes() for b in range(info.shape[0])], [bool(v) for v in small[0]], [int(v) for v in small[1]], [int(v) for v in small[2]],
+                   d.message)
+
+
+def score_from_counts(counts: torch.Tensor, copies: int) -> torch.Tensor:
+    """the plain vote as a score: 2 counts - copies (int32 [B, M])"""
+    return (2 * counts.to(torch.int32) - int(copies)).contiguous()
+
+
+def format_read(r: EccRead, b: int, message_length: int) -> str:
+    """the text the command-line tools append for image b"""
+    return f"payload {r.payload[b].hex()} crc {'ok' if r.ok[b] else 'FAILED'}, corrected {r.flips[b]} of {message_length}"

@@ -130,30 +130,77 @@ def _alignment_note(r) -> str:
     return f", alignment: {AL.describe(r.alignment)}, log10 p, {r.log10_p:.3f}" if isinstance(r, _AlignedBits) else ""
 
 
+class _EccBits(str):
+    """A recovered bit string (the vote's, as without --ecc) that also carries the payload read of the same votes (--ecc conv)"""
+    note = ""
+
+
+def _ecc_wanted(args):
+    """--ecc as None or "conv"; next to --align, --align_shift or several GPUs it is refused by name, and the message length must be a coded one"""
+    code = getattr(args, "ecc", None)
+    if code is None:
+        return None
+    from . import ecc as E
+    E.check_code(code)
+    for flag, on in (("--align", getattr(args, "align", None) not in (None, "none")), ("--align_shift", bool(int(getattr(args, "align_shift", 0) or 0)))):
+        if on:
+            raise ValueError(f"--ecc cannot be combined with {flag} yet: the payload read is not wired through the alignment search")
+    if int(getattr(args, "gpus", 1) or 1) > 1:
+        raise ValueError("--ecc cannot be combined with --gpus above 1 yet: the payload read runs on one GPU")
+    E.check_length(int(args.message_length))
+    return code
+
+
+def _ecc_note(r) -> str:
+    """what --ecc adds after an image's line"""
+    return f"\n{r.note}" if isinstance(r, _EccBits) and r.note else ""
+
+
+def _with_payloads(strings, score, m: int):
+    """the bit strings of a batch (or the exceptions raised for them) -> the same, every string carrying its payload read: ONE `ecc.read` launch"""
+    from . import ecc as E
+    read = E.read(score.contiguous())
+    out = []
+    for b, s in enumerate(strings):
+        if not isinstance(s, Exception):
+            s = _EccBits(s)
+            s.note = E.format_read(read, b, m)
+        out.append(s)
+    return out
+
+
 def _vote(z, args, m: int, l: int):
-    """(bits, flags) of the reference's vote, with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations), with
+    return _vote_scored(z, args, m, l, False)[:2]
+
+
+def _vote_scored(z, args, m: int, l: int, want_score: bool = True):
+    """(bits, flags, score) of the reference's vote, with --robust 1 of the tile-weighted vote (tamper.extract_robust, its default iterations), with
     --soft 1 of the level-weighted vote (soft.extract_soft, thresholds scaled to each image's RMS), with --window_soft L at --l 2 / 4 of the
     vote with a level per cipher bit (soft.extract_soft_l, soft.window_thresholds), with --robust_soft L of the robust decode with levels
-    (tamper.extract_robust_soft: --tile, --iters, --sign_rounds, at any --l)"""
+    (tamper.extract_robust_soft: --tile, --iters, --sign_rounds, at any --l).  score: the int32 [B, m] votes the bits are the signs of (the plain vote's
+    2 counts - copies, asked for with want_score only: without it the launch is the one it always was)"""
     robust_levels = _robust_soft_wanted(args)
     if robust_levels:
         from . import tamper
         res = tamper.extract_robust_soft(z, args.key, args.nonce, m, l=l, tile=int(getattr(args, "tile", 8)), iters=int(getattr(args, "iters", 2)),
                                          levels=robust_levels, clip=float(getattr(args, "soft_clip", 2.5)), sign_rounds=int(getattr(args, "sign_rounds", 1)))
-        return res.bits, res.flags
+        return res.bits, res.flags, res.score
     window_levels = _window_soft_wanted(args, l)
     if window_levels:
         from . import soft
         res = soft.extract_soft_l(z, args.key, args.nonce, m, l, levels=window_levels, clip=float(getattr(args, "soft_clip", 2.5)))
-        return res.bits, res.flags
+        return res.bits, res.flags, res.score
     if _soft_wanted(args, l):
         from . import soft
         res = soft.extract_soft(z, args.key, args.nonce, m, levels=int(getattr(args, "soft_levels", 15)), clip=float(getattr(args, "soft_clip", 2.5)))
-        return res.bits, res.flags
+        return res.bits, res.flags, res.score
     if int(getattr(args, "robust", 0) or 0):
         from . import tamper
-        return tamper.extract_robust(z, args.key, args.nonce, m, l=l, tile=int(getattr(args, "tile", 8)))[:2]
-    return codec.extract_batch(z, args.key, args.nonce, m, l=l)
+        return tamper.extract_robust(z, args.key, args.nonce, m, l=l, tile=int(getattr(args, "tile", 8)))[:3]
+    if not want_score:
+        return codec.extract_batch(z, args.key, args.nonce, m, l=l) + (None,)
+    bits, flags, counts = codec.extract_batch(z, args.key, args.nonce, m, return_counts=True, l=l)
+    return bits, flags, 2 * counts - codec.vote_copies(z.numel() // z.shape[0], m, l)
 
 
 def write_tamper_maps(latents, files, args) -> None:
@@ -177,6 +224,7 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     z = _to_device_latents(reversed_latents, device)
     m = int(args.message_length)
     robust_soft = _robust_soft_wanted(args)
+    code = _ecc_wanted(args)
     if _align_wanted(args):                                  # the alignments act on the lattice: the search needs the image's [C, h, w]
         shape = tuple(int(d) for d in np.shape(reversed_latents))
         if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
@@ -190,13 +238,14 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
         if len(shape) < 3 or int(np.prod(shape[-3:])) != z.numel():
             raise ValueError(f"{'--robust_soft' if robust_soft else '--robust 1'} needs the latents of ONE image as [..., C, h, w] (got {shape})")
         z = z.view(1, *shape[-3:])
-    bits, flags = _vote(z, args, m, l)
+    bits, flags, score = _vote_scored(z, args, m, l, code is not None)
     f = int(flags[0].item())
     if f & N.GSW_FLAG_NAN:
         raise ValueError("cannot convert float NaN to integer")
     if f & N.GSW_FLAG_SATURATED:
         raise ValueError("invalid literal for int() with base 2")
-    return codec.bits_to_str(bits[0].cpu().numpy())[:m]
+    text = codec.bits_to_str(bits[0].cpu().numpy())[:m]
+    return text if code is None else _with_payloads([text], score[:1], m)[0]
 
 
 def recover_exactracted_message_batch(latents: torch.Tensor, args):
@@ -205,9 +254,10 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
     l = _window(args)
     m = int(args.message_length)
     _robust_soft_wanted(args)
+    code = _ecc_wanted(args)
     if _align_wanted(args):
         return _vote_aligned(latents.contiguous(), args, m, l)
-    bits, flags = _vote(latents.contiguous(), args, m, l)
+    bits, flags, score = _vote_scored(latents.contiguous(), args, m, l, code is not None)
     bits_h, flags_h = bits.cpu().numpy(), flags.cpu().numpy()
     out = []
     for b in range(bits_h.shape[0]):
@@ -217,7 +267,7 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
             out.append(ValueError("invalid literal for int() with base 2"))
         else:
             out.append(codec.bits_to_str(bits_h[b])[:m])
-    return out
+    return out if code is None else _with_payloads(out, score, m)
 
 
 def calculate_bit_accuracy(original_message_hex, extracted_message_bin):
@@ -474,7 +524,7 @@ def get_result_for_one_image(args):
     extracted_message_bin = recover_exactracted_message(reversed_latents, args)
     original_message_bin, bit_accuracy = calculate_bit_accuracy(args.original_message_hex, extracted_message_bin)
     print(f"{os.path.basename(args.single_image_path)}\nOriginal Message: {original_message_bin} \nExtracted Message: {extracted_message_bin}\n"
-          f"Bit Accuracy: {bit_accuracy}{_alignment_note(extracted_message_bin)}\n")
+          f"Bit Accuracy: {bit_accuracy}{_alignment_note(extracted_message_bin)}{_ecc_note(extracted_message_bin)}\n")
     return original_message_bin, extracted_message_bin, bit_accuracy
 
 
@@ -608,8 +658,10 @@ def _report(job, args, synthetic):
                 continue
             original_message_bin, bit_accuracy = calculate_bit_accuracy(args.original_message_hex, r)
             name = os.path.basename(f)
-            print(f"{name}\nOriginal Message: {original_message_bin} \nExtracted Message: {r}\nBit Accuracy: {bit_accuracy}{_alignment_note(r)}\n")
+            print(f"{name}\nOriginal Message: {original_message_bin} \nExtracted Message: {r}\nBit Accuracy: {bit_accuracy}{_alignment_note(r)}{_ecc_note(r)}\n")
             out.write(f"{name}, Bit Accuracy, {bit_accuracy}{_alignment_note(r)}\n")
+            if _ecc_note(r):
+                out.write(f"{name}, {r.note}\n")
             accs.append(float(bit_accuracy))
         if accs:
             mean = sum(accs) / len(accs)
@@ -723,6 +775,21 @@ def build_parser():
                 self.error("--align cannot be combined with --soft 1, --robust 1 or --tamper_map: the alignment search reads the reference's vote")
             if a.align_shift < 0 or (a.align == "none" and a.align_shift):
                 self.error("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
+            if a.ecc is not None:
+                try:
+                    _ecc_wanted(a)
+                except ValueError as e:
+                    self.error(str(e))
+            if a.original_payload_hex is not None:
+                if a.ecc is None or a.original_message_hex is not None:
+                    self.error("--original_payload_hex needs --ecc conv and takes the place of --original_message_hex: give one of the two")
+                from . import ecc as E
+                try:
+                    a.original_message_hex = E.encode(bytes.fromhex(a.original_payload_hex), int(a.message_length)).hex()
+                except ValueError as e:
+                    self.error(f"--original_payload_hex: {e}")
+            if a.original_message_hex is None:
+                self.error("the following arguments are required: --original_message_hex")
             return a
 
     parser = Parser(description="Extract watermark from a image")
@@ -731,7 +798,8 @@ def build_parser():
     parser.add_argument("--single_image_path", default="")
     parser.add_argument("--key_hex", required=True, help="Hexadecimal key used for encryption")
     parser.add_argument("--nonce_hex", required=True, help="Hexadecimal nonce used for encryption, It will use the fixed part of the key if nonce is none")
-    parser.add_argument("--original_message_hex", required=True, help="Hexadecimal representation of the original message for accuracy calculation")
+    parser.add_argument("--original_message_hex", default=None, help="Hexadecimal representation of the original message for accuracy calculation (required; "
+                                                                      "with --ecc conv it stays the CODED message, or give --original_payload_hex)")
     parser.add_argument("--num_inference_steps", default=30, type=int, help="Number of inference steps for the model")
     parser.add_argument("--scheduler", default="DDIM", help="Choose a scheduler between 'DPMs' and 'DDIM' to inverse the image")
     parser.add_argument("--is_traverse_subdirectories", default=0, help="Whether to traverse subdirectories recursively")
@@ -778,6 +846,12 @@ def build_parser():
                         help="(not a reference flag) read the message under the best alignment of the lattice (align.extract_aligned): flips = half turn and "
                              "the two mirrors, d4 = all eight orientations; none: the reference's vote as it is")
     parser.add_argument("--align_shift", type=int, default=0, metavar="R", help="(not a reference flag) with --align: also every lattice shift in [-R, R]^2")
+    parser.add_argument("--ecc", default=None, choices=("conv",),
+                        help="(not a reference flag) the message is an error-corrected payload (issue --ecc conv): the votes of whichever decoder is chosen "
+                             "(plain, --soft 1, --window_soft L, --robust 1, --robust_soft L) are decoded by one Viterbi launch per batch, and after the "
+                             "existing line comes 'payload <hex> crc ok|FAILED, corrected <flips> of <M>'.  Not with --align, --align_shift or --gpus above 1 yet")
+    parser.add_argument("--original_payload_hex", default=None,
+                        help="(not a reference flag) with --ecc conv, in the place of --original_message_hex: the payload, encoded to the coded message first")
     return parser
 
 

@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import codec
+from . import codec, ecc as _ecc
 from .trace import KeyedRegistry, _check_user_id
 
 Record = Tuple[bytes, bytes, bytes]         # key[32], nonce[16], message
@@ -104,6 +104,28 @@ def resolve_requests(requests: Sequence[Request], registry: Optional[KeyedRegist
     return out
 
 
+def encode_requests(requests: Sequence[Request], message_bytes: int, ecc: Optional[str]) -> List[Request]:
+    """With ecc="conv" the requests' messages are PAYLOADS: every request comes back with its payload encoded to the `message_bytes`-byte coded message
+    (`ecc.encode`), which is what the registry, the log and the embed launch then see.  bytes must have exactly `ecc.capacity(8 message_bytes)` bytes, a
+    str at most that many once encoded (zero-padded); anything else raises here, before anything runs.  ecc=None: the requests as they are."""
+    if _ecc.check_code(ecc) is None:
+        return list(requests)
+    M = 8 * int(message_bytes)
+    cap = _ecc.capacity(M)
+    out = []
+    for r in requests:
+        if not isinstance(r, Request):
+            raise TypeError(f"expected issue.Request, got {type(r).__name__}")
+        raw = r.message.encode() if isinstance(r.message, str) else r.message
+        if len(raw) > cap or (len(raw) != cap and not isinstance(r.message, str)):
+            raise ValueError(f"user {r.user_id!r}: payload has {len(raw)} bytes, {message_bytes}-byte coded messages carry "
+                             f"{'at most' if isinstance(r.message, str) else 'exactly'} {cap}")
+        q = Request.__new__(Request)
+        q.user_id, q.key, q.nonce, q.message = r.user_id, r.key, r.nonce, _ecc.encode(raw + b"\0" * (cap - len(raw)), M)
+        out.append(q)
+    return out
+
+
 def pack_records(records: Sequence[Record], message_bytes: int) -> np.ndarray:
     """uint8 [B, stride] rows key | nonce | message, zero-padded to a multiple of 16 bytes: `KeyedRegistry.packed`'s row format"""
     t = np.zeros((len(records), codec.keyed_record_stride(message_bytes)), dtype=np.uint8)
@@ -120,18 +142,20 @@ def write_log(log_path, records: Sequence[Record]) -> None:
 
 
 def issue_latents(requests: Sequence[Request], shape: Sequence[int] = (4, 64, 64), *, registry: Optional[KeyedRegistry] = None, log_path=None,
-                  seed: Optional[int] = None, image_index0: int = 0, dtype=None, fast: bool = False, l: int = 1, device="cuda"):
+                  seed: Optional[int] = None, image_index0: int = 0, dtype=None, fast: bool = False, l: int = 1, device="cuda", ecc: Optional[str] = None):
     """Watermarked initial latents [B, *shape] for B requests, image b under request b's own record, after ONE embed launch:
     (latents, records) with records the uint8 [B, stride] device rows the launch read (`codec.extract_records` verifies against them).
 
     seed=None: the B * n uniforms come from NumPy's global MT19937, generated on the device (`codec.mt19937_uniform`): row b is what
     the b-th of B reference calls in a row would get, as `gs_watermark_init_noise_batch`; seed=int: in-kernel Philox by global image
     index image_index0 + b.  registry: every record is added under its user id BEFORE the launch (a clash raises before anything
-    runs or changes); log_path: one info_data.txt block per image is appended.  Without a registry 32-byte messages are issued."""
+    runs or changes); log_path: one info_data.txt block per image is appended.  Without a registry 32-byte messages are issued.
+    ecc="conv": the requests' messages are payloads (`encode_requests`); registry rows, log blocks and `records` hold the CODED message."""
     import torch
     l = codec.check_window(l)
-    records = resolve_requests(requests, registry)
     mb = registry.message_bytes if registry is not None else 32
+    requests = encode_requests(requests, mb, ecc)
+    records = resolve_requests(requests, registry)
     n = 1
     for s in shape:
         n *= int(s)
@@ -191,6 +215,8 @@ def build_parser():
     p.add_argument("--seed", type=int, default=None, help="in-kernel Philox stream of this seed (default: NumPy's global MT19937, as the reference draws)")
     p.add_argument("--dtype", default="float32", choices=_DTYPES)
     p.add_argument("--fast", action="store_true", help="fp32 inverse-CDF core (|dz| <= 1e-5)")
+    p.add_argument("--ecc", default=None, choices=_ecc.CODES, help="the requests' messages are payloads of ecc.capacity(8 message_bytes) bytes (13 in a 32-byte "
+                                                                   "message): the registry and the latents carry their convolutional codeword")
     return p
 
 
@@ -210,6 +236,7 @@ def main(argv=None):
         raise ValueError("--height and --width must be positive multiples of 8")
     requests = read_requests(args.requests)
     registry = KeyedRegistry.load(args.registry) if os.path.exists(args.registry) and os.path.getsize(args.registry) else KeyedRegistry(args.message_bytes)
+    requests = encode_requests(requests, registry.message_bytes, args.ecc)      # payloads -> coded messages, before anything else
     resolve_requests(requests, registry)                    # clashes and lengths: before the device is touched or a file written
     import torch
     latents, _ = issue_latents(requests, (4, args.height // 8, args.width // 8), registry=registry, log_path=args.info_data, seed=args.seed,

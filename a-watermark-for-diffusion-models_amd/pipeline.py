@@ -71,7 +71,7 @@ class GaussianShadingPipeline:
     # X2 + X3-X5 + X6 against each image's own record
     def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False, soft: bool = False,
                        levels: int = 15, clip: float = 2.5, window_levels: Optional[int] = None, robust_levels: Optional[int] = None, tile: int = 8,
-                       iters: int = 2, sign_rounds: int = 1):
+                       iters: int = 2, sign_rounds: int = 1, ecc: Optional[str] = None):
         """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`.
         soft=True: the `codec.SoftVote` (bits, flags, matches, score, wsum, wsq) of `codec.extract_soft` instead, every element weighted by
         one of `levels` reliability levels with thresholds scaled to its image's RMS (`soft.uniform_thresholds(z, levels, clip)`); l = 1 only.
@@ -79,7 +79,19 @@ class GaussianShadingPipeline:
         levels (`soft.window_thresholds(z, l, L, clip)`); not with soft=True, and not at l = 1 (that is soft=True).
         robust_levels=L in 1..15, at the pipeline's l: the `RobustRecordsVote` of the one-launch robust decode (`codec.level_pack[_l]` with the
         default table of L levels for this l, then `codec.decode_robust` under each record's own key with `tile`, `iters` and `sign_rounds`;
-        matches from `codec.bit_matches` against each record's message); not with soft=True or window_levels."""
+        matches from `codec.bit_matches` against each record's message); not with soft=True or window_levels.
+        ecc="conv": the records' messages are coded payloads (`issue_latents(..., ecc="conv")`); the votes of whichever decoder was chosen go through one
+        `codec.viterbi_decode` launch and the result is (what is returned without ecc, `ecc.EccRead`) -- with return_latents (that, EccRead, z)."""
+        from . import ecc as E
+        if E.check_code(ecc) is not None:
+            E.check_length(8 * int(msg_bytes))
+
+        def finish(res, z, score):
+            if ecc is None:
+                return (*res, z) if return_latents else res
+            read = E.read(score.contiguous())
+            return (res, read, z) if return_latents else (res, read)
+
         if robust_levels is not None:
             if soft:
                 raise ValueError("robust_levels cannot be combined with soft=True: the robust decode weights by levels AND tiles, in a launch of its own")
@@ -94,7 +106,7 @@ class GaussianShadingPipeline:
             B, _, msg_bytes = codec._records_operand(records, msg_bytes)
             z = ddim_invert(self.eps_model, x0, self._uncond(x0.shape[0]), self.schedule)
             res = self._robust_records(z, records, B, msg_bytes, robust_levels, clip, tile, iters, sign_rounds)
-            return (*res, z) if return_latents else res
+            return finish(res, z, res.score)
         if soft and self.l != 1:
             raise ValueError(f"soft=True cannot be combined with l = {self.l}: reliability levels are defined for one cipher bit per element")
         if window_levels is not None:
@@ -110,9 +122,12 @@ class GaussianShadingPipeline:
         elif soft:
             from . import soft as S
             res = codec.extract_soft(z, records, msg_bytes, S.uniform_thresholds(z, levels, clip))
+        elif ecc is not None:
+            *res, counts = codec.extract_records(z, records, msg_bytes, l=self.l, return_counts=True)
+            return finish(tuple(res), z, 2 * counts - codec.vote_copies(z.numel() // z.shape[0], 8 * int(msg_bytes), self.l))
         else:
             res = codec.extract_records(z, records, msg_bytes, l=self.l)
-        return (*res, z) if return_latents else res
+        return finish(res, z, res.score if ecc is not None else None)
 
     def _robust_records(self, z: torch.Tensor, records: torch.Tensor, B: int, msg_bytes: int, levels: int, clip: float, tile: int, iters: int,
                         sign_rounds: int) -> RobustRecordsVote:

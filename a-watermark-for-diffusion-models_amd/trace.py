@@ -1424,6 +1424,13 @@ def build_parser():
     class Parser(argparse.ArgumentParser):
         def parse_args(self, args=None, namespace=None):
             a = super().parse_args(args, namespace)
+            if a.ecc is not None:                                   # the registries hold CODED messages and are searched as they are: the payload read is extract's and detect's
+                if a.pool is not None:
+                    self.error("--ecc cannot be combined with --pool yet: the payload read is not wired through pooled sets")
+                if a.align != "none":
+                    self.error("--ecc cannot be combined with --align yet: the payload read is not wired through the alignment search")
+                self.error("--ecc is not a trace flag: registry rows hold the coded message and are matched unchanged; read payloads with extract --ecc conv "
+                           "or detect --ecc conv")
             if a.pool_reliability is not None:
                 if a.pool is None:
                     self.error("--pool_reliability requires --pool all or --pool subdirs: it sets the reliability levels of the rows a pooled trace adds up")
@@ -1568,6 +1575,9 @@ def build_parser():
     p.add_argument("--pool_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
                    help="with --pool: pool rows of LEVELS (1..15) reliability levels per lattice element instead of unit levels; a set then holds at most "
                         "1023 // (2^P - 1) images, P the bit length of LEVELS (68 at 15) (--l 1)")
+    p.add_argument("--ecc", default=None, choices=("conv",),
+                   help="refused by name: messages issued with --ecc conv are registered CODED and traced unchanged; with --pool or --align the payload read is "
+                        "not wired yet (extract --ecc conv and detect --ecc conv read payloads)")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
     return p

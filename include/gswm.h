@@ -958,6 +958,30 @@ int gsw_trace_keyed_pooled_topk(const uint8_t* signs_dev, const uint8_t* planes_
                                 const uint8_t* records_dev, int64_t record_stride, int msg_bytes, int64_t n_records, int k, int32_t* idx_dev,
                                 int32_t* score_dev, void* workspace_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Error-corrected payloads: the message of message_bits = M bits is a codeword of the rate-1/2, constraint-length-7
+ * convolutional code (generators 0o171, 0o133; state = the last 6 inputs, the newest at bit 5, starting at 0; 6 zero tail bits), so T = M / 2
+ * trellis steps carry I = T - 6 info bits: payload (M / 16 - 3 bytes, bits MSB first), CRC-16/CCITT-FALSE of the payload (0x1021, init 0xFFFF,
+ * no reflection, no final xor), 2 zero pad bits.  Code bit i sits at message position (i S) mod M, S the smallest odd integer >= (isqrt(M) | 1)
+ * coprime to M.  Additive: gsw_version() stays 500.
+ *
+ * gsw_viterbi_decode, one launch per batch, one wavefront per image: the maximum-correlation path through the trellis for the votes
+ *   score_dev   : int32 [B, score_stride] (4-byte aligned, score_stride >= M elements), positive = bit 1: gsw_extract_soft[_l]'s or
+ *                 gsw_decode_robust's score, or 2 counts - copies; sum_t |score[b, t]| < 2^30 (every vote of this library stays below 15 x 2^20)
+ * The branch from state 2 (s & 31) + d into state s (input s >> 5) adds (2 c0 - 1) x[2t] + (2 c1 - 1) x[2t + 1], x the de-interleaved row; only
+ * state 0 is reachable before step 0, an unreachable predecessor never wins, the 6 tail steps have u = 0 branches only, on equal metrics the
+ * predecessor with the lower index wins, the traceback starts from state 0.  Outputs, every element written for every image:
+ *   info_dev    : uint8 [B, M / 16], the I info bits MSB first (the last byte: the 2 pad bits, then zeros)
+ *   message_dev : uint8 [B, M / 8], the re-encoded, re-interleaved codeword: the corrected message
+ *   metric_dev  : int32 [B], the winning path's correlation = sum_p (2 message_p - 1) score[p]
+ *   flips_dev   : int32 [B], positions p with message_p != (score[p] > 0)
+ *   ok_dev      : int32 [B], 1 when the CRC of the payload bytes matches and the last info byte is zero, else 0
+ * Integer arithmetic only, no atomics, no workspace.
+ * GSW_ERR_BAD_ARG: null or misaligned pointer, B < 1, M < 64 or not a multiple of 16, score_stride < M.  GSW_ERR_UNSUPPORTED: M > 8192.
+ * In that order; every refusal happens before any launch. */
+int gsw_viterbi_decode(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, uint8_t* info_dev, uint8_t* message_dev, int32_t* metric_dev,
+                       int32_t* flips_dev, int32_t* ok_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
