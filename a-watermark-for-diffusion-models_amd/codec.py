@@ -976,6 +976,64 @@ def viterbi_decode(score: torch.Tensor) -> ViterbiDecode:
     return out
 
 
+VITERBI_LIST_SIZES = (1, 2, 4, 8)
+VITERBI_LIST_LDS = 160 * 1024                   # one wavefront's LDS slice may take the LDS of a compute unit (csrc/gswm_viterbi_list_plan.h)
+
+
+def viterbi_list_wave_lds(message_bits: int, list_size: int) -> int:
+    """bytes of LDS one image's list decode needs: M (5 + 1/16 + 9 L / 2) + 256 L, rounded up to 16"""
+    M, L = int(message_bits), int(list_size)
+    return (4 * M + 256 * L + 4 * M * L + M * L // 2 + M + M // 16 + 15) // 16 * 16
+
+
+class ViterbiListDecode(NamedTuple):
+    """What `viterbi_list_decode` returns, all on score's device; the first five describe the SELECTED path as `ViterbiDecode` describes its single path"""
+    info: torch.Tensor      # uint8 [B, M / 16]
+    message: torch.Tensor   # uint8 [B, M / 8]
+    metric: torch.Tensor    # int32 [B]
+    flips: torch.Tensor     # int32 [B]
+    ok: torch.Tensor        # int32 [B]
+    rank: torch.Tensor      # int32 [B], the selected rank: the lowest one whose CRC holds, 0 when none does
+    n_ok: torch.Tensor      # int32 [B], the number of the L ranks whose CRC holds
+
+
+def viterbi_list_decode(score: torch.Tensor, list_size: int) -> ViterbiListDecode:
+    """`viterbi_decode` with a list: every trellis state keeps its `list_size` = L best paths (L in 1, 2, 4, 8), and of the L paths that end in state 0
+    the best-ranked one whose CRC holds is returned -- rank 0, the plain decode, when none does.  One launch (gsw_viterbi_list_decode, one wavefront
+    per image); at L = 1 the first five tensors equal `viterbi_decode`'s.  DESIGN.md section 4.30 has the merge order and its tie rule.
+
+    score: as `viterbi_decode`.  M a multiple of 16 from 64 up, as large as `viterbi_list_wave_lds(M, L)` <= 163 840 allows: 17 104, 11 600, 7 056,
+    3 936 bits at L = 1, 2, 4, 8 (ValueError beyond).  Integer arithmetic: the results equal tests/ecc_list_reference.py bit for bit."""
+    if isinstance(list_size, bool) or not isinstance(list_size, int) or list_size not in VITERBI_LIST_SIZES:
+        raise ValueError(f"list_size must be one of {VITERBI_LIST_SIZES}, got {list_size!r}")
+    if not isinstance(score, torch.Tensor) or score.dim() != 2 or score.dtype != torch.int32:
+        raise ValueError("score must be an int32 tensor [B, message bits]")
+    B, M = score.shape
+    if M % 16 or M < VITERBI_MIN_BITS:
+        raise ValueError(f"score holds {M} message bits: a coded message has a multiple of 16 bits, {VITERBI_MIN_BITS} at least")
+    if viterbi_list_wave_lds(M, list_size) > VITERBI_LIST_LDS:
+        raise ValueError(f"score holds {M} message bits: at list_size {list_size} one image's survivor records need {viterbi_list_wave_lds(M, list_size)} "
+                         f"bytes of LDS, more than the {VITERBI_LIST_LDS} of a compute unit")
+    if B < 1:
+        raise ValueError("score holds no image")
+    if not score.is_cuda:
+        raise RuntimeError(f"score must live on a HIP device (got {score.device}); the watermark hot path has no CPU fallback")
+    if score.stride(1) != 1 or (B > 1 and score.stride(0) < M):
+        raise ValueError("score must have unit stride along the message and rows that do not overlap")
+    if score.data_ptr() % 4:
+        raise ValueError("score must be 4-byte aligned")
+    stride = score.stride(0) if B > 1 else M
+    dev = score.device
+    i32 = lambda: torch.empty((B,), dtype=torch.int32, device=dev)
+    out = ViterbiListDecode(torch.empty((B, M // 16), dtype=torch.uint8, device=dev), torch.empty((B, M // 8), dtype=torch.uint8, device=dev),
+                            i32(), i32(), i32(), i32(), i32())
+    with torch.cuda.device(dev):
+        N.check(N.lib().gsw_viterbi_list_decode(score.data_ptr(), stride, B, M, list_size, out.info.data_ptr(), out.message.data_ptr(),
+                                                out.metric.data_ptr(), out.flips.data_ptr(), out.ok.data_ptr(), out.rank.data_ptr(),
+                                                out.n_ok.data_ptr(), _stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ blind key search ranked by reliability levels
 def key_search_soft_topk(rows: LevelRows, n_bits: int, keys: torch.Tensor, msg_bytes: int, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """`key_search_topk` ranked by reliability levels: (idx int32 [B, k], stat int32 [B, k]), best first, ties towards the lower row; past

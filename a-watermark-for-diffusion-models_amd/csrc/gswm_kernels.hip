@@ -1674,3 +1674,9 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
 // ------------------------------------------------------------------------------------------------
 #include "gswm_viterbi_plan.h"
 #include "gswm_viterbi.inc"
+
+// ------------------------------------------------------------------------------------------------
+// The list read of error-corrected payloads (L best paths per state, the CRC picks among them): gsw_viterbi_list_decode, kernel and entry point
+// ------------------------------------------------------------------------------------------------
+#include "gswm_viterbi_list_plan.h"
+#include "gswm_viterbi_list.inc"

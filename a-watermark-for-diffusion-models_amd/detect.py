@@ -610,15 +610,18 @@ def detect_latents_soft_l(latents, keyring: Keyring, message_length: int, l: int
 
 
 def detect_payloads(latents, keyring: Keyring, message_length: int, *, ecc: str = "conv", k: int = 1, fpr: float = 1e-6, l: int = 1, reliability: int = 0,
-                    window_reliability: int = 0):
+                    window_reliability: int = 0, list_size: int = 1):
     """Blind detection of images whose messages are error-corrected payloads (`ecc.encode`) -> (results, reads):
     `results` is what `detect_latents` (sign statistic, or `reliability=L` at l = 1) or `detect_latents_soft_l` (`window_reliability=L` at l = 2, 4)
     returns, unchanged -- `DetectResult.message` stays the majority-voted CODED message -- and reads[b] is the `ecc.EccRead` of image b (one entry in each
     of its lists) when a key is named, else None.  The votes of every image under its own best key -- the read's score, or 2 counts - copies of the sign
-    read -- go through ONE `codec.viterbi_decode` launch for the whole batch.  Alignments are not wired yet: `ecc` with `align` is the next step."""
+    read -- go through ONE `codec.viterbi_decode` launch for the whole batch.  Alignments are not wired yet: `ecc` with `align` is the next step.
+    list_size = 2, 4 or 8: the list read (DESIGN.md section 4.30) -- the launch is `codec.viterbi_list_decode`'s and reads[b] an `ecc.EccListRead`;
+    list_size = 1 is today's launch and today's `EccRead`."""
     from . import ecc as E
     if E.check_code(ecc) is None:
         raise ValueError('detect_payloads needs ecc="conv": without a code this is detect_latents')
+    list_size = E.check_list_size(list_size)
     limit, mb = _rate_and_bytes(fpr, message_length)
     E.check_length(8 * mb)
     l = codec.check_window(l)
@@ -630,7 +633,7 @@ def detect_payloads(latents, keyring: Keyring, message_length: int, *, ecc: str 
     if window_reliability and l == 1:
         raise ValueError("window_reliability needs l = 2 or 4: at l = 1 the levels are reliability")
     results, _, _, score = _detect(latents, keyring, mb, k, limit, l=l, levels=reliability or window_reliability, aligns=None, scores=True)
-    read = E.read(score.contiguous())
+    read = E.read_any(score.contiguous(), list_size)
     return results, [read.image(b) if r.key_id is not None else None for b, r in enumerate(results)]
 
 
@@ -757,12 +760,18 @@ def build_parser():
                    help="the messages are error-corrected payloads (issue --ecc conv): for a named key the votes are decoded by one Viterbi launch per batch and "
                         "the line gains 'payload <hex> crc ok|FAILED, corrected <flips> of <M>' (with the sign statistic, --reliability or "
                         "--window_reliability; not with --align, --align_shift, --align_reliability or --align_window_reliability yet)")
+    p.add_argument("--ecc_list", type=int, default=1, choices=(1, 2, 4, 8),
+                   help="with --ecc conv: the list read -- the decoder keeps this many best paths and the CRC picks among them; the line gains "
+                        "', list rank <r> of <L>[, <n> candidates pass]'.  1 (default): the plain read and today's text.  Nothing issued changes; a false "
+                        "'crc ok' on an unmarked image becomes at most L times as likely (L 2^-18 at 256 bits)")
     return p
 
 
 def ecc_refusal(args) -> Optional[str]:
     """--ecc next to an alignment flag: refused by name (the decode composes with the alignment search; wiring it is not part of this step)"""
     if getattr(args, "ecc", None) is None:
+        if int(getattr(args, "ecc_list", 1) or 1) > 1:
+            return "--ecc_list above 1 needs --ecc conv: the list read is a read of error-corrected payloads"
         return None
     for flag, on in (("--align", getattr(args, "align", "none") != "none"), ("--align_shift", bool(getattr(args, "align_shift", 0))),
                      ("--align_reliability", bool(getattr(args, "align_reliability", 0))),
@@ -785,8 +794,10 @@ def _detect_files(files, args, keyring) -> list:
         if getattr(args, "ecc", None) is not None:
             from . import ecc as E
             results, reads = detect_payloads(latents, keyring, args.message_length, ecc=args.ecc, k=args.top, fpr=args.fpr, l=args.l,
-                                             reliability=getattr(args, "reliability", 0), window_reliability=getattr(args, "window_reliability", 0))
-            return [_PayloadOutcome(r, "" if e is None else ", " + E.format_read(e, 0, int(args.message_length))) for r, e in zip(results, reads)]
+                                             reliability=getattr(args, "reliability", 0), window_reliability=getattr(args, "window_reliability", 0),
+                                             list_size=int(getattr(args, "ecc_list", 1) or 1))
+            return [_PayloadOutcome(r, "" if e is None else ", " + E.format_any(e, 0, int(args.message_length), int(getattr(args, "ecc_list", 1) or 1)))
+                    for r, e in zip(results, reads)]
         if getattr(args, "align", "none") != "none":
             from . import align as AL
             cands = AL.alignments(args.align, int(args.align_shift), latents.shape[-2], latents.shape[-1])
@@ -822,6 +833,8 @@ def _report(job, outcomes, args, keyring, synthetic: bool) -> None:
             fields += [("align_window_reliability", args.align_window_reliability)]
         if getattr(args, "ecc", None) is not None:
             fields += [("ecc", args.ecc)]
+            if int(getattr(args, "ecc_list", 1) or 1) > 1:
+                fields += [("ecc_list", args.ecc_list)]
         out.write(f"{bar}Batch Info{bar}\n" + "".join(f"{k},{v}\n" for k, v in fields) + f"{bar}Batch Start{bar}\n")
         if synthetic:
             out.write(f"{X.SYNTHETIC_MARKER},'{args.model_id}' is not a local checkpoint: the detections below are not meaningful\n")

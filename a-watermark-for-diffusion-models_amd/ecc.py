@@ -1,7 +1,9 @@
 """Error-corrected payloads: the M-bit message is a codeword of the rate-1/2, constraint-length-7 convolutional code (generators
 0o171, 0o133, zero tail) over payload | CRC-16/CCITT-FALSE | pad, its code bits spread over the message by a multiplicative interleaver.  `encode` runs on
 the host (a few hundred bit operations); `read` decodes the soft votes of a batch in one launch (`codec.viterbi_decode`, gsw_viterbi_decode) -- there is no
-CPU decoder here.  The coded message is a message like any other: embed, registries, trace and the searches take it as it is."""
+CPU decoder here.  The coded message is a message like any other: embed, registries, trace and the searches take it as it is.
+`read_list` is the same read with a list: the decoder keeps the 2, 4 or 8 best paths and the CRC picks among them
+(`codec.viterbi_list_decode`, gsw_viterbi_list_decode); what is issued does not change."""
 from __future__ import annotations
 
 import math
@@ -115,6 +117,67 @@ def read(score: torch.Tensor) -> EccRead:
     small = torch.stack([d.ok, d.flips, d.metric]).cpu().numpy()
     return EccRead([info[b, :pb].tobytes() for b in range(info.shape[0])], [bool(v) for v in small[0]], [int(v) for v in small[1]], [int(v) for v in small[2]],
                    d.message)
+
+
+LIST_SIZES = codec.VITERBI_LIST_SIZES
+
+
+def check_list_size(list_size) -> int:
+    """`list_size=` / `ecc_list=` / `--ecc_list`: 1 (the plain read), 2, 4 or 8"""
+    if isinstance(list_size, bool) or not isinstance(list_size, (int, np.integer)) or int(list_size) not in LIST_SIZES:
+        raise ValueError(f"ecc: the list size must be one of {LIST_SIZES}, got {list_size!r}")
+    return int(list_size)
+
+
+class EccListRead(NamedTuple):
+    """What `read_list` returns for a batch of B images: `EccRead`'s fields for the SELECTED path, then which path that was"""
+    payload: List[bytes]
+    ok: List[bool]
+    flips: List[int]
+    metric: List[int]
+    message: torch.Tensor    # uint8 [B, M / 8] on score's device
+    rank: List[int]          # the rank of the selected path among the L best: the lowest whose CRC holds, 0 when none does
+    n_ok: List[int]          # how many of the L paths pass the CRC; above 1 the CRC alone did not single the payload out
+
+    def image(self, b: int) -> "EccListRead":
+        return EccListRead([self.payload[b]], [self.ok[b]], [self.flips[b]], [self.metric[b]], self.message[b:b + 1], [self.rank[b]], [self.n_ok[b]])
+
+
+def list_read_from_decode(d, message_length: int) -> EccListRead:
+    """the host side of `read_list`: the seven arrays of a list decode (device tensors or NumPy arrays) -> `EccListRead`"""
+    host = lambda t: t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    pb = capacity(message_length)
+    info = host(d.info)
+    ints = lambda t: [int(v) for v in host(t)]
+    return EccListRead([info[b, :pb].tobytes() for b in range(info.shape[0])], [bool(v) for v in host(d.ok)], ints(d.flips), ints(d.metric), d.message,
+                       ints(d.rank), ints(d.n_ok))
+
+
+def read_list(score: torch.Tensor, list_size: int) -> EccListRead:
+    """`read` with a list: the decoder keeps the `list_size` best paths and returns the best-ranked one whose CRC holds, in one
+    launch (`codec.viterbi_list_decode`).  What was issued does not change; a row that carries no payload gets ok with probability at most
+    list_size 2^-18 instead of 2^-18."""
+    list_size = check_list_size(list_size)
+    if isinstance(score, torch.Tensor) and score.dim() == 2:
+        check_length(score.shape[1])                                # payloads are defined for 64..8192 bits, whatever longer rows the kernel serves
+    d = codec.viterbi_list_decode(score, list_size)
+    small = torch.stack([d.ok, d.flips, d.metric, d.rank, d.n_ok]).cpu().numpy()    # one device-to-host copy for the five small results
+    return list_read_from_decode(codec.ViterbiListDecode(d.info, d.message, small[2], small[1], small[0], small[3], small[4]), score.shape[1])
+
+
+def read_any(score: torch.Tensor, list_size: int = 1):
+    """`read` at list size 1 (today's launch and today's `EccRead`), `read_list` above"""
+    return read(score) if check_list_size(list_size) == 1 else read_list(score, list_size)
+
+
+def format_read_list(r: EccListRead, b: int, message_length: int, list_size: int) -> str:
+    """`format_read`'s text plus which of the `list_size` paths was selected, and how many pass when more than one does"""
+    text = f"{format_read(r, b, message_length)}, list rank {r.rank[b]} of {list_size}"
+    return text + (f", {r.n_ok[b]} candidates pass" if r.n_ok[b] > 1 else "")
+
+
+def format_any(r, b: int, message_length: int, list_size: int = 1) -> str:
+    return format_read_list(r, b, message_length, list_size) if isinstance(r, EccListRead) else format_read(r, b, message_length)
 
 
 def score_from_counts(counts: torch.Tensor, copies: int) -> torch.Tensor:

@@ -139,9 +139,12 @@ def _ecc_wanted(args):
     """--ecc as None or "conv"; next to --align, --align_shift or several GPUs it is refused by name, and the message length must be a coded one"""
     code = getattr(args, "ecc", None)
     if code is None:
+        if _ecc_list(args) > 1:
+            raise ValueError("--ecc_list above 1 needs --ecc conv: the list read is a read of error-corrected payloads")
         return None
     from . import ecc as E
     E.check_code(code)
+    E.check_list_size(_ecc_list(args))
     for flag, on in (("--align", getattr(args, "align", None) not in (None, "none")), ("--align_shift", bool(int(getattr(args, "align_shift", 0) or 0)))):
         if on:
             raise ValueError(f"--ecc cannot be combined with {flag} yet: the payload read is not wired through the alignment search")
@@ -151,20 +154,27 @@ def _ecc_wanted(args):
     return code
 
 
+def _ecc_list(args) -> int:
+    """--ecc_list: the list size of the payload read, 1 (the plain read) when absent"""
+    v = getattr(args, "ecc_list", 1)
+    return 1 if v is None else v
+
+
 def _ecc_note(r) -> str:
     """what --ecc adds after an image's line"""
     return f"\n{r.note}" if isinstance(r, _EccBits) and r.note else ""
 
 
-def _with_payloads(strings, score, m: int):
-    """the bit strings of a batch (or the exceptions raised for them) -> the same, every string carrying its payload read: ONE `ecc.read` launch"""
+def _with_payloads(strings, score, m: int, list_size: int = 1):
+    """the bit strings of a batch (or the exceptions raised for them) -> the same, every string carrying its payload read: ONE `ecc.read` launch, with
+    --ecc_list above 1 ONE `ecc.read_list` launch"""
     from . import ecc as E
-    read = E.read(score.contiguous())
+    read = E.read_any(score.contiguous(), list_size)
     out = []
     for b, s in enumerate(strings):
         if not isinstance(s, Exception):
             s = _EccBits(s)
-            s.note = E.format_read(read, b, m)
+            s.note = E.format_any(read, b, m, list_size)
         out.append(s)
     return out
 
@@ -245,7 +255,7 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     if f & N.GSW_FLAG_SATURATED:
         raise ValueError("invalid literal for int() with base 2")
     text = codec.bits_to_str(bits[0].cpu().numpy())[:m]
-    return text if code is None else _with_payloads([text], score[:1], m)[0]
+    return text if code is None else _with_payloads([text], score[:1], m, _ecc_list(args))[0]
 
 
 def recover_exactracted_message_batch(latents: torch.Tensor, args):
@@ -267,7 +277,7 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
             out.append(ValueError("invalid literal for int() with base 2"))
         else:
             out.append(codec.bits_to_str(bits_h[b])[:m])
-    return out if code is None else _with_payloads(out, score, m)
+    return out if code is None else _with_payloads(out, score, m, _ecc_list(args))
 
 
 def calculate_bit_accuracy(original_message_hex, extracted_message_bin):
@@ -775,7 +785,7 @@ def build_parser():
                 self.error("--align cannot be combined with --soft 1, --robust 1 or --tamper_map: the alignment search reads the reference's vote")
             if a.align_shift < 0 or (a.align == "none" and a.align_shift):
                 self.error("--align_shift is a non-negative number of lattice steps and needs --align flips or --align d4")
-            if a.ecc is not None:
+            if a.ecc is not None or a.ecc_list > 1:
                 try:
                     _ecc_wanted(a)
                 except ValueError as e:
@@ -850,6 +860,9 @@ def build_parser():
                         help="(not a reference flag) the message is an error-corrected payload (issue --ecc conv): the votes of whichever decoder is chosen "
                              "(plain, --soft 1, --window_soft L, --robust 1, --robust_soft L) are decoded by one Viterbi launch per batch, and after the "
                              "existing line comes 'payload <hex> crc ok|FAILED, corrected <flips> of <M>'.  Not with --align, --align_shift or --gpus above 1 yet")
+    parser.add_argument("--ecc_list", type=int, default=1, choices=(1, 2, 4, 8),
+                        help="(not a reference flag) with --ecc conv: the list read -- the decoder keeps this many best paths and the CRC picks among them; "
+                             "the payload line gains ', list rank <r> of <L>[, <n> candidates pass]'.  1 (default): the plain read and today's text")
     parser.add_argument("--original_payload_hex", default=None,
                         help="(not a reference flag) with --ecc conv, in the place of --original_message_hex: the payload, encoded to the coded message first")
     return parser

@@ -71,7 +71,7 @@ class GaussianShadingPipeline:
     # X2 + X3-X5 + X6 against each image's own record
     def verify_records(self, x0: torch.Tensor, records: torch.Tensor, msg_bytes: int, *, return_latents: bool = False, soft: bool = False,
                        levels: int = 15, clip: float = 2.5, window_levels: Optional[int] = None, robust_levels: Optional[int] = None, tile: int = 8,
-                       iters: int = 2, sign_rounds: int = 1, ecc: Optional[str] = None):
+                       iters: int = 2, sign_rounds: int = 1, ecc: Optional[str] = None, ecc_list: int = 1):
         """(bits, flags, matches) of `codec.extract_records` on the DDIM inversion of x0, image b under row b of `records`.
         soft=True: the `codec.SoftVote` (bits, flags, matches, score, wsum, wsq) of `codec.extract_soft` instead, every element weighted by
         one of `levels` reliability levels with thresholds scaled to its image's RMS (`soft.uniform_thresholds(z, levels, clip)`); l = 1 only.
@@ -81,15 +81,20 @@ class GaussianShadingPipeline:
         default table of L levels for this l, then `codec.decode_robust` under each record's own key with `tile`, `iters` and `sign_rounds`;
         matches from `codec.bit_matches` against each record's message); not with soft=True or window_levels.
         ecc="conv": the records' messages are coded payloads (`issue_latents(..., ecc="conv")`); the votes of whichever decoder was chosen go through one
-        `codec.viterbi_decode` launch and the result is (what is returned without ecc, `ecc.EccRead`) -- with return_latents (that, EccRead, z)."""
+        `codec.viterbi_decode` launch and the result is (what is returned without ecc, `ecc.EccRead`) -- with return_latents (that, EccRead, z).
+        ecc_list=2, 4 or 8 with ecc="conv": the list read (`ecc.read_list`), an `ecc.EccListRead` in the EccRead's place; 1 is
+        today's launch."""
         from . import ecc as E
+        ecc_list = E.check_list_size(ecc_list)
         if E.check_code(ecc) is not None:
             E.check_length(8 * int(msg_bytes))
+        elif ecc_list > 1:
+            raise ValueError('ecc_list above 1 needs ecc="conv": the list read is a read of error-corrected payloads')
 
         def finish(res, z, score):
             if ecc is None:
                 return (*res, z) if return_latents else res
-            read = E.read(score.contiguous())
+            read = E.read_any(score.contiguous(), ecc_list)
             return (res, read, z) if return_latents else (res, read)
 
         if robust_levels is not None:

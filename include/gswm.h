@@ -982,6 +982,31 @@ int gsw_trace_keyed_pooled_topk(const uint8_t* signs_dev, const uint8_t* planes_
 int gsw_viterbi_decode(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, uint8_t* info_dev, uint8_t* message_dev, int32_t* metric_dev,
                        int32_t* flips_dev, int32_t* ok_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * The list read of error-corrected payloads.  The code, the interleaver, the info word, the branch metrics, the tail and the
+ * int32 bound are gsw_viterbi_decode's; the embed and the coded message do not change.  Additive: gsw_version() stays 500.
+ *
+ * gsw_viterbi_list_decode, one launch per batch, one wavefront per image: a parallel list Viterbi decode with list_size = L in {1, 2, 4, 8}.  Every
+ * state s keeps at most L (metric, path) entries, best first.  Before step 0 state 0 holds one entry of metric 0 and nothing else holds any.  Step t
+ * merges the lists of the predecessors 2 (s & 31) + d, d in {0, 1} (d = 0 entries + bm, d = 1 entries - bm) and keeps the first L: higher metric
+ * first, on equal metrics a d = 0 entry before a d = 1 entry, entries of one predecessor in their rank order; an empty slot never precedes a filled
+ * one and a state holds min(L, count0 + count1) entries; in the 6 tail steps only states with s >> 5 == 0 hold any.  After step T - 1 state 0 holds L
+ * paths.  ok_r: the info word of rank r passes the CRC and its last byte is zero.  The selected rank is the lowest r with ok_r, rank 0 when there is none.
+ * Outputs, every element written for every image; info, message, metric, flips and ok describe the SELECTED path exactly as gsw_viterbi_decode
+ * describes its single path:
+ *   rank_dev    : int32 [B], the selected rank
+ *   n_ok_dev    : int32 [B], the number of ranks with ok_r (more than one: the CRC alone did not single the payload out)
+ * At list_size 1 the first five outputs equal gsw_viterbi_decode's byte for byte, rank is 0 and n_ok equals ok.  A row that carries no payload gets
+ * ok = 1 with probability at most L 2^-18 (16 CRC bits, 2 pad bits) instead of 2^-18.
+ * Integer arithmetic only, no atomics, no workspace: the survivor records (L bits per state and step) live in LDS, one slice per wavefront of
+ *   wave_lds(M, L) = M (5 + 1/16 + 9 L / 2) + 256 L bytes, rounded up to 16.
+ * GSW_ERR_BAD_ARG: null or misaligned pointer (score, metric, flips, ok, rank, n_ok: 4 bytes), B < 1, M < 64 or not a multiple of 16,
+ * score_stride < M, list_size not in {1, 2, 4, 8}.  GSW_ERR_UNSUPPORTED: wave_lds(M, L) > 163 840 (the LDS of a compute unit): M above 17 104,
+ * 11 600, 7 056 and 3 936 at L = 1, 2, 4 and 8.  In that order; every refusal happens before any launch. */
+int gsw_viterbi_list_decode(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, int list_size,
+                            uint8_t* info_dev, uint8_t* message_dev, int32_t* metric_dev, int32_t* flips_dev,
+                            int32_t* ok_dev, int32_t* rank_dev, int32_t* n_ok_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif
