@@ -934,24 +934,48 @@ def trace_keyed_pooled_topk(rows: PooledRows, n_bits: int, records: torch.Tensor
 
 # ------------------------------------------------------------------------------------------------ error-corrected payloads: the Viterbi read of the votes
 VITERBI_MIN_BITS, VITERBI_MAX_BITS = 64, 8192   # message bits of a coded message (csrc/gswm_viterbi_plan.h)
+VITERBI_CODES = ("conv", "conv23", "conv34")    # rates 1/2, 2/3, 3/4: the index is the C entry points' `rate` (csrc/gswm_viterbi_rate_plan.h)
+
+
+def viterbi_rate(code) -> int:
+    if not isinstance(code, str) or code not in VITERBI_CODES:
+        raise ValueError(f"code must be one of {VITERBI_CODES}, got {code!r}")
+    return VITERBI_CODES.index(code)
+
+
+def viterbi_kept_bits(steps: int, code="conv") -> int:
+    """N(t): the code bits the first `steps` trellis steps keep -- (rate + 2) (t div P) + (0, 2, 3)[t mod P], P = rate + 1"""
+    rate = viterbi_rate(code)
+    return (rate + 2) * (steps // (rate + 1)) + (0, 2, 3)[steps % (rate + 1)]
+
+
+def viterbi_steps(message_bits: int, code="conv") -> int:
+    """T: the largest multiple of 8 with N(T) <= M"""
+    T = int(message_bits) // 8 * 8
+    while T > 0 and viterbi_kept_bits(T, code) > message_bits:
+        T -= 8
+    return T
 
 
 class ViterbiDecode(NamedTuple):
     """What `viterbi_decode` returns, all on score's device"""
-    info: torch.Tensor      # uint8 [B, M / 16], the I = M / 2 - 6 info bits MSB first: payload, CRC-16, 2 pad bits (the rest of the last byte is zero)
+    info: torch.Tensor      # uint8 [B, T / 8] (M / 16 under "conv"), the I = T - 6 info bits MSB first: payload, CRC-16, 2 pad bits (the rest of the last byte is zero)
     message: torch.Tensor   # uint8 [B, M / 8], the re-encoded, re-interleaved codeword: the corrected message
     metric: torch.Tensor    # int32 [B], the winning path's correlation
     flips: torch.Tensor     # int32 [B], positions where the corrected message disagrees with score > 0
     ok: torch.Tensor        # int32 [B], 1: the CRC matches and the pad bits are zero
 
 
-def viterbi_decode(score: torch.Tensor) -> ViterbiDecode:
+def viterbi_decode(score: torch.Tensor, code="conv") -> ViterbiDecode:
     """Decode the soft votes of B images under the rate-1/2, constraint-length-7 convolutional code of `ecc.encode`, in one launch
     (gsw_viterbi_decode, one wavefront per image): the maximum-correlation codeword for every row.
 
     score: int32 [B, M] on a HIP device, positive = bit 1 (`SoftVote.score`, `RobustVote.score`, 2 counts - copies); rows may be strided (a column
     slice of a wider tensor), elements may not; M a multiple of 16 in 64..8192 (ValueError); sum_t |score[b, t]| < 2**30 is the caller's bound,
-    which every vote of this library keeps.  Integer arithmetic: the results equal tests/ecc_reference.py bit for bit."""
+    which every vote of this library keeps.  Integer arithmetic: the results equal tests/ecc_reference.py bit for bit.
+    code: "conv" is that code and that launch; "conv23" / "conv34" are its punctured forms of rates 2/3 and 3/4 (gsw_viterbi_decode_rate; DESIGN.md
+    section 4.31, tests/ecc_rate_reference.py): info has T / 8 bytes, message carries 0 at the M - N spare positions, flips counts the N code positions."""
+    rate = viterbi_rate(code)
     if not isinstance(score, torch.Tensor) or score.dim() != 2 or score.dtype != torch.int32:
         raise ValueError("score must be an int32 tensor [B, message bits]")
     B, M = score.shape
@@ -967,12 +991,16 @@ def viterbi_decode(score: torch.Tensor) -> ViterbiDecode:
         raise ValueError("score must be 4-byte aligned")
     stride = score.stride(0) if B > 1 else M
     dev = score.device
-    out = ViterbiDecode(torch.empty((B, M // 16), dtype=torch.uint8, device=dev), torch.empty((B, M // 8), dtype=torch.uint8, device=dev),
+    out = ViterbiDecode(torch.empty((B, viterbi_steps(M, code) // 8), dtype=torch.uint8, device=dev), torch.empty((B, M // 8), dtype=torch.uint8, device=dev),
                         torch.empty((B,), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
                         torch.empty((B,), dtype=torch.int32, device=dev))
     with torch.cuda.device(dev):
-        N.check(N.lib().gsw_viterbi_decode(score.data_ptr(), stride, B, M, out.info.data_ptr(), out.message.data_ptr(), out.metric.data_ptr(),
-                                           out.flips.data_ptr(), out.ok.data_ptr(), _stream_ptr()))
+        if rate == 0:
+            N.check(N.lib().gsw_viterbi_decode(score.data_ptr(), stride, B, M, out.info.data_ptr(), out.message.data_ptr(), out.metric.data_ptr(),
+                                               out.flips.data_ptr(), out.ok.data_ptr(), _stream_ptr()))
+        else:
+            N.check(N.lib().gsw_viterbi_decode_rate(score.data_ptr(), stride, B, M, rate, out.info.data_ptr(), out.message.data_ptr(),
+                                                    out.metric.data_ptr(), out.flips.data_ptr(), out.ok.data_ptr(), _stream_ptr()))
     return out
 
 
@@ -980,10 +1008,11 @@ VITERBI_LIST_SIZES = (1, 2, 4, 8)
 VITERBI_LIST_LDS = 160 * 1024                   # one wavefront's LDS slice may take the LDS of a compute unit (csrc/gswm_viterbi_list_plan.h)
 
 
-def viterbi_list_wave_lds(message_bits: int, list_size: int) -> int:
-    """bytes of LDS one image's list decode needs: M (5 + 1/16 + 9 L / 2) + 256 L, rounded up to 16"""
-    M, L = int(message_bits), int(list_size)
-    return (4 * M + 256 * L + 4 * M * L + M * L // 2 + M + M // 16 + 15) // 16 * 16
+def viterbi_list_wave_lds(message_bits: int, list_size: int, code="conv") -> int:
+    """bytes of LDS one image's list decode needs: 4 M + 256 L + 9 T L + M + T / 8, rounded up to 16 -- M (5 + 1/16 + 9 L / 2) + 256 L under "conv",
+    where T = M / 2"""
+    M, L, T = int(message_bits), int(list_size), viterbi_steps(message_bits, code)
+    return (4 * M + 256 * L + 9 * T * L + M + T // 8 + 15) // 16 * 16
 
 
 class ViterbiListDecode(NamedTuple):
@@ -997,13 +1026,15 @@ class ViterbiListDecode(NamedTuple):
     n_ok: torch.Tensor      # int32 [B], the number of the L ranks whose CRC holds
 
 
-def viterbi_list_decode(score: torch.Tensor, list_size: int) -> ViterbiListDecode:
+def viterbi_list_decode(score: torch.Tensor, list_size: int, code="conv") -> ViterbiListDecode:
     """`viterbi_decode` with a list: every trellis state keeps its `list_size` = L best paths (L in 1, 2, 4, 8), and of the L paths that end in state 0
     the best-ranked one whose CRC holds is returned -- rank 0, the plain decode, when none does.  One launch (gsw_viterbi_list_decode, one wavefront
     per image); at L = 1 the first five tensors equal `viterbi_decode`'s.  DESIGN.md section 4.30 has the merge order and its tie rule.
 
     score: as `viterbi_decode`.  M a multiple of 16 from 64 up, as large as `viterbi_list_wave_lds(M, L)` <= 163 840 allows: 17 104, 11 600, 7 056,
-    3 936 bits at L = 1, 2, 4, 8 (ValueError beyond).  Integer arithmetic: the results equal tests/ecc_list_reference.py bit for bit."""
+    3 936 bits at L = 1, 2, 4, 8 (ValueError beyond).  Integer arithmetic: the results equal tests/ecc_list_reference.py bit for bit.
+    code: as in `viterbi_decode`; the punctured codes go through gsw_viterbi_list_decode_rate and are bounded by `viterbi_list_wave_lds(M, L, code)`."""
+    rate = viterbi_rate(code)
     if isinstance(list_size, bool) or not isinstance(list_size, int) or list_size not in VITERBI_LIST_SIZES:
         raise ValueError(f"list_size must be one of {VITERBI_LIST_SIZES}, got {list_size!r}")
     if not isinstance(score, torch.Tensor) or score.dim() != 2 or score.dtype != torch.int32:
@@ -1011,8 +1042,8 @@ def viterbi_list_decode(score: torch.Tensor, list_size: int) -> ViterbiListDecod
     B, M = score.shape
     if M % 16 or M < VITERBI_MIN_BITS:
         raise ValueError(f"score holds {M} message bits: a coded message has a multiple of 16 bits, {VITERBI_MIN_BITS} at least")
-    if viterbi_list_wave_lds(M, list_size) > VITERBI_LIST_LDS:
-        raise ValueError(f"score holds {M} message bits: at list_size {list_size} one image's survivor records need {viterbi_list_wave_lds(M, list_size)} "
+    if viterbi_list_wave_lds(M, list_size, code) > VITERBI_LIST_LDS:
+        raise ValueError(f"score holds {M} message bits: at list_size {list_size} one image's survivor records need {viterbi_list_wave_lds(M, list_size, code)} "
                          f"bytes of LDS, more than the {VITERBI_LIST_LDS} of a compute unit")
     if B < 1:
         raise ValueError("score holds no image")
@@ -1025,12 +1056,17 @@ def viterbi_list_decode(score: torch.Tensor, list_size: int) -> ViterbiListDecod
     stride = score.stride(0) if B > 1 else M
     dev = score.device
     i32 = lambda: torch.empty((B,), dtype=torch.int32, device=dev)
-    out = ViterbiListDecode(torch.empty((B, M // 16), dtype=torch.uint8, device=dev), torch.empty((B, M // 8), dtype=torch.uint8, device=dev),
-                            i32(), i32(), i32(), i32(), i32())
+    out = ViterbiListDecode(torch.empty((B, viterbi_steps(M, code) // 8), dtype=torch.uint8, device=dev),
+                            torch.empty((B, M // 8), dtype=torch.uint8, device=dev), i32(), i32(), i32(), i32(), i32())
     with torch.cuda.device(dev):
-        N.check(N.lib().gsw_viterbi_list_decode(score.data_ptr(), stride, B, M, list_size, out.info.data_ptr(), out.message.data_ptr(),
-                                                out.metric.data_ptr(), out.flips.data_ptr(), out.ok.data_ptr(), out.rank.data_ptr(),
-                                                out.n_ok.data_ptr(), _stream_ptr()))
+        if rate == 0:
+            N.check(N.lib().gsw_viterbi_list_decode(score.data_ptr(), stride, B, M, list_size, out.info.data_ptr(), out.message.data_ptr(),
+                                                    out.metric.data_ptr(), out.flips.data_ptr(), out.ok.data_ptr(), out.rank.data_ptr(),
+                                                    out.n_ok.data_ptr(), _stream_ptr()))
+        else:
+            N.check(N.lib().gsw_viterbi_list_decode_rate(score.data_ptr(), stride, B, M, rate, list_size, out.info.data_ptr(), out.message.data_ptr(),
+                                                         out.metric.data_ptr(), out.flips.data_ptr(), out.ok.data_ptr(), out.rank.data_ptr(),
+                                                         out.n_ok.data_ptr(), _stream_ptr()))
     return out
 
 

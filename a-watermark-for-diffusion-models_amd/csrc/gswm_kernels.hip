@@ -1673,6 +1673,7 @@ int gsw_geglu(const void* in_dev, void* out_dev, int64_t rows, int inner, int dt
 // Error-corrected payloads (rate-1/2, K = 7 convolutional code under the votes): gsw_viterbi_decode, kernel and entry point
 // ------------------------------------------------------------------------------------------------
 #include "gswm_viterbi_plan.h"
+#include "gswm_viterbi_rate_plan.h"   // the punctured codes' plan, for both reads (it brings the list read's plan with it)
 #include "gswm_viterbi.inc"
 
 // ------------------------------------------------------------------------------------------------

@@ -20,6 +20,15 @@
 // a wave-uniform 64-bit mask; the survivor decisions of a step are one ballot, written to LDS by lane 0.  Lane 0 then walks the T ballots back (a serial,
 // latency-bound walk of T <= 4096 dependent LDS reads), and the wave re-encodes, counts, packs and stores in parallel; lane 0 runs the CRC over at most 509
 // bytes.  No scratch, no atomics, no workspace, every output element written.
+//
+// Punctured codes (DESIGN.md section 4.31; tests/ecc_rate_reference.py).  The kernel takes the rate as a compile-time parameter: RATE = 0 is the code above,
+// instruction for instruction; RATE = 1, 2 (rates 2/3, 3/4) puncture it with period P = RATE + 1 (gswm_viterbi_rate_plan.h: phase 0 keeps c0 c1, phase 1 c1,
+// phase 2 c0).  A punctured output adds nothing to a branch metric, so the complement property holds as it is.  The N kept votes are staged compactly --
+// x[j] = score[(j S) mod M] for j < N, the spare positions are not read -- and step t reads its one or two votes at N(t).  Between the first 6 steps and the
+// tail the loop runs whole periods: one wave-uniform LDS read of the period's 3 or 4 votes, the P branch metrics, then the P dependent add-compare-selects, so
+// that neither the fetch nor the labels sit on the path-metric chain; the steps before the first period boundary (the loop is entered at phase 6 mod P) and
+// after the last (it is left at phase I mod P) take one step at a time.  Re-encoding is lane per step: a step's kept bits go to the positions of N(t), N(t) + 1,
+// and the M - N spare positions of the message are written 0.
 
 namespace viterbi {
 
@@ -33,11 +42,14 @@ struct ViterbiArgs {
     int64_t stride;         // elements
     int B, M, T, I, info_bytes, payload_bytes, S, Sinv;
     uint32_t wave_lds;
+    int N;                  // code bits kept (M at rate 1/2, where it is not read)
 };
 
 __device__ __forceinline__ uint32_t parity7(uint32_t v) { return (uint32_t)__popc(v) & 1u; }
 
+template <int RATE>
 __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_decode_kernel(ViterbiArgs a) {
+    constexpr int P = viterbi_rate_period(RATE), V = viterbi_rate_votes(RATE);
     extern __shared__ __attribute__((aligned(16))) uint8_t vit_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int waves = blockDim.x >> 6;
@@ -47,15 +59,22 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_decode_ker
     const int M = a.M, T = a.T, I = a.I;
 
     uint8_t* base = vit_lds + (size_t)wave * a.wave_lds;
-    int32_t* x = (int32_t*)base;                                    // [M] de-interleaved scores
+    int32_t* x = (int32_t*)base;                                    // [M] de-interleaved scores, the first N of them staged
     unsigned long long* dec = (unsigned long long*)(base + 4 * (size_t)M);   // [T] survivor ballots
-    uint8_t* ub = base + 8 * (size_t)M;                             // [T] decoded inputs
+    uint8_t* ub = base + 4 * (size_t)M + 8 * (size_t)T;             // [T] decoded inputs
     uint8_t* cw = ub + T;                                           // [M] the message, a byte per bit
     uint8_t* ib = cw + M;                                           // [info_bytes] the packed info word
 
     // ---- stage the row through the interleaver: coalesced global reads, the permutation on the LDS side
     const int32_t* row = a.score + (int64_t)b * a.stride;
-    for (int p = lane; p < M; p += 64) x[(uint32_t)(p * a.Sinv) % (uint32_t)M] = row[p];
+    if constexpr (RATE == 0) {
+        for (int p = lane; p < M; p += 64) x[(uint32_t)(p * a.Sinv) % (uint32_t)M] = row[p];
+    } else {
+        for (int p = lane; p < M; p += 64) {
+            const uint32_t j = (uint32_t)(p * a.Sinv) % (uint32_t)M;
+            if (j < (uint32_t)a.N) x[j] = row[p];                    // a spare position holds no code bit: its vote is not read
+        }
+    }
     __syncthreads();
 
     // ---- forward pass.  The labels of the d = 0 branch into state `lane` are constants of the lane.
@@ -68,9 +87,7 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_decode_ker
     // One step.  `general`: the form of the definition, for the first 6 steps (states become reachable) and the 6 tail steps (states cease to be).  In between
     // every state is reachable through both predecessors and both inputs exist, so the step is an add, a subtract, a compare and a maximum: the loop is bound
     // by the instructions it issues per step as much as by the latency of the exchange, and this form issues about a dozen fewer.
-    auto step = [&](int t, auto general) {
-        const int2 ab = xx[t];
-        const int bm = (l0 ? ab.x : -ab.x) + (l1 ? ab.y : -ab.y);
+    auto advance = [&](int t, int bm, auto general) {
         const int m0 = __shfl(pm, p0, 64), m1 = __shfl(pm, p0 + 1, 64);
         const int c0 = m0 + bm, c1 = m1 - bm;
         unsigned long long ball;
@@ -88,8 +105,36 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_decode_ker
         }
         if (lane == 0) dec[t] = ball;
     };
+    // the branch metric of a step of phase `ph` whose first kept vote is x[o]
+    auto bm_of = [&](int ph, int o) {
+        if (ph == 0) return (l0 ? x[o] : -x[o]) + (l1 ? x[o + 1] : -x[o + 1]);
+        const int v = x[o];
+        return ph == 1 ? (l1 ? v : -v) : (l0 ? v : -v);
+    };
+    auto step = [&](int t, auto general) {
+        if constexpr (RATE == 0) {
+            const int2 ab = xx[t];
+            advance(t, (l0 ? ab.x : -ab.x) + (l1 ? ab.y : -ab.y), general);
+        } else {
+            const int ph = t % P;
+            advance(t, bm_of(ph, V * (t / P) + viterbi_rate_phase_offset(ph)), general);
+        }
+    };
     for (int t = 0; t < VITERBI_TAIL; ++t) step(t, std::true_type{});
-    for (int t = VITERBI_TAIL; t < I; ++t) step(t, std::false_type{});       // (after 6 steps `reach` is all ones and stays so until the tail)
+    if constexpr (RATE == 0) {
+        for (int t = VITERBI_TAIL; t < I; ++t) step(t, std::false_type{});   // (after 6 steps `reach` is all ones and stays so until the tail)
+    } else {
+        int t = VITERBI_TAIL;
+        for (; t < I && t % P; ++t) step(t, std::false_type{});              // to the first period boundary
+        for (int o = V * (t / P); t + P <= I; t += P, o += V) {              // whole periods: the votes and the metrics first, then the chain
+            int bm[P];
+#pragma unroll
+            for (int ph = 0; ph < P; ++ph) bm[ph] = bm_of(ph, o + viterbi_rate_phase_offset(ph));
+#pragma unroll
+            for (int ph = 0; ph < P; ++ph) advance(t + ph, bm[ph], std::false_type{});
+        }
+        for (; t < I; ++t) step(t, std::false_type{});                       // the period the tail cuts
+    }
     for (int t = I; t < T; ++t) step(t, std::true_type{});
     __syncthreads();
 
@@ -113,13 +158,29 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_decode_ker
         for (int k = 0; k <= VITERBI_TAIL; ++k)
             if (t - k >= 0) r |= (uint32_t)ub[t - k] << (6 - k);
         const uint32_t c0 = parity7(r & 0171u), c1 = parity7(r & 0133u);
-        const int2 ab = xx[t];
-        nflip += (int)(c0 != (uint32_t)(ab.x > 0)) + (int)(c1 != (uint32_t)(ab.y > 0));
-        const uint32_t q0 = (uint32_t)(2 * t) * (uint32_t)a.S % (uint32_t)M;
-        const uint32_t q1 = (uint32_t)(2 * t + 1) * (uint32_t)a.S % (uint32_t)M;
-        cw[q0] = (uint8_t)c0;
-        cw[q1] = (uint8_t)c1;
+        if constexpr (RATE == 0) {
+            const int2 ab = xx[t];
+            nflip += (int)(c0 != (uint32_t)(ab.x > 0)) + (int)(c1 != (uint32_t)(ab.y > 0));
+            const uint32_t q0 = (uint32_t)(2 * t) * (uint32_t)a.S % (uint32_t)M;
+            const uint32_t q1 = (uint32_t)(2 * t + 1) * (uint32_t)a.S % (uint32_t)M;
+            cw[q0] = (uint8_t)c0;
+            cw[q1] = (uint8_t)c1;
+        } else {
+            const int ph = t % P, kept = viterbi_rate_kept(ph);
+            int j = V * (t / P) + viterbi_rate_phase_offset(ph);    // N(t): the step's first kept bit
+            if (kept & 1) {
+                nflip += (int)(c0 != (uint32_t)(x[j] > 0));
+                cw[(uint32_t)j * (uint32_t)a.S % (uint32_t)M] = (uint8_t)c0;
+                ++j;
+            }
+            if (kept & 2) {
+                nflip += (int)(c1 != (uint32_t)(x[j] > 0));
+                cw[(uint32_t)j * (uint32_t)a.S % (uint32_t)M] = (uint8_t)c1;
+            }
+        }
     }
+    if constexpr (RATE != 0)
+        for (int j = a.N + lane; j < M; j += 64) cw[(uint32_t)j * (uint32_t)a.S % (uint32_t)M] = 0;       // the spare positions
     for (int k = lane; k < a.info_bytes; k += 64) {                 // T = 8 info_bytes: the tail's zeros fill the last byte
         uint32_t v = 0u;
 #pragma unroll
@@ -154,6 +215,41 @@ static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 }  // namespace viterbi
 
+namespace viterbi {
+
+template <int RATE>
+static int launch(const ViterbiRatePlan& p, const ViterbiArgs& a, hipStream_t stream) {
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_viterbi_decode_kernel<RATE>, p.lds));
+    hipLaunchKernelGGL(gsw_viterbi_decode_kernel<RATE>, dim3((uint32_t)p.grid), dim3((uint32_t)p.wg), p.lds, stream, a);
+    GSW_HIP(hipGetLastError());
+    return GSW_OK;
+}
+
+}  // namespace viterbi
+
+int gsw_viterbi_decode_rate(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, int rate, uint8_t* info_dev, uint8_t* message_dev,
+                            int32_t* metric_dev, int32_t* flips_dev, int32_t* ok_dev, void* stream) {
+    using namespace viterbi;
+    ViterbiRateQuery q{};
+    q.pointers_ok = score_dev && info_dev && message_dev && metric_dev && flips_dev && ok_dev && aligned4(score_dev) && aligned4(metric_dev) &&
+                    aligned4(flips_dev) && aligned4(ok_dev);
+    q.list = false;
+    q.B = B;
+    q.rate = rate;
+    q.M = message_bits;
+    q.stride = score_stride;
+    const ViterbiRatePlan p = viterbi_rate_decide(q);
+    if (p.status != GSW_OK) return p.status;
+    const ViterbiArgs a{score_dev, info_dev, message_dev, metric_dev, flips_dev, ok_dev, score_stride, B, p.M, p.T, p.I, p.info_bytes, p.payload_bytes, p.S, p.Sinv,
+                        p.wave_lds, p.N};
+    switch (p.rate) {
+        case 0: return launch<0>(p, a, (hipStream_t)stream);
+        case 1: return launch<1>(p, a, (hipStream_t)stream);
+        default: return launch<2>(p, a, (hipStream_t)stream);
+    }
+}
+
+// rate 1/2: the entry point of section 4.29, its plan and its kernel instantiation
 int gsw_viterbi_decode(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, uint8_t* info_dev, uint8_t* message_dev, int32_t* metric_dev,
                        int32_t* flips_dev, int32_t* ok_dev, void* stream) {
     using namespace viterbi;
@@ -166,9 +262,9 @@ int gsw_viterbi_decode(const int32_t* score_dev, int64_t score_stride, int B, in
     const ViterbiPlan p = viterbi_decide(q);
     if (p.status != GSW_OK) return p.status;
     const ViterbiArgs a{score_dev, info_dev, message_dev, metric_dev, flips_dev, ok_dev, score_stride, B, p.M, p.T, p.I, p.info_bytes, p.payload_bytes, p.S, p.Sinv,
-                        p.wave_lds};
-    GSW_HIP(allow_dynamic_lds((const void*)gsw_viterbi_decode_kernel, p.lds));
-    hipLaunchKernelGGL(gsw_viterbi_decode_kernel, dim3((uint32_t)p.grid), dim3((uint32_t)p.wg), p.lds, (hipStream_t)stream, a);
+                        p.wave_lds, p.M};
+    GSW_HIP(allow_dynamic_lds((const void*)gsw_viterbi_decode_kernel<0>, p.lds));
+    hipLaunchKernelGGL(gsw_viterbi_decode_kernel<0>, dim3((uint32_t)p.grid), dim3((uint32_t)p.wg), p.lds, (hipStream_t)stream, a);
     GSW_HIP(hipGetLastError());
     return GSW_OK;
 }

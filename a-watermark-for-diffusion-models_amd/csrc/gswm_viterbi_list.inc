@@ -21,6 +21,11 @@
 // LDS reads per lane), each runs the CRC over its own candidate bit-serially, and a ballot gives rank and n_ok.  The wave re-encodes the selected path, counts
 // flips, packs and stores as gswm_viterbi.inc does.  No scratch, no atomics, no workspace; every output element written; the barriers are workgroup barriers
 // that every wave reaches the same number of times (a wave past the batch decodes the last image again and stores nothing).
+//
+// Punctured codes (DESIGN.md section 4.31).  RATE is a compile-time parameter as in gswm_viterbi.inc, with the same three changes and nothing else: the N kept
+// votes staged compactly, the mask-free steps run as whole periods (votes and branch metrics first, then the P merges; entered at phase full_from mod P, left at
+// phase I mod P), and the re-encode writing a step's kept bits at N(t) and zeros at the spare positions.  RATE = 0 is the code above, instruction for
+// instruction.  Exchange, merge, records, traceback and CRC do not know the rate.
 
 namespace viterbi_list {
 
@@ -38,6 +43,7 @@ struct ListArgs {
     int64_t stride;         // elements
     int B, M, T, I, info_bytes, payload_bytes, S, Sinv, full_from;
     uint32_t wave_lds;
+    int N;                  // code bits kept (M at rate 1/2, where it is not read)
 };
 
 // lane i of a quad reads lane sel[i] of its quad
@@ -46,8 +52,9 @@ __device__ __forceinline__ uint32_t quad_perm(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
 }
 
-template <int L, bool LDSX>
+template <int L, bool LDSX, int RATE = 0>
 __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_list_kernel(ListArgs a) {
+    constexpr int P = viterbi_rate_period(RATE), V = viterbi_rate_votes(RATE);
     extern __shared__ __attribute__((aligned(16))) uint8_t vl_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int waves = blockDim.x >> 6;
@@ -66,7 +73,14 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_list_kerne
 
     // ---- stage the row through the interleaver: coalesced global reads, the permutation on the LDS side
     const int32_t* row = a.score + (int64_t)b * a.stride;
-    for (int p = lane; p < M; p += 64) x[(uint32_t)(p * a.Sinv) % (uint32_t)M] = row[p];
+    if constexpr (RATE == 0) {
+        for (int p = lane; p < M; p += 64) x[(uint32_t)(p * a.Sinv) % (uint32_t)M] = row[p];
+    } else {
+        for (int p = lane; p < M; p += 64) {
+            const uint32_t j = (uint32_t)(p * a.Sinv) % (uint32_t)M;
+            if (j < (uint32_t)a.N) x[j] = row[p];                    // a spare position holds no code bit: its vote is not read
+        }
+    }
     __syncthreads();
 
     // ---- forward pass.  The labels of the d = 0 branch into state `lane` are constants of the lane.
@@ -80,9 +94,7 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_list_kerne
     const int2* xx = (const int2*)x;
 
     // One step.  `general`: lists may hold empty slots (the first 6 + log2 L steps, the tail); `tail`: states with u = 1 end empty.
-    auto step = [&](int t, auto general, auto tail) {
-        const int2 ab = xx[t];
-        const int bm = (l0 ? ab.x : -ab.x) + (l1 ? ab.y : -ab.y);
+    auto advance = [&](int t, int bm, auto general, auto tail) {
         int A[L], Bv[L];
         if constexpr (LDSX) {
             // 16-byte accesses where the list allows: a lane's run starts at 4 L lane bytes, the predecessors' at 8 L (lane & 31) bytes
@@ -158,9 +170,37 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_list_kerne
             if (lane == 0) ((unsigned long long*)dec)[t] = ball;
         }
     };
+    // the branch metric of a step of phase `ph` whose first kept vote is x[o]
+    auto bm_of = [&](int ph, int o) {
+        if (ph == 0) return (l0 ? x[o] : -x[o]) + (l1 ? x[o + 1] : -x[o + 1]);
+        const int v = x[o];
+        return ph == 1 ? (l1 ? v : -v) : (l0 ? v : -v);
+    };
+    auto step = [&](int t, auto general, auto tail) {
+        if constexpr (RATE == 0) {
+            const int2 ab = xx[t];
+            advance(t, (l0 ? ab.x : -ab.x) + (l1 ? ab.y : -ab.y), general, tail);
+        } else {
+            const int ph = t % P;
+            advance(t, bm_of(ph, V * (t / P) + viterbi_rate_phase_offset(ph)), general, tail);
+        }
+    };
     const int full_from = a.full_from;
     for (int t = 0; t < full_from; ++t) step(t, std::true_type{}, std::false_type{});
-    for (int t = full_from; t < I; ++t) step(t, std::false_type{}, std::false_type{});
+    if constexpr (RATE == 0) {
+        for (int t = full_from; t < I; ++t) step(t, std::false_type{}, std::false_type{});
+    } else {
+        int t = full_from;
+        for (; t < I && t % P; ++t) step(t, std::false_type{}, std::false_type{});      // to the first period boundary
+        for (int o = V * (t / P); t + P <= I; t += P, o += V) {                          // whole periods: the votes and the metrics first, then the merges
+            int bm[P];
+#pragma unroll
+            for (int ph = 0; ph < P; ++ph) bm[ph] = bm_of(ph, o + viterbi_rate_phase_offset(ph));
+#pragma unroll
+            for (int ph = 0; ph < P; ++ph) advance(t + ph, bm[ph], std::false_type{}, std::false_type{});
+        }
+        for (; t < I; ++t) step(t, std::false_type{}, std::false_type{});               // the period the tail cuts
+    }
     for (int t = I; t < T; ++t) step(t, std::true_type{}, std::true_type{});
     __syncthreads();
 
@@ -207,13 +247,29 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_list_kerne
         for (int k = 0; k <= VITERBI_TAIL; ++k)
             if (t - k >= 0) r |= (uint32_t)sel[t - k] << (6 - k);
         const uint32_t c0 = viterbi::parity7(r & 0171u), c1 = viterbi::parity7(r & 0133u);
-        const int2 ab = xx[t];
-        nflip += (int)(c0 != (uint32_t)(ab.x > 0)) + (int)(c1 != (uint32_t)(ab.y > 0));
-        const uint32_t q0 = (uint32_t)(2 * t) * (uint32_t)a.S % (uint32_t)M;
-        const uint32_t q1 = (uint32_t)(2 * t + 1) * (uint32_t)a.S % (uint32_t)M;
-        cw[q0] = (uint8_t)c0;
-        cw[q1] = (uint8_t)c1;
+        if constexpr (RATE == 0) {
+            const int2 ab = xx[t];
+            nflip += (int)(c0 != (uint32_t)(ab.x > 0)) + (int)(c1 != (uint32_t)(ab.y > 0));
+            const uint32_t q0 = (uint32_t)(2 * t) * (uint32_t)a.S % (uint32_t)M;
+            const uint32_t q1 = (uint32_t)(2 * t + 1) * (uint32_t)a.S % (uint32_t)M;
+            cw[q0] = (uint8_t)c0;
+            cw[q1] = (uint8_t)c1;
+        } else {
+            const int ph = t % P, kept = viterbi_rate_kept(ph);
+            int j = V * (t / P) + viterbi_rate_phase_offset(ph);    // N(t): the step's first kept bit
+            if (kept & 1) {
+                nflip += (int)(c0 != (uint32_t)(x[j] > 0));
+                cw[(uint32_t)j * (uint32_t)a.S % (uint32_t)M] = (uint8_t)c0;
+                ++j;
+            }
+            if (kept & 2) {
+                nflip += (int)(c1 != (uint32_t)(x[j] > 0));
+                cw[(uint32_t)j * (uint32_t)a.S % (uint32_t)M] = (uint8_t)c1;
+            }
+        }
     }
+    if constexpr (RATE != 0)
+        for (int j = a.N + lane; j < M; j += 64) cw[(uint32_t)j * (uint32_t)a.S % (uint32_t)M] = 0;       // the spare positions
     for (int k = lane; k < a.info_bytes; k += 64) {                 // T = 8 info_bytes: the tail's zeros fill the last byte
         uint32_t v = 0u;
 #pragma unroll
@@ -243,17 +299,52 @@ __global__ __launch_bounds__(64 * VITERBI_MAX_WAVES) void gsw_viterbi_list_kerne
 // where it was the faster form at every size measured (by 3 to 19 %); at L = 1 neither form wins everywhere and the two ds_bpermute of gswm_viterbi.inc stay.
 template <int L> constexpr bool lds_exchange() { return L >= 2; }
 
-template <int L>
-static int launch(const ViterbiListPlan& p, const ListArgs& a, hipStream_t stream) {
-    const void* k = (const void*)gsw_viterbi_list_kernel<L, lds_exchange<L>()>;
-    GSW_HIP(allow_dynamic_lds(k, p.lds));
-    hipLaunchKernelGGL((gsw_viterbi_list_kernel<L, lds_exchange<L>()>), dim3((uint32_t)p.grid), dim3((uint32_t)p.wg), p.lds, stream, a);
+template <int L, int RATE>
+static int launch(int grid, int wg, uint32_t lds, const ListArgs& a, hipStream_t stream) {
+    const void* k = (const void*)gsw_viterbi_list_kernel<L, lds_exchange<L>(), RATE>;
+    GSW_HIP(allow_dynamic_lds(k, lds));
+    hipLaunchKernelGGL((gsw_viterbi_list_kernel<L, lds_exchange<L>(), RATE>), dim3((uint32_t)grid), dim3((uint32_t)wg), lds, stream, a);
     GSW_HIP(hipGetLastError());
     return GSW_OK;
 }
 
+template <int RATE>
+static int launch_rate(const ViterbiRatePlan& p, const ListArgs& a, hipStream_t stream) {
+    switch (p.L) {
+        case 1: return launch<1, RATE>(p.grid, p.wg, p.lds, a, stream);
+        case 2: return launch<2, RATE>(p.grid, p.wg, p.lds, a, stream);
+        case 4: return launch<4, RATE>(p.grid, p.wg, p.lds, a, stream);
+        default: return launch<8, RATE>(p.grid, p.wg, p.lds, a, stream);
+    }
+}
+
 }  // namespace viterbi_list
 
+int gsw_viterbi_list_decode_rate(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, int rate, int list_size, uint8_t* info_dev,
+                                 uint8_t* message_dev, int32_t* metric_dev, int32_t* flips_dev, int32_t* ok_dev, int32_t* rank_dev, int32_t* n_ok_dev, void* stream) {
+    using namespace viterbi_list;
+    using viterbi::aligned4;
+    ViterbiRateQuery q{};
+    q.pointers_ok = score_dev && info_dev && message_dev && metric_dev && flips_dev && ok_dev && rank_dev && n_ok_dev && aligned4(score_dev) &&
+                    aligned4(metric_dev) && aligned4(flips_dev) && aligned4(ok_dev) && aligned4(rank_dev) && aligned4(n_ok_dev);
+    q.list = true;
+    q.B = B;
+    q.L = list_size;
+    q.rate = rate;
+    q.M = message_bits;
+    q.stride = score_stride;
+    const ViterbiRatePlan p = viterbi_rate_decide(q);
+    if (p.status != GSW_OK) return p.status;
+    const ListArgs a{score_dev, info_dev, message_dev, metric_dev, flips_dev, ok_dev, rank_dev, n_ok_dev, score_stride, B, p.M, p.T, p.I, p.info_bytes,
+                     p.payload_bytes, p.S, p.Sinv, p.full_from, p.wave_lds, p.N};
+    switch (p.rate) {
+        case 0: return launch_rate<0>(p, a, (hipStream_t)stream);
+        case 1: return launch_rate<1>(p, a, (hipStream_t)stream);
+        default: return launch_rate<2>(p, a, (hipStream_t)stream);
+    }
+}
+
+// rate 1/2: the entry point of section 4.30, its plan and its kernel instantiations
 int gsw_viterbi_list_decode(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, int list_size, uint8_t* info_dev, uint8_t* message_dev,
                             int32_t* metric_dev, int32_t* flips_dev, int32_t* ok_dev, int32_t* rank_dev, int32_t* n_ok_dev, void* stream) {
     using namespace viterbi_list;
@@ -268,11 +359,11 @@ int gsw_viterbi_list_decode(const int32_t* score_dev, int64_t score_stride, int 
     const ViterbiListPlan p = viterbi_list_decide(q);
     if (p.status != GSW_OK) return p.status;
     const ListArgs a{score_dev, info_dev, message_dev, metric_dev, flips_dev, ok_dev, rank_dev, n_ok_dev, score_stride, B, p.M, p.T, p.I, p.info_bytes,
-                     p.payload_bytes, p.S, p.Sinv, p.full_from, p.wave_lds};
+                     p.payload_bytes, p.S, p.Sinv, p.full_from, p.wave_lds, p.M};
     switch (p.L) {
-        case 1: return launch<1>(p, a, (hipStream_t)stream);
-        case 2: return launch<2>(p, a, (hipStream_t)stream);
-        case 4: return launch<4>(p, a, (hipStream_t)stream);
-        default: return launch<8>(p, a, (hipStream_t)stream);
+        case 1: return launch<1, 0>(p.grid, p.wg, p.lds, a, (hipStream_t)stream);
+        case 2: return launch<2, 0>(p.grid, p.wg, p.lds, a, (hipStream_t)stream);
+        case 4: return launch<4, 0>(p.grid, p.wg, p.lds, a, (hipStream_t)stream);
+        default: return launch<8, 0>(p.grid, p.wg, p.lds, a, (hipStream_t)stream);
     }
 }

@@ -617,7 +617,7 @@ def detect_payloads(latents, keyring: Keyring, message_length: int, *, ecc: str 
     of its lists) when a key is named, else None.  The votes of every image under its own best key -- the read's score, or 2 counts - copies of the sign
     read -- go through ONE `codec.viterbi_decode` launch for the whole batch.  Alignments are not wired yet: `ecc` with `align` is the next step.
     list_size = 2, 4 or 8: the list read (DESIGN.md section 4.30) -- the launch is `codec.viterbi_list_decode`'s and reads[b] an `ecc.EccListRead`;
-    list_size = 1 is today's launch and today's `EccRead`."""
+    list_size = 1 is today's launch and today's `EccRead`.  ecc="conv23" / "conv34": the punctured codes, same reads."""
     from . import ecc as E
     if E.check_code(ecc) is None:
         raise ValueError('detect_payloads needs ecc="conv": without a code this is detect_latents')
@@ -633,7 +633,7 @@ def detect_payloads(latents, keyring: Keyring, message_length: int, *, ecc: str 
     if window_reliability and l == 1:
         raise ValueError("window_reliability needs l = 2 or 4: at l = 1 the levels are reliability")
     results, _, _, score = _detect(latents, keyring, mb, k, limit, l=l, levels=reliability or window_reliability, aligns=None, scores=True)
-    read = E.read_any(score.contiguous(), list_size)
+    read = E.read_any(score.contiguous(), list_size, ecc)
     return results, [read.image(b) if r.key_id is not None else None for b, r in enumerate(results)]
 
 
@@ -756,7 +756,7 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=16, help="images per device batch")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,
                    help="1: raise when a GPU half-precision call would leave the hand-written kernels instead of warning (default: 1)")
-    p.add_argument("--ecc", default=None, choices=("conv",),
+    p.add_argument("--ecc", default=None, choices=("conv", "conv23", "conv34"),
                    help="the messages are error-corrected payloads (issue --ecc conv): for a named key the votes are decoded by one Viterbi launch per batch and "
                         "the line gains 'payload <hex> crc ok|FAILED, corrected <flips> of <M>' (with the sign statistic, --reliability or "
                         "--window_reliability; not with --align, --align_shift, --align_reliability or --align_window_reliability yet)")
@@ -796,7 +796,7 @@ def _detect_files(files, args, keyring) -> list:
             results, reads = detect_payloads(latents, keyring, args.message_length, ecc=args.ecc, k=args.top, fpr=args.fpr, l=args.l,
                                              reliability=getattr(args, "reliability", 0), window_reliability=getattr(args, "window_reliability", 0),
                                              list_size=int(getattr(args, "ecc_list", 1) or 1))
-            return [_PayloadOutcome(r, "" if e is None else ", " + E.format_any(e, 0, int(args.message_length), int(getattr(args, "ecc_list", 1) or 1)))
+            return [_PayloadOutcome(r, "" if e is None else ", " + E.format_any(e, 0, int(args.message_length), int(getattr(args, "ecc_list", 1) or 1), args.ecc))
                     for r, e in zip(results, reads)]
         if getattr(args, "align", "none") != "none":
             from . import align as AL

@@ -136,7 +136,7 @@ class _EccBits(str):
 
 
 def _ecc_wanted(args):
-    """--ecc as None or "conv"; next to --align, --align_shift or several GPUs it is refused by name, and the message length must be a coded one"""
+    """--ecc as None or a code of `ecc.CODES`; next to --align, --align_shift or several GPUs it is refused by name, and the message length must be a coded one"""
     code = getattr(args, "ecc", None)
     if code is None:
         if _ecc_list(args) > 1:
@@ -165,16 +165,16 @@ def _ecc_note(r) -> str:
     return f"\n{r.note}" if isinstance(r, _EccBits) and r.note else ""
 
 
-def _with_payloads(strings, score, m: int, list_size: int = 1):
+def _with_payloads(strings, score, m: int, list_size: int = 1, code: str = "conv"):
     """the bit strings of a batch (or the exceptions raised for them) -> the same, every string carrying its payload read: ONE `ecc.read` launch, with
     --ecc_list above 1 ONE `ecc.read_list` launch"""
     from . import ecc as E
-    read = E.read_any(score.contiguous(), list_size)
+    read = E.read_any(score.contiguous(), list_size, code)
     out = []
     for b, s in enumerate(strings):
         if not isinstance(s, Exception):
             s = _EccBits(s)
-            s.note = E.format_any(read, b, m, list_size)
+            s.note = E.format_any(read, b, m, list_size, code)
         out.append(s)
     return out
 
@@ -255,7 +255,7 @@ def recover_exactracted_message(reversed_latents, args, *, device="cuda"):
     if f & N.GSW_FLAG_SATURATED:
         raise ValueError("invalid literal for int() with base 2")
     text = codec.bits_to_str(bits[0].cpu().numpy())[:m]
-    return text if code is None else _with_payloads([text], score[:1], m, _ecc_list(args))[0]
+    return text if code is None else _with_payloads([text], score[:1], m, _ecc_list(args), code)[0]
 
 
 def recover_exactracted_message_batch(latents: torch.Tensor, args):
@@ -277,7 +277,7 @@ def recover_exactracted_message_batch(latents: torch.Tensor, args):
             out.append(ValueError("invalid literal for int() with base 2"))
         else:
             out.append(codec.bits_to_str(bits_h[b])[:m])
-    return out if code is None else _with_payloads(out, score, m, _ecc_list(args))
+    return out if code is None else _with_payloads(out, score, m, _ecc_list(args), code)
 
 
 def calculate_bit_accuracy(original_message_hex, extracted_message_bin):
@@ -795,7 +795,7 @@ def build_parser():
                     self.error("--original_payload_hex needs --ecc conv and takes the place of --original_message_hex: give one of the two")
                 from . import ecc as E
                 try:
-                    a.original_message_hex = E.encode(bytes.fromhex(a.original_payload_hex), int(a.message_length)).hex()
+                    a.original_message_hex = E.encode(bytes.fromhex(a.original_payload_hex), int(a.message_length), a.ecc).hex()
                 except ValueError as e:
                     self.error(f"--original_payload_hex: {e}")
             if a.original_message_hex is None:
@@ -856,7 +856,7 @@ def build_parser():
                         help="(not a reference flag) read the message under the best alignment of the lattice (align.extract_aligned): flips = half turn and "
                              "the two mirrors, d4 = all eight orientations; none: the reference's vote as it is")
     parser.add_argument("--align_shift", type=int, default=0, metavar="R", help="(not a reference flag) with --align: also every lattice shift in [-R, R]^2")
-    parser.add_argument("--ecc", default=None, choices=("conv",),
+    parser.add_argument("--ecc", default=None, choices=("conv", "conv23", "conv34"),
                         help="(not a reference flag) the message is an error-corrected payload (issue --ecc conv): the votes of whichever decoder is chosen "
                              "(plain, --soft 1, --window_soft L, --robust 1, --robust_soft L) are decoded by one Viterbi launch per batch, and after the "
                              "existing line comes 'payload <hex> crc ok|FAILED, corrected <flips> of <M>'.  Not with --align, --align_shift or --gpus above 1 yet")

@@ -105,13 +105,13 @@ def resolve_requests(requests: Sequence[Request], registry: Optional[KeyedRegist
 
 
 def encode_requests(requests: Sequence[Request], message_bytes: int, ecc: Optional[str]) -> List[Request]:
-    """With ecc="conv" the requests' messages are PAYLOADS: every request comes back with its payload encoded to the `message_bytes`-byte coded message
+    """With ecc="conv" (or a punctured code, "conv23" / "conv34": more payload bytes, `ecc.capacity(M, ecc)`) the requests' messages are PAYLOADS: every request comes back with its payload encoded to the `message_bytes`-byte coded message
     (`ecc.encode`), which is what the registry, the log and the embed launch then see.  bytes must have exactly `ecc.capacity(8 message_bytes)` bytes, a
     str at most that many once encoded (zero-padded); anything else raises here, before anything runs.  ecc=None: the requests as they are."""
     if _ecc.check_code(ecc) is None:
         return list(requests)
     M = 8 * int(message_bytes)
-    cap = _ecc.capacity(M)
+    cap = _ecc.capacity(M, ecc)
     out = []
     for r in requests:
         if not isinstance(r, Request):
@@ -121,7 +121,7 @@ def encode_requests(requests: Sequence[Request], message_bytes: int, ecc: Option
             raise ValueError(f"user {r.user_id!r}: payload has {len(raw)} bytes, {message_bytes}-byte coded messages carry "
                              f"{'at most' if isinstance(r.message, str) else 'exactly'} {cap}")
         q = Request.__new__(Request)
-        q.user_id, q.key, q.nonce, q.message = r.user_id, r.key, r.nonce, _ecc.encode(raw + b"\0" * (cap - len(raw)), M)
+        q.user_id, q.key, q.nonce, q.message = r.user_id, r.key, r.nonce, _ecc.encode(raw + b"\0" * (cap - len(raw)), M, ecc)
         out.append(q)
     return out
 
@@ -216,7 +216,8 @@ def build_parser():
     p.add_argument("--dtype", default="float32", choices=_DTYPES)
     p.add_argument("--fast", action="store_true", help="fp32 inverse-CDF core (|dz| <= 1e-5)")
     p.add_argument("--ecc", default=None, choices=_ecc.CODES, help="the requests' messages are payloads of ecc.capacity(8 message_bytes) bytes (13 in a 32-byte "
-                                                                   "message): the registry and the latents carry their convolutional codeword")
+                                                                   "message; 18 with conv23 and 21 with conv34, the punctured codes of rates 2/3 and 3/4): "
+                                                                   "the registry and the latents carry their convolutional codeword")
     return p
 
 

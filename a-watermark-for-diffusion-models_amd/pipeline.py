@@ -83,7 +83,7 @@ class GaussianShadingPipeline:
         ecc="conv": the records' messages are coded payloads (`issue_latents(..., ecc="conv")`); the votes of whichever decoder was chosen go through one
         `codec.viterbi_decode` launch and the result is (what is returned without ecc, `ecc.EccRead`) -- with return_latents (that, EccRead, z).
         ecc_list=2, 4 or 8 with ecc="conv": the list read (`ecc.read_list`), an `ecc.EccListRead` in the EccRead's place; 1 is
-        today's launch."""
+        today's launch.  ecc="conv23" / "conv34": the punctured codes through the same two reads."""
         from . import ecc as E
         ecc_list = E.check_list_size(ecc_list)
         if E.check_code(ecc) is not None:
@@ -94,7 +94,7 @@ class GaussianShadingPipeline:
         def finish(res, z, score):
             if ecc is None:
                 return (*res, z) if return_latents else res
-            read = E.read_any(score.contiguous(), ecc_list)
+            read = E.read_any(score.contiguous(), ecc_list, ecc)
             return (res, read, z) if return_latents else (res, read)
 
         if robust_levels is not None:

@@ -1575,7 +1575,7 @@ def build_parser():
     p.add_argument("--pool_reliability", type=int, default=None, choices=range(1, 16), metavar="LEVELS",
                    help="with --pool: pool rows of LEVELS (1..15) reliability levels per lattice element instead of unit levels; a set then holds at most "
                         "1023 // (2^P - 1) images, P the bit length of LEVELS (68 at 15) (--l 1)")
-    p.add_argument("--ecc", default=None, choices=("conv",),
+    p.add_argument("--ecc", default=None, choices=("conv", "conv23", "conv34"),
                    help="refused by name: messages issued with --ecc conv are registered CODED and traced unchanged; with --pool or --align the payload read is "
                         "not wired yet (extract --ecc conv and detect --ecc conv read payloads)")
     p.add_argument("--strict_kernels", type=int, choices=[0, 1], default=None,

@@ -1007,6 +1007,27 @@ int gsw_viterbi_list_decode(const int32_t* score_dev, int64_t score_stride, int 
                             uint8_t* info_dev, uint8_t* message_dev, int32_t* metric_dev, int32_t* flips_dev,
                             int32_t* ok_dev, int32_t* rank_dev, int32_t* n_ok_dev, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Punctured payload codes: rates 2/3 and 3/4 of the same mother code, through both reads.  Additive: gsw_version() stays 500.
+ *
+ * rate in {0, 1, 2} = {1/2, 2/3, 3/4} ("conv", "conv23", "conv34").  The pattern has period P = rate + 1; step t keeps, in this order, c0 c1 in phase
+ * t mod P = 0, c1 in phase 1 and c0 in phase 2 (c0: 0o171, c1: 0o133; the DVB / 802.11 patterns).  N(t) = (rate + 2) (t div P) + (0, 2, 3)[t mod P] is the
+ * number of kept bits of the first t steps.  T is the largest multiple of 8 with N(T) <= M, I = T - 6, the info word has T / 8 bytes: payload
+ * (T / 8 - 3 bytes), CRC-16, 2 pad bits, the tail.  Kept bit j < N = N(T) sits at message position (j S) mod M; the M - N spare positions carry 0 when
+ * encoded and their votes are never read.  A punctured output adds nothing to a branch metric; everything else -- states, tie rule, list order,
+ * traceback, the ok rule, the int32 bound -- is gsw_viterbi_decode's and gsw_viterbi_list_decode's.
+ * Outputs as theirs, with info_dev uint8 [B, T / 8], message_dev carrying 0 at the spare positions and flips counted over the N code positions only.
+ * At rate 0 every output equals the older entry point's byte for byte.
+ * One wavefront's LDS slice, rounded up to 16 bytes: 4 M + 9 T + M + T / 8 (plain), 4 M + 256 L + 9 T L + M + T / 8 (list).
+ * GSW_ERR_BAD_ARG: what the older entry point refuses with it, and a rate outside {0, 1, 2}.  GSW_ERR_UNSUPPORTED: M > 8192 (plain); a list slice above
+ * 163 840 bytes: M above 17 104, 11 600, 7 056, 3 936 (rate 0), 14 752, 9 552, 5 600, 3 040 (rate 1) and 13 808, 8 784, 5 072, 2 736 (rate 2) at
+ * L = 1, 2, 4, 8.  In that order; every refusal happens before any launch. */
+int gsw_viterbi_decode_rate(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, int rate, uint8_t* info_dev, uint8_t* message_dev,
+                            int32_t* metric_dev, int32_t* flips_dev, int32_t* ok_dev, void* stream);
+int gsw_viterbi_list_decode_rate(const int32_t* score_dev, int64_t score_stride, int B, int message_bits, int rate, int list_size,
+                                 uint8_t* info_dev, uint8_t* message_dev, int32_t* metric_dev, int32_t* flips_dev,
+                                 int32_t* ok_dev, int32_t* rank_dev, int32_t* n_ok_dev, void* stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -13,8 +13,9 @@ __attribute__((visibility("hidden"))) thread_local int g_last_hip_error = 0;   /
 
 #include "../a-watermark-for-diffusion-models_amd/csrc/gswm_host.h"
 #include "../a-watermark-for-diffusion-models_amd/csrc/gswm_viterbi_plan.h"
-#include "../a-watermark-for-diffusion-models_amd/csrc/gswm_viterbi.inc"
 #include "../a-watermark-for-diffusion-models_amd/csrc/gswm_viterbi_list_plan.h"
+#include "../a-watermark-for-diffusion-models_amd/csrc/gswm_viterbi_rate_plan.h"
+#include "../a-watermark-for-diffusion-models_amd/csrc/gswm_viterbi.inc"
 #include "../a-watermark-for-diffusion-models_amd/csrc/gswm_viterbi_list.inc"
 
 namespace {
@@ -48,7 +49,7 @@ extern "C" __attribute__((visibility("default"))) int vlx_decode(int lds_exchang
     const ViterbiListPlan p = viterbi_list_decide(q);
     if (p.status != GSW_OK) return p.status;
     const viterbi_list::ListArgs a{score_dev, info_dev, message_dev, metric_dev, flips_dev, ok_dev, rank_dev, n_ok_dev, score_stride, B, p.M, p.T, p.I,
-                                   p.info_bytes, p.payload_bytes, p.S, p.Sinv, p.full_from, p.wave_lds};
+                                   p.info_bytes, p.payload_bytes, p.S, p.Sinv, p.full_from, p.wave_lds, p.M};
     switch (p.L) {
         case 1: return launch_either<1>(lds_exchange, p, a, (hipStream_t)stream);
         case 2: return launch_either<2>(lds_exchange, p, a, (hipStream_t)stream);
